@@ -9,7 +9,8 @@ gan_inference_cifar10.py (32x32x3, BATCH_SIZE=64) with the one MODE of that scri
 steps, each critic step with the penalty's double backward, and consumes 6 minibatches; `value` counts BATCH_SIZE images per iteration
 as the reference's own iteration counter does.  Per-GPU batch stays 64 as N grows (weak scaling).
 
-The one JSON line also carries `variants`: the other BASELINE configurations, each measured in a process of its own at N = 1
+A plain run measures the headline workload and nothing else.  With --full the one JSON line also carries the repeat windows, the roofline
+(per-kernel figures), the CPU baseline and `variants`: the other BASELINE configurations, each measured in a process of its own at N = 1
 (`variant_leg`; GGAN_BENCH_VARIANTS_IN_PROCESS=1: behind the headline in this process, as rounds 2-5 did), each with its own ms_per_step, algorithmic GFLOP, roofline (dominant kernel) and cpu_baseline:
   ali                gan_inference_cifar10.py at the script's default MODE='ali' ("G+D", CRITIC_ITERS=1: the headline of rounds 1-4)
   gmgan-cifar10-K30  gmgan_inference_cifar10.py with the script's N_COMS=30;  gmgan-cifar10-K10: BASELINE configs[2] (K=10)
@@ -17,7 +18,7 @@ The one JSON line also carries `variants`: the other BASELINE configurations, ea
   ssgan-moving-mnist ssgan_inference_moving_mnist.py 64x64 T=16 bs=32 (configs[4])
   ssgan-moving-mnist-3dcnn  the same script with MODE='ali', ALI_MODE='3dcnn' (the Conv3D sequence critic, :352-405)
 
-  python bench.py --gpus 1 --steps 200 --warmup 20
+  python bench.py --gpus 1 --steps 200 --warmup 20 [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port P bench.py --gpus 8 ...
 """
 import argparse
@@ -82,6 +83,23 @@ def _build_id():
     return build.build_id()
 
 
+def native_library():
+    """libggan.so for this run, bound symbol by symbol (raises if it is missing or stale: no CPU path).  A library whose stamp matches
+    the sources is loaded as it is -- the benchmark may run as a user who cannot write to the tree that build() filled, and build()
+    takes its lock file in the package directory even when there is nothing to compile; anything else is built first."""
+    from graphical_gan_amd import build, _lib
+    stamp = None
+    try:
+        with open(build.STAMP) as f:
+            stamp = f.read().strip()
+    except OSError:
+        pass
+    if not (os.path.exists(build.LIB) and stamp == build._digest()):
+        build.build()
+    import graphical_gan_amd  # noqa: F401  (registers the tflib alias)
+    return _lib.load()
+
+
 def host_cores():
     """CPUs this process may actually use: scheduler affinity capped by the cgroup CPU quota (the GPU boxes expose 256 logical
     CPUs but grant 16; running the CPU baseline on 256 threads measured 0.6 img/s instead of 670)."""
@@ -93,6 +111,33 @@ def host_cores():
     except (OSError, ValueError):
         pass
     return n
+
+
+DUMP_BYTES = 64 << 20      # --dump-outputs: what the written arrays may add up to
+
+
+def dump_outputs(dirname, costs, params, budget=DUMP_BYTES):
+    """--dump-outputs: what the timed path hands its caller after its last step -- the step's costs and the weights it leaves
+    (Adam-updated parameters, BatchNorm moving statistics) -- as <dirname>/<name>.npy, costs float64, weights float32
+    (param.<registry name>.npy).  Weights over the budget are represented by the same fixed, seeded sample of each tensor's
+    elements (flattened, in index order), so that two builds of the same arguments compare element for element.  -> file names"""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    written = []
+    for k in sorted(costs):
+        np.save(os.path.join(dirname, k + '.npy'), np.asarray(float(costs[k]), dtype=np.float64))
+        written.append(k + '.npy')
+    total = 4 * sum(p.numel() for p in params.values())
+    frac = min(1.0, (budget - (1 << 20)) / max(total, 1))      # (1 MB kept for the costs and the .npy headers)
+    rng = np.random.default_rng(0)
+    for name in sorted(params):
+        a = params[name].detach().float().cpu().numpy()
+        if frac < 1.0:
+            flat = a.reshape(-1)
+            a = flat[np.sort(rng.choice(flat.size, max(1, int(flat.size * frac)), replace=False))]
+        np.save(os.path.join(dirname, 'param.%s.npy' % name), np.ascontiguousarray(a, dtype=np.float32))
+        written.append('param.%s.npy' % name)
+    return written
 
 
 def ssgan_gflop_per_iteration(cfg):
@@ -360,6 +405,9 @@ def run_workload(spec, args, env, steps, warmup, top_kernels=None):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     finite = all(np.isfinite(float(v)) for v in last.values())
+    if args.dump_outputs and rank == 0 and spec.get('key') == 'headline':
+        # (before anything else replays the step: the costs of a graph replay live in the graph's own buffers)
+        dump_outputs(args.dump_outputs, last, lib.named_params())
     # run-to-run spread of the same K-step window (not part of `value`: the contract's timed region is the one above)
     repeats = []
     for _ in range(args.repeats if spec.get('key') == 'headline' else 0):
@@ -764,17 +812,19 @@ def _flush_c_stdio():
         pass
 
 
-def emit(full):
+def emit(full, record=True):
     """Full record -> gpurun_out/bench_full.json (GGAN_BENCH_FULL overrides; merged back from the GPU box), compact line -> the
     last line of stdout."""
     path = os.environ.get('GGAN_BENCH_FULL') or os.path.join(ROOT, 'gpurun_out', 'bench_full.json')
-    try:
-        os.makedirs(os.path.dirname(path), exist_ok=True)
-        with open(path, 'w') as f:
-            json.dump(full, f, indent=1)
-        full['_full_path'] = os.path.relpath(path, ROOT)
-    except OSError:
-        full['_full_path'] = None
+    full['_full_path'] = None
+    if record:                                             # (--full only: a plain run prints its line and nothing else)
+        try:
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+            with open(path, 'w') as f:
+                json.dump(full, f, indent=1)
+            full['_full_path'] = os.path.relpath(path, ROOT)
+        except OSError:
+            pass
     sys.stdout.flush()
     _flush_c_stdio()
     print(compact_line(full))
@@ -826,7 +876,7 @@ def variant_leg(v, args, vsteps, warmup):
     tmp.close()
     env = dict(os.environ, GGAN_BENCH_NO_DP_LEG='1', GGAN_BENCH_FULL=tmp.name)
     env = {k: val for k, val in env.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
-    cmd = [sys.executable, os.path.abspath(__file__), '--gpus', '1', '--steps', str(vsteps), '--warmup', str(warmup), '--no-variants',
+    cmd = [sys.executable, os.path.abspath(__file__), '--gpus', '1', '--steps', str(vsteps), '--warmup', str(warmup), '--full', '--no-variants',
            '--repeats', '0', '--dataset', v['dataset']]
     if v.get('mode'):
         cmd += ['--mode', v['mode']]
@@ -877,13 +927,26 @@ def main():
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-kernel-profile', action='store_true')
     ap.add_argument('--no-variants', action='store_true', help='headline workload only')
-    ap.add_argument('--repeats', type=int, default=3, help='extra repetitions of the K-step window after the timed one (spread; headline only)')
-    ap.add_argument('--variants', default=None, help='comma-separated subset of: ' + ', '.join(v['key'] for v in VARIANTS))
-    ap.add_argument('--variant-steps', type=int, default=None, help='timed iterations per variant (default: min(steps, 60))')
+    ap.add_argument('--repeats', type=int, default=None, help='extra repetitions of the K-step window after the timed one (spread; headline only; '
+                    'default 3 with --full, else 0)')
+    ap.add_argument('--variants', default=None, help='--full: comma-separated subset of: ' + ', '.join(v['key'] for v in VARIANTS))
+    ap.add_argument('--variant-steps', type=int, default=None, help='--full: timed iterations per variant (default: min(steps, 60))')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline figure does not need: repeat windows, per-kernel / roofline figures, the CPU baseline, '
+                    'the other BASELINE configurations, the data-parallel legs, and the full record')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="after the timed steps, write the costs and weights of the headline's last step as DIR/<name>.npy")
     ap.add_argument('--no-ring', action='store_true', help='minibatches through the staging buffer (one device copy per step) instead of read in place from the resident ring')
     ap.add_argument('--host-feed', action='store_true',
                     help='minibatches start in host memory (pinned double-buffered H->D copies): the PCIe-inclusive rate')
     args = ap.parse_args()
+    if not args.full:
+        if args.variants or args.variant_steps:
+            ap.error('--variants / --variant-steps need --full')
+        # a plain run: set up, warm up, time the steps, print the line
+        args.no_cpu_baseline = args.no_kernel_profile = args.no_variants = True
+    if args.repeats is None:
+        args.repeats = 3 if args.full else 0
     diag0 = diag_env()
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ and 'RANK' not in os.environ and not os.environ.get('GGAN_BENCH_CHILD'):
@@ -918,8 +981,7 @@ def main():
 
     if os.environ.get('GGAN_BENCH_ABORT_TEST') == '%s:%s' % (os.environ.get('GGAN_DP_GRAPH', '1'), rank):
         os.abort()                                         # (tests: a rank that dies the way a failed captured collective kills it)
-    import __graft_entry__ as ge
-    ge.build()
+    native_library()
     env = dict(dev=dev, world=world, rank=rank)
 
     head_spec = dict(key='headline', dataset=args.dataset, mode=args.mode, ssgan_mode=args.ssgan_mode, n_coms=args.n_coms,
@@ -1001,7 +1063,7 @@ def main():
         out['variants'] = variants
         if dp_n1 is not None:
             out['dp_schedule_n1'] = dp_n1
-        emit(out)
+        emit(out, record=args.full)
 
 
 if __name__ == '__main__':

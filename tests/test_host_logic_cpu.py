@@ -381,3 +381,61 @@ def test_bench_static_tables_are_keyed_by_workload_not_by_role():
     for v in bench.VARIANTS:
         assert v['key'] in tab or v['key'] == 'gmgan-cifar10-K30', v['key']      # (K = 30 reads the K = 10 table: same launch shapes)
     assert 'headline' in tab and tab.get('_build') and tab.get('_tag')
+
+
+def test_bench_dump_outputs_sample_is_fixed_and_within_budget(tmp_path):
+    """bench.py --dump-outputs: costs as float64 scalars, weights as float32 -- whole while they fit the budget, else the same seeded
+    sample of every tensor on every run (two builds compare element for element), and the files stay inside the budget."""
+    import importlib
+    import os
+    import sys
+    import torch
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    bench = importlib.import_module('bench')
+    g = torch.Generator().manual_seed(0)
+    params = {'A.W': torch.randn(300, 200, generator=g), 'B.b': torch.randn(7, generator=g), 'C.Filters': torch.randn(64, 3, 5, 5, generator=g)}
+    costs = {'gen_cost': torch.tensor(1.25), 'disc_cost': torch.tensor(-0.5)}
+    whole = bench.dump_outputs(str(tmp_path / 'whole'), costs, params)
+    assert sorted(whole) == ['disc_cost.npy', 'gen_cost.npy', 'param.A.W.npy', 'param.B.b.npy', 'param.C.Filters.npy']
+    c = np.load(tmp_path / 'whole' / 'gen_cost.npy')
+    assert c.dtype == np.float64 and c.shape == () and float(c) == 1.25
+    w = np.load(tmp_path / 'whole' / 'param.C.Filters.npy')
+    assert w.dtype == np.float32 and np.array_equal(w, params['C.Filters'].numpy())
+    budget = (1 << 20) + 4 * 10000                                      # (room for a sixth of the 65k weights)
+    runs = []
+    for d in ('s1', 's2'):
+        bench.dump_outputs(str(tmp_path / d), costs, params, budget=budget)
+        runs.append({f: np.load(tmp_path / d / f) for f in sorted(os.listdir(tmp_path / d))})
+        assert sum(os.path.getsize(tmp_path / d / f) for f in os.listdir(tmp_path / d)) <= budget
+    for f, a in runs[0].items():
+        assert np.array_equal(a, runs[1][f]), f
+    a = runs[0]['param.A.W.npy']
+    assert a.dtype == np.float32 and a.ndim == 1 and 0 < a.size < 60000
+    assert np.isin(a, params['A.W'].numpy().reshape(-1)).all()
+
+
+def test_bench_variants_need_full():
+    """the other BASELINE configurations are measured with --full only: asking for them in a plain run is an error, not a silent no-op"""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--variants', 'ali'], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and '--full' in r.stderr, r.stderr[-500:]
+
+
+def test_bench_loads_a_current_library_without_writing(lib_built, monkeypatch):
+    """bench.py may run as a user who cannot write to the tree build() filled: a library whose stamp matches the sources is loaded as it
+    is, without build() (which takes a lock file in the package directory even when there is nothing to compile)."""
+    import importlib
+    import os
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    bench = importlib.import_module('bench')
+    from graphical_gan_amd import build, _lib
+
+    def refuse(*a, **k):
+        raise PermissionError('build() called although the library is current')
+    monkeypatch.setattr(build, 'build', refuse)
+    L = bench.native_library()
+    assert L is _lib.load() and L.ggan_version() == _lib.ABI_VERSION

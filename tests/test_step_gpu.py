@@ -426,7 +426,7 @@ def test_bench_contract_line_single_and_two_ranks(gpu):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0')
     env['GGAN_BENCH_CPU_BUDGET_S'] = '2'
-    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '6', '--warmup', '2', '--variant-steps', '4'],
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '6', '--warmup', '2', '--full', '--variant-steps', '4'],
                        capture_output=True, text=True, timeout=1500, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     # the driver keeps the tail of stdout: the LAST line must parse on its own and stay well under 4 KB
@@ -479,7 +479,7 @@ def test_bench_contract_line_single_and_two_ranks(gpu):
     # exactly as the driver invokes it: no launcher around it -- bench.py starts its own ranks (round-3 review: this form used to exit)
     env2 = {k: v for k, v in env2.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '6', '--warmup', '2',
-                        '--variants', 'gmgan-cifar10-K10', '--variant-steps', '4'],
+                        '--full', '--variants', 'gmgan-cifar10-K10', '--variant-steps', '4'],
                        capture_output=True, text=True, timeout=900, env=env2, cwd=root)
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
@@ -517,6 +517,29 @@ def test_bench_line_stays_last_when_rccl_writes_to_stdout(gpu):
     assert d['n_gpus'] == 1 and d['value'] > 0 and len([l for l in lines if l.startswith('{')]) == 1
 
 
+def test_bench_plain_run_times_the_headline_only_and_dumps_its_outputs(gpu, tmp_path):
+    """bench.py without --full: the headline workload's K timed steps and its line, none of what --full adds; --dump-outputs writes the
+    costs and weights of the last timed step (float64 / float32 .npy, at most 64 MB in all)."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / 'outputs'
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '5', '--warmup', '2', '--dump-outputs', str(out)],
+                       capture_output=True, text=True, timeout=600, env=dict(os.environ, GGAN_BENCH_FULL=str(tmp_path / 'full.json')), cwd=root)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads(r.stdout.rstrip('\n').splitlines()[-1])
+    assert d['steps'] == 5 and d['warmup'] == 2 and d['ms_per_step'] > 0 and d['value'] > 0 and 'G+D+GP' in d['metric']
+    assert abs(d['value'] - 64 * 1e3 / d['ms_per_step']) <= 1e-3 * d['value'] + 0.1
+    assert d['variants'] == [] and d['cpu_baseline'] is None and d['roofline'] is None and 'repeat_ms_per_step' not in d
+    assert d['full_record'] is None and not (tmp_path / 'full.json').exists()
+    files = sorted(os.listdir(out))
+    assert 'gen_cost.npy' in files and 'disc_cost.npy' in files and len([f for f in files if f.startswith('param.')]) > 20
+    assert sum(os.path.getsize(out / f) for f in files) <= 64 << 20
+    for f in files:
+        a = np.load(out / f)
+        assert a.dtype == (np.float64 if f.endswith('_cost.npy') else np.float32) and np.isfinite(a).all(), f
+    assert d['config']['finite_costs']
+
+
 def test_rccl_exchange_inside_the_step_graph_one_rank_rehearsal(gpu):
     """The driver's N > 1 launch puts the gradient exchange (RCCL all-reduce) INSIDE the captured graphs.  One rank over RCCL is
     enough to rehearse that on a single-GPU box (GGAN_FORCE_ALLREDUCE): the exchange goes through the directly bound communicator
@@ -528,7 +551,7 @@ def test_rccl_exchange_inside_the_step_graph_one_rank_rehearsal(gpu):
     port = 29400 + (os.getpid() % 200)
     r = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr', '127.0.0.1',
                         '--master-port', str(port), os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '6', '--warmup', '2',
-                        '--variants', 'ali', '--variant-steps', '3', '--no-cpu-baseline', '--repeats', '0'],
+                        '--full', '--variants', 'ali', '--variant-steps', '3', '--no-cpu-baseline', '--repeats', '0'],
                        capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert r.returncode == 0, (r.stdout[-500:], r.stderr[-3000:])
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][0])
