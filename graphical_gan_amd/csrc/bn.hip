@@ -526,7 +526,7 @@ int ggan_bn_bwd_act(const float* x, const float* gy, const float* y, int y_act, 
     hipStream_t s = (hipStream_t)stream;
     const GyMask mk{y_act != GGAN_ACT_NONE ? y : nullptr, y_act, y_alpha};
     const double bytes = 20.0 * N * C * HW;
-    const bool v4 = (HW & 3) == 0 && ((((uintptr_t)x) | ((uintptr_t)gy) | ((uintptr_t)gx) | ((uintptr_t)mk.ref)) & 15) == 0 && !getenv("GGAN_BN_SCALAR");
+    const bool v4 = (HW & 3) == 0 && ((((uintptr_t)x) | ((uintptr_t)gy) | ((uintptr_t)gx) | ((uintptr_t)mk.ref)) & 15) == 0;
     if (HW > 1 && v4 && N * HW <= 16 * 256) {
         GGAN_LAUNCH("bn_bwd_nchw", 0, 12.0 * N * C * HW, bn_bwd_nchw_reg4_k<256>, dim3(C), dim3(256), 0, s, x, gy, mk, scale, save_mean, save_invstd, gx, gscale, goffset, gx_chansum, N, C, HW,
                     make_fastdiv((uint32_t)HW));

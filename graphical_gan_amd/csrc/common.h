@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 #include <string>
 #include "../../include/ggan.h"
@@ -29,15 +30,15 @@ struct ProfScope {
     int idx_;
 };
 int check_launch(const char* name);
-// Timing experiments only (tools/criticality.sh): kernels whose name contains one of the ';'-separated substrings of
+// Timing experiments only: kernels whose name contains one of the ';'-separated substrings of
 // GGAN_SKIP_KERNELS are not launched at all.  Results are garbage; what the step then gains is that kernel's share of the critical path.
 bool launch_skipped(const char* name);
 // debugging aid: GGAN_TRACE_LAUNCHES=1 prints one stderr line per launch (name, grid, block, dynamic LDS, flops)
 void trace_launch(const char* name, dim3 grid, dim3 block, size_t shmem, double flops);
 
 // LAUNCH(name, flops, bytes, kernel, grid, block, shmem, stream, args...)
-// (GGAN_SKIP_KERNELS is compiled in only with -DGGAN_DIAG -- tools/variant_lib.sh builds such a library for tools/criticality*.sh; the
-//  product library has no switch that silently drops launches)
+// (GGAN_SKIP_KERNELS is compiled in only with -DGGAN_DIAG -- build.py adds it under GGAN_BUILD_DIAG=1; the product library has
+//  no switch that silently drops launches)
 #ifdef GGAN_DIAG
 #define GGAN_LAUNCH_SKIPPED(name) ggan::launch_skipped(name)
 #else
@@ -53,6 +54,11 @@ void trace_launch(const char* name, dim3 grid, dim3 block, size_t shmem, double 
     if (ggan::check_launch(name)) return -2
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+// an integer environment switch (INTEGRATION.md section 6 lists them), dflt when it is unset
+static inline int env_int(const char* name, int dflt) {
+    const char* v = getenv(name);
+    return v ? atoi(v) : dflt;
+}
 // true the first time it is called with `seen` on the current device: hipFuncSetAttribute(MaxDynamicSharedMemorySize) is per device,
 // a process-wide "once" flag would leave a second device of the same process on the 64 KB default
 static inline bool first_on_device(std::atomic<unsigned long long>& seen) {

@@ -19,6 +19,8 @@ int conv_wgrad_naive(const ggan_conv_geom& g, const float* x, const float* gy, G
 
 // MFMA paths: return 1 when the geometry is not covered (caller falls back to the naive kernel),
 // 0 on success, <0 on error.
+// Workgroups the forward / data-gradient launches are planned for when ggan_conv_geom.plan_wgs is 0 (~one per CU)
+constexpr int kTargetWgs = 200;
 int conv_fwd_mfma(const ggan_conv_geom& g, const float* x, const float* w, const float* bias, float* y, int act,
                   float alpha, void* ws, size_t ws_bytes, hipStream_t s);
 int conv_dgrad_mfma(const ggan_conv_geom& g, const float* gy, GyMask m, const float* w, const float* bias, float* gx,

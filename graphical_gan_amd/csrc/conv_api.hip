@@ -58,7 +58,7 @@ int ggan_conv2d_fwd_cast_ring(const ggan_conv_geom* g, const int32_t* ring, int 
                               float alpha, ggan_stream_t stream) {
     if (check_geom(g)) return -1;
     GGAN_CHECK_ARG(ring && x_out && w && y && nslots > 0, "bad argument");
-    if ((g->plan_flags & GGAN_PLAN_PLAIN) || getenv("GGAN_NAIVE_FWD") || getenv("GGAN_NO_CAST_FUSION")) return 1;
+    if ((g->plan_flags & GGAN_PLAN_PLAIN) || getenv("GGAN_NAIVE_FWD")) return 1;
     ThinCastSrc c;
     c.ring = ring; c.ctr_a = ctr_a; c.ctr_b = ctr_b; c.noise = noise; c.x_out = x_out; c.nslots = nslots; c.offset = offset; c.div = div; c.mul = mul;
     return conv_fwd_thin(*g, nullptr, w, bias, y, act, alpha, (hipStream_t)stream, &c);
@@ -201,19 +201,14 @@ int ggan_conv2d_fwd_masked(const ggan_conv_geom* g, const float* x, const float*
                            float ref_alpha, void* ws, size_t ws_bytes, ggan_stream_t stream) {
     if (check_geom(g)) return -1;
     GGAN_CHECK_ARG(x && w && y && yref, "null pointer");
-    if ((g->plan_flags & GGAN_PLAN_PLAIN) || getenv("GGAN_NAIVE_FWD") || getenv("GGAN_NO_FWD_MASK")) return 1;
+    if ((g->plan_flags & GGAN_PLAN_PLAIN) || getenv("GGAN_NAIVE_FWD")) return 1;
     if ((((uintptr_t)yref) & 15) != 0) return 1;
     // (thin first layers: the thin-channel forward kernel with the mask in its epilogue since round 6 -- K = 25 * Ci instead of 25 x a padded
-    //  16-channel chunk; rounds 3-5 ran the padded-channel MFMA launch with the mask.  GGAN_FWD_MASK_THIN=0 selects that one,
-    //  GGAN_NO_FWD_MASK_THIN the unfused pair conv_thin.hip + act_bwd)
-    if (g->Ci <= 4 && getenv("GGAN_NO_FWD_MASK_THIN")) return 1;
+    //  16-channel chunk; rounds 3-5 ran the padded-channel MFMA launch with the mask)
     OutMask M{yref, ref_act, ref_alpha, false};
     if (g->Ci <= 4 && (ref_act == GGAN_ACT_LRELU || ref_act == GGAN_ACT_RELU)) {
-        const char* e = getenv("GGAN_FWD_MASK_THIN");
-        if (!e || atoi(e) != 0) {
-            const int r = conv_fwd_thin(*g, x, w, nullptr, y, GGAN_ACT_NONE, 0.f, (hipStream_t)stream, nullptr, &M);
-            if (r <= 0) return r;
-        }
+        const int r = conv_fwd_thin(*g, x, w, nullptr, y, GGAN_ACT_NONE, 0.f, (hipStream_t)stream, nullptr, &M);
+        if (r <= 0) return r;
     }
     g_out_mask = &M;
     const int rc = conv_fwd_mfma(*g, x, w, nullptr, y, GGAN_ACT_NONE, 0.f, ws, ws ? ws_bytes : 0, (hipStream_t)stream);

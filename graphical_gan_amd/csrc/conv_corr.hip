@@ -89,12 +89,6 @@ struct CorrParams {
     CorrClass cls[4];
 };
 
-// Compile-time ablations for timing experiments (tools/variant_lib.sh builds a second libggan.so with -DGGAN_ABL=bits and
-// tools/stamps.py prints the per-workgroup phase times): 1 = no staging inside the chunk loop, 4 = MFMAs on register constants
-// instead of LDS fragments.  0 in the product build: the branches fold away.
-#ifndef GGAN_ABL
-#define GGAN_ABL 0
-#endif
 // One chunk's MFMAs for one class.  hipcc emits "ds_read; s_waitcnt lgkmcnt(0); v_mfma; v_mfma" for the straightforward loop
 // (operands fetched right before use into the same four registers), which leaves the matrix pipe idle for one LDS latency
 // per MFMA pair (measured: 5300 cycles per chunk where the MFMAs need 3200).  Here the operands of MFMA pair s+2,s+3 are
@@ -144,7 +138,6 @@ __device__ __forceinline__ void mma_taps_wd(const float* __restrict__ xs, const 
         float a[NT], b[NT];
         auto load = [&](int s) {
             const int i = s / TW, j = s - i * TW;
-            if (GGAN_ABL & 4) { a[s] = __int_as_float(wfrag + s); b[s] = __int_as_float(xfrag + s); return; }
             a[s] = ws[s * TS + wfrag];
             b[s] = xs[xfrag + DI * (i * SCp + j)];
         };
@@ -941,11 +934,6 @@ __global__ void splitk_reduce_small_k(const float* __restrict__ partial, int SK,
     }
 }
 
-int env_int(const char* name, int dflt) {
-    const char* v = getenv(name);
-    return v ? atoi(v) : dflt;
-}
-
 struct WaveCfg { int WM, WN, KS, PW; };
 // fwd: 25 taps per chunk-channel-pair; dgrad class pairs carry only 12-13 taps, so they stage twice as many channels per
 // chunk (PW doubled) to keep ~25+ MFMAs per wave between barriers
@@ -986,7 +974,7 @@ void allow_big_lds(K kernel) {
 }
 
 // wave layouts of the data-gradient kinds that have a 16-byte-unit variant (launch_cfg)
-bool dgrad_x4_cfg(int mode, int cfg) { return mode == 1 ? (cfg == 4 || cfg == 5 || cfg == 7) : (cfg == 5 || cfg == 6 || cfg == 7); }
+bool dgrad_x4_cfg(int mode, int cfg) { return mode == 1 ? (cfg == 4 || cfg == 5) : (cfg == 5 || cfg == 6 || cfg == 7); }
 
 template <int MODE>
 int launch_cfg(int cfg, const CorrParams& P, dim3 grid, size_t shmem, hipStream_t s, const char* name, double fl) {
@@ -994,19 +982,16 @@ int launch_cfg(int cfg, const CorrParams& P, dim3 grid, size_t shmem, hipStream_
     const double ab = (double)P.in_bytes + (double)P.w_bytes + 4.0 * (double)P.out_elems;
     static std::atomic<unsigned long long> once{0};
     if (first_on_device(once)) {   // double-buffered staging can exceed the 64 KiB default dynamic-LDS limit
-        allow_big_lds(corr_kernel<0, 2, 2, 1, 2>); allow_big_lds(corr_kernel<0, 2, 1, 2, 2>); allow_big_lds(corr_kernel<0, 1, 1, 4, 1>);
-        allow_big_lds(corr_kernel<1, 2, 2, 1, 4>); allow_big_lds(corr_kernel<1, 2, 1, 2, 4>); allow_big_lds(corr_kernel<1, 1, 1, 4, 2>);
-        allow_big_lds(corr_kernel<0, 1, 1, 4, 2>); allow_big_lds(corr_kernel<1, 1, 1, 4, 4>);
+        allow_big_lds(corr_kernel<0, 2, 1, 2, 2>); allow_big_lds(corr_kernel<1, 2, 1, 2, 4>);
         allow_big_lds(corr_kernel<0, 2, 1, 4, 1>); allow_big_lds(corr_kernel<0, 1, 1, 8, 1>);
         allow_big_lds(corr_kernel<1, 2, 1, 4, 2>); allow_big_lds(corr_kernel<1, 1, 1, 8, 1>);
         allow_big_lds(corr_kernel<0, 2, 2, 2, 1>); allow_big_lds(corr_kernel<1, 2, 2, 2, 2>);
-        allow_big_lds(corr_kernel<2, 2, 2, 1, 2>); allow_big_lds(corr_kernel<2, 2, 1, 2, 2>); allow_big_lds(corr_kernel<2, 1, 1, 4, 1>);
-        allow_big_lds(corr_kernel<2, 1, 1, 4, 2>); allow_big_lds(corr_kernel<2, 2, 1, 4, 1>); allow_big_lds(corr_kernel<2, 1, 1, 8, 1>);
+        allow_big_lds(corr_kernel<2, 2, 1, 2, 2>); allow_big_lds(corr_kernel<2, 2, 1, 4, 1>); allow_big_lds(corr_kernel<2, 1, 1, 8, 1>);
         allow_big_lds(corr_kernel<2, 2, 2, 2, 1>); allow_big_lds(corr_kernel<0, 2, 1, 4, 2>); allow_big_lds(corr_kernel<2, 2, 1, 4, 2>);
-        allow_big_lds(corr_kernel<0, 4, 1, 2, 2>); allow_big_lds(corr_kernel<2, 4, 1, 2, 2>); allow_big_lds(corr_kernel<1, 1, 1, 8, 2>);
+        allow_big_lds(corr_kernel<0, 4, 1, 2, 2>); allow_big_lds(corr_kernel<2, 4, 1, 2, 2>);
         allow_big_lds(corr_kernel<0, 2, 1, 4, 1, true>); allow_big_lds(corr_kernel<0, 1, 1, 8, 1, true>); allow_big_lds(corr_kernel<0, 2, 2, 2, 1, true>);
-        allow_big_lds(corr_kernel<0, 2, 1, 4, 2, true>); allow_big_lds(corr_kernel<0, 4, 1, 2, 2, true>);
-        allow_big_lds(corr_kernel<1, 2, 1, 4, 2, true>); allow_big_lds(corr_kernel<1, 1, 1, 8, 1, true>); allow_big_lds(corr_kernel<1, 1, 1, 8, 2, true>);
+        allow_big_lds(corr_kernel<0, 4, 1, 2, 2, true>);
+        allow_big_lds(corr_kernel<1, 2, 1, 4, 2, true>); allow_big_lds(corr_kernel<1, 1, 1, 8, 1, true>);
         allow_big_lds(corr_kernel<2, 1, 1, 8, 1, true>); allow_big_lds(corr_kernel<2, 2, 1, 4, 2, true>); allow_big_lds(corr_kernel<2, 2, 2, 2, 1, true>);
     }
     if (shmem > 160 * 1024) { set_error("%s: LDS request %zu too large", name, shmem); return -3; }
@@ -1016,7 +1001,6 @@ int launch_cfg(int cfg, const CorrParams& P, dim3 grid, size_t shmem, hipStream_
                 case 4: GGAN_LAUNCH("corr_kernel<0, 2, 1, 4, 1, true>", fl, ab, (corr_kernel<0, 2, 1, 4, 1, true>), grid, dim3(512), shmem, s, P); break;
                 case 5: GGAN_LAUNCH("corr_kernel<0, 1, 1, 8, 1, true>", fl, ab, (corr_kernel<0, 1, 1, 8, 1, true>), grid, dim3(512), shmem, s, P); break;
                 case 6: GGAN_LAUNCH("corr_kernel<0, 2, 2, 2, 1, true>", fl, ab, (corr_kernel<0, 2, 2, 2, 1, true>), grid, dim3(512), shmem, s, P); break;
-                case 7: GGAN_LAUNCH("corr_kernel<0, 2, 1, 4, 2, true>", fl, ab, (corr_kernel<0, 2, 1, 4, 2, true>), grid, dim3(512), shmem, s, P); break;
                 case 8: GGAN_LAUNCH("corr_kernel<0, 4, 1, 2, 2, true>", fl, ab, (corr_kernel<0, 4, 1, 2, 2, true>), grid, dim3(512), shmem, s, P); break;
                 default: set_error("%s: no 16-byte-unit variant of wave layout %d", name, cfg); return -3;
             }
@@ -1038,33 +1022,28 @@ int launch_cfg(int cfg, const CorrParams& P, dim3 grid, size_t shmem, hipStream_
             switch (cfg) {
                 case 4: GGAN_LAUNCH("corr_kernel<1, 2, 1, 4, 2, true>", fl, ab, (corr_kernel<1, 2, 1, 4, 2, true>), grid, dim3(512), shmem, s, P); break;
                 case 5: GGAN_LAUNCH("corr_kernel<1, 1, 1, 8, 1, true>", fl, ab, (corr_kernel<1, 1, 1, 8, 1, true>), grid, dim3(512), shmem, s, P); break;
-                default: GGAN_LAUNCH("corr_kernel<1, 1, 1, 8, 2, true>", fl, ab, (corr_kernel<1, 1, 1, 8, 2, true>), grid, dim3(512), shmem, s, P); break;
+                default: set_error("%s: no 16-byte-unit variant of wave layout %d", name, cfg); return -3;
             }
             return 0;
         }
     }
     if constexpr (MODE == 0 || MODE == 2) {
         switch (cfg) {
-            case 0: GGAN_LAUNCH((MODE == 0 ? "corr_kernel<0, 2, 2, 1, 2, false>" : "corr_kernel<2, 2, 2, 1, 2, false>"), fl, ab, (corr_kernel<MODE, 2, 2, 1, 2>), grid, dim3(256), shmem, s, P); break;
             case 1: GGAN_LAUNCH((MODE == 0 ? "corr_kernel<0, 2, 1, 2, 2, false>" : "corr_kernel<2, 2, 1, 2, 2, false>"), fl, ab, (corr_kernel<MODE, 2, 1, 2, 2>), grid, dim3(256), shmem, s, P); break;
-            case 2: GGAN_LAUNCH((MODE == 0 ? "corr_kernel<0, 1, 1, 4, 1, false>" : "corr_kernel<2, 1, 1, 4, 1, false>"), fl, ab, (corr_kernel<MODE, 1, 1, 4, 1>), grid, dim3(256), shmem, s, P); break;
-            case 3: GGAN_LAUNCH((MODE == 0 ? "corr_kernel<0, 1, 1, 4, 2, false>" : "corr_kernel<2, 1, 1, 4, 2, false>"), fl, ab, (corr_kernel<MODE, 1, 1, 4, 2>), grid, dim3(256), shmem, s, P); break;
             case 4: GGAN_LAUNCH((MODE == 0 ? "corr_kernel<0, 2, 1, 4, 1, false>" : "corr_kernel<2, 2, 1, 4, 1, false>"), fl, ab, (corr_kernel<MODE, 2, 1, 4, 1>), grid, dim3(512), shmem, s, P); break;
             case 5: GGAN_LAUNCH((MODE == 0 ? "corr_kernel<0, 1, 1, 8, 1, false>" : "corr_kernel<2, 1, 1, 8, 1, false>"), fl, ab, (corr_kernel<MODE, 1, 1, 8, 1>), grid, dim3(512), shmem, s, P); break;
             case 6: GGAN_LAUNCH((MODE == 0 ? "corr_kernel<0, 2, 2, 2, 1, false>" : "corr_kernel<2, 2, 2, 2, 1, false>"), fl, ab, (corr_kernel<MODE, 2, 2, 2, 1>), grid, dim3(512), shmem, s, P); break;
             case 7: GGAN_LAUNCH((MODE == 0 ? "corr_kernel<0, 2, 1, 4, 2, false>" : "corr_kernel<2, 2, 1, 4, 2, false>"), fl, ab, (corr_kernel<MODE, 2, 1, 4, 2>), grid, dim3(512), shmem, s, P); break;
-            default: GGAN_LAUNCH((MODE == 0 ? "corr_kernel<0, 4, 1, 2, 2, false>" : "corr_kernel<2, 4, 1, 2, 2, false>"), fl, ab, (corr_kernel<MODE, 4, 1, 2, 2>), grid, dim3(512), shmem, s, P); break;
+            case 8: GGAN_LAUNCH((MODE == 0 ? "corr_kernel<0, 4, 1, 2, 2, false>" : "corr_kernel<2, 4, 1, 2, 2, false>"), fl, ab, (corr_kernel<MODE, 4, 1, 2, 2>), grid, dim3(512), shmem, s, P); break;
+            default: set_error("%s: no variant of wave layout %d", name, cfg); return -3;
         }
     } else {
         switch (cfg) {
-            case 0: GGAN_LAUNCH("corr_kernel<1, 2, 2, 1, 4, false>", fl, ab, (corr_kernel<1, 2, 2, 1, 4>), grid, dim3(256), shmem, s, P); break;
             case 1: GGAN_LAUNCH("corr_kernel<1, 2, 1, 2, 4, false>", fl, ab, (corr_kernel<1, 2, 1, 2, 4>), grid, dim3(256), shmem, s, P); break;
-            case 2: GGAN_LAUNCH("corr_kernel<1, 1, 1, 4, 2, false>", fl, ab, (corr_kernel<1, 1, 1, 4, 2>), grid, dim3(256), shmem, s, P); break;
-            case 3: GGAN_LAUNCH("corr_kernel<1, 1, 1, 4, 4, false>", fl, ab, (corr_kernel<1, 1, 1, 4, 4>), grid, dim3(256), shmem, s, P); break;
             case 4: GGAN_LAUNCH("corr_kernel<1, 2, 1, 4, 2, false>", fl, ab, (corr_kernel<1, 2, 1, 4, 2>), grid, dim3(512), shmem, s, P); break;
             case 5: GGAN_LAUNCH("corr_kernel<1, 1, 1, 8, 1, false>", fl, ab, (corr_kernel<1, 1, 1, 8, 1>), grid, dim3(512), shmem, s, P); break;
             case 6: GGAN_LAUNCH("corr_kernel<1, 2, 2, 2, 2, false>", fl, ab, (corr_kernel<1, 2, 2, 2, 2>), grid, dim3(512), shmem, s, P); break;
-            default: GGAN_LAUNCH("corr_kernel<1, 1, 1, 8, 2, false>", fl, ab, (corr_kernel<1, 1, 1, 8, 2>), grid, dim3(512), shmem, s, P); break;
+            default: set_error("%s: no data-gradient variant of wave layout %d", name, cfg); return -3;
         }
     }
     return 0;
@@ -1117,55 +1096,44 @@ const unsigned* fwd_slab_table(const CorrParams& P, int CK, int nthr, int su, hi
 template <int MODE>
 int plan_and_launch(CorrParams& P, int Hu, int Wv, int su, int ext_r, int ext_c, int ntaps, int groups, float* dst,
                     const float* bias, int act, float alpha, void* ws, size_t ws_bytes, hipStream_t s, const char* name,
-                    double fl, const char* sk_env, const char* cfg_env) {
-    const int target = P.plan_wgs > 0 ? P.plan_wgs : env_int("GGAN_TARGET_WGS", 200);
+                    double fl, const char* sk_env) {
+    const int target = P.plan_wgs > 0 ? P.plan_wgs : kTargetWgs;
     const WaveCfg* kCfgs = MODE == 1 ? kCfgsDgrad : kCfgsFwd;
-    int cfg = env_int(cfg_env, -1);
-    if (cfg < 0 || cfg > (MODE == 1 ? 7 : 8)) {
-        // 8 waves per workgroup (two per SIMD: one wave's LDS / barrier stalls hide under the other's MFMAs; measured
-        // 12-19 % faster than the 4-wave layouts).  Largest tile that still yields ~one workgroup per CU.
-        // 128x32, 64x64, 64x32, 32x32 (pixels x channels).  The filter slice is 2/3 of what a 64x32 workgroup stages per chunk and
-        // is the same for every pixel tile: the 128-pixel layout stages it once for twice the MFMA work (forward kinds only:
-        // measured 43.2 vs 47.9 us on the critic's 64->128 layer at 128 images, slower for the data-gradient kinds)
-        // (all-class data gradient: the 64x32 tile with two accumulator pairs per wave = 16-channel chunks, so that its filter slice
-        //  goes by LDS-DMA with 8-byte fragment reads: 47.4 vs 53.9 us on the 64->128 layer at 128 images)
-        static const int order_fwd[4] = {8, 6, 4, 5}, order_all[4] = {8, 6, 7, 5};
-        const int* order = MODE == 2 ? order_all : order_fwd;
-        // class pairs: 32x32 tiles with 32-channel chunks (13 / 12 taps leave room for them in LDS).  Measured equal to the
-        // 16-channel chunks (33.6 vs 33.9 us on the 128->256 layer: the time per chunk follows the staged bytes, not the barriers),
-        // so it stays an option
-        const bool deep_pairs = MODE == 1 && getenv("GGAN_DEEP_PAIRS");
-        const int first = (MODE == 0 && !getenv("GGAN_NO_WIDE_TILE")) ? 0 : 1;
-        cfg = 5;
-        for (int oi = first; oi < 4; ++oi) {
-            const int c = order[oi];
-            const WaveCfg& wc = kCfgs[c];
-            const int CK = 2 * wc.KS * wc.PW, TM = 32 * wc.WM, TNW = 32 * wc.WN;
-            if (P.CNtot <= 32 && TNW > 32) continue;                               // don't pad tiny channel counts to 64
-            CorrParams T = P;
-            if (!pick_tile(T, Hu, Wv, TM, CK, su, ext_r, ext_c)) continue;
-            if (oi < 3 && T.TI * T.TR * T.TC * 2 <= TM && Hu * Wv * P.N >= TM) continue;   // staging budget forced a half-empty tile
-            const int wgs = cdiv(P.N, T.TI) * cdiv(Hu, T.TR) * cdiv(Wv, T.TC) * cdiv(P.CNtot, TNW) * groups;
-            // (the 128-pixel layout pays only while the grid is about one workgroup per CU: with several rounds of 64x64 tiles --
-            //  the 512-frame launches of the state-space scripts -- those stay faster, 200 vs 190+ us measured)
-            if (oi == 0 && wgs >= 2 * target) continue;
-            if (wgs >= target || oi == 3) { cfg = c; break; }
-        }
-        if (deep_pairs && cfg == 5 && P.CKtot >= 64) {
-            // 13 / 12 taps per chunk-channel leave room for 32-channel chunks in LDS: twice the MFMAs per barrier
-            CorrParams T = P;
-            if (pick_tile(T, Hu, Wv, 32, 32, su, ext_r, ext_c) && !(T.TI * T.TR * T.TC * 2 <= 32 && Hu * Wv * P.N >= 32)) cfg = 7;
-        }
-        if (P.CKtot < 8) cfg = P.CNtot <= 32 ? 1 : 6;                              // 3-channel inputs: smallest chunks
+    // 8 waves per workgroup (two per SIMD: one wave's LDS / barrier stalls hide under the other's MFMAs; measured
+    // 12-19 % faster than the 4-wave layouts).  Largest tile that still yields ~one workgroup per CU.
+    // 128x32, 64x64, 64x32, 32x32 (pixels x channels).  The filter slice is 2/3 of what a 64x32 workgroup stages per chunk and
+    // is the same for every pixel tile: the 128-pixel layout stages it once for twice the MFMA work (forward kinds only:
+    // measured 43.2 vs 47.9 us on the critic's 64->128 layer at 128 images, slower for the data-gradient kinds)
+    // (all-class data gradient: the 64x32 tile with two accumulator pairs per wave = 16-channel chunks, so that its filter slice
+    //  goes by LDS-DMA with 8-byte fragment reads: 47.4 vs 53.9 us on the 64->128 layer at 128 images)
+    // (class pairs on 32x32 tiles with 32-channel chunks measured equal to the 16-channel chunks, 33.6 vs 33.9 us on the 128->256
+    //  layer: the time per chunk follows the staged bytes, not the barriers)
+    static const int order_fwd[4] = {8, 6, 4, 5}, order_all[4] = {8, 6, 7, 5};
+    const int* order = MODE == 2 ? order_all : order_fwd;
+    int cfg = 5;
+    for (int oi = MODE == 0 ? 0 : 1; oi < 4; ++oi) {
+        const int c = order[oi];
+        const WaveCfg& wc = kCfgs[c];
+        const int CK = 2 * wc.KS * wc.PW, TM = 32 * wc.WM, TNW = 32 * wc.WN;
+        if (P.CNtot <= 32 && TNW > 32) continue;                               // don't pad tiny channel counts to 64
+        CorrParams T = P;
+        if (!pick_tile(T, Hu, Wv, TM, CK, su, ext_r, ext_c)) continue;
+        if (oi < 3 && T.TI * T.TR * T.TC * 2 <= TM && Hu * Wv * P.N >= TM) continue;   // staging budget forced a half-empty tile
+        const int wgs = cdiv(P.N, T.TI) * cdiv(Hu, T.TR) * cdiv(Wv, T.TC) * cdiv(P.CNtot, TNW) * groups;
+        // (the 128-pixel layout pays only while the grid is about one workgroup per CU: with several rounds of 64x64 tiles --
+        //  the 512-frame launches of the state-space scripts -- those stay faster, 200 vs 190+ us measured)
+        if (oi == 0 && wgs >= 2 * target) continue;
+        if (wgs >= target || oi == 3) { cfg = c; break; }
     }
+    if (P.CKtot < 8) cfg = P.CNtot <= 32 ? 1 : 6;                              // 3-channel inputs: smallest chunks
     const WaveCfg& wc = kCfgs[cfg];
     const int CK = 2 * wc.KS * wc.PW, TM = 32 * wc.WM, TNW = 32 * wc.WN;
     if (!pick_tile(P, Hu, Wv, TM, CK, su, ext_r, ext_c)) return 1;
     P.dbg = env_int("GGAN_DBG", 0);
-    P.dma = (MODE == 0 ? env_int("GGAN_CORR_DMA", 1) : (CK % 16 == 0 && wc.PW <= 2 && env_int("GGAN_DGRAD_DMA", 1))) && (P.dbg & 3) == 0;
+    P.dma = (MODE == 0 || (CK % 16 == 0 && wc.PW <= 2)) && (P.dbg & 3) == 0;
     const int RS = TNW + (MODE != 0 ? 2 : 0);     // filter row stride in LDS (corr_body: padded for the k-contiguous staging)
     P.xq = 1;
-    if (MODE == 0 && cfg >= 4 && P.dma && (P.Win & 3) == 0 && (((uintptr_t)P.in) & 15) == 0 && ((su * P.TC) & 3) == 0 && env_int("GGAN_CORR_X4", 1)) {
+    if (MODE == 0 && cfg >= 4 && P.dma && (P.Win & 3) == 0 && (((uintptr_t)P.in) & 15) == 0 && ((su * P.TC) & 3) == 0) {
         // Slab rows in 16-byte units of the image rows: a dword-gather DMA instruction costs the texture path ~64 cycles (a lane
         // per cycle) and the slab took 6 of them per wave and chunk -- as much texture-path time as the chunk has MFMA time.  With
         // the slab columns shifted so that LDS column c holds image column (unit-aligned start) + c, a lane moves 4 floats, and
@@ -1179,7 +1147,7 @@ int plan_and_launch(CorrParams& P, int Hu, int Wv, int su, int ext_r, int ext_c,
         //  branches then no longer share a CU -- measured +0.8 % on the iteration although the kernel alone is 1.6 % faster)
         const size_t stage1 = 2 * ((size_t)fwd_region(CK * P.CS, CK * P.CS, 1) + (size_t)wregion);
         const bool crosses = stage1 * sizeof(float) <= 80 * 1024 && stage4 * sizeof(float) > 80 * 1024;
-        if (stage4 * sizeof(float) <= 160 * 1024 && CK * cs4 / 4 <= (size_t)XE_MAX * 256 && (!crosses || env_int("GGAN_CORR_X4", 1) > 1)) {
+        if (stage4 * sizeof(float) <= 160 * 1024 && CK * cs4 / 4 <= (size_t)XE_MAX * 256 && !crosses) {
             P.xq = 4;
             P.col0 -= shift;
             for (int c = 0; c < 4; ++c) P.cls[c].coff += shift;
@@ -1188,7 +1156,7 @@ int plan_and_launch(CorrParams& P, int Hu, int Wv, int su, int ext_r, int ext_c,
         }
     }
     if (MODE != 0 && dgrad_x4_cfg(MODE, cfg) && (P.Win & 3) == 0 && (((uintptr_t)P.in) & 15) == 0 &&
-        (((uintptr_t)P.in_ref) & 15) == 0 && ((su * P.TC) & 3) == 0 && env_int("GGAN_DGRAD_X4", 1)) {
+        (((uintptr_t)P.in_ref) & 15) == 0 && ((su * P.TC) & 3) == 0) {
         // The same units for the register-staged slab of the data-gradient kinds: a thread fetches and commits 4 floats of an image
         // row per instruction (the 8-wave layouts staged 3 dwords per thread and chunk, twice that with the activation mask).
         const int shift = ((P.col0 % 4) + 4) % 4;
@@ -1238,26 +1206,20 @@ int plan_and_launch(CorrParams& P, int Hu, int Wv, int su, int ext_r, int ext_c,
     size_t stage = MODE == 0 ? 2 * ((size_t)fwd_region(CK * P.CS, CK * P.CS / P.xq, P.xq) + (size_t)fwd_region(ntaps * CK * RS, ntaps * CK * (TNW / 4), 4))
                              : 2 * ((size_t)((CK * P.CS + 1 + 3) & ~3) + (size_t)((ntaps * CK * RS + 4 * RS + 3) & ~3));
     size_t red = (size_t)wc.KS * (MODE == 2 ? 4 : (MODE == 1 ? 2 : 1)) * TNW * TM;     // epilogue: [ks][class][cn][pixel]
+    // (two staging buffers: three, fetched two chunks ahead, measured SLOWER on every forward layout in round 4 -- 64->128 @16:
+    //  24.6 -> 26.1 us; iteration 1.046 -> 1.057 ms: the loads dealt out from the first MFMA pair on already land within their chunk,
+    //  and twice the bytes in flight only lengthen every request's queue)
     P.nstg = 2;
-    if (MODE == 0 && P.dma && env_int("GGAN_CORR_NSTG", 2) >= 3 && stage / 2 * 3 * sizeof(float) <= 160 * 1024 && P.cps >= 3 * CK) {
-        // round 4 experiment (GGAN_CORR_NSTG=3): three staging buffers, fetched two chunks ahead.  Measured SLOWER than the two-buffer
-        // scheme on every forward layout (64->128 @16: 24.6 -> 26.1 us, chunk 3990 -> 4250 cycles, first barrier 5440 -> 6600; face 32->64
-        // at 128 images 40.3 -> 48.1 us; iteration 1.046 -> 1.057 ms): the loads dealt out from the first MFMA pair on already land within
-        // their chunk, and twice the bytes in flight only lengthen every request's queue.  Off by default.
-        P.nstg = 3;
-        stage = stage / 2 * 3;
-    }
-    if (MODE == 0 && P.dma && env_int("GGAN_CORR_XTAB", 1)) P.xtab = fwd_slab_table(P, CK, 64 * wc.WM * wc.WN * wc.KS, su, s);
+    if (MODE == 0 && P.dma) P.xtab = fwd_slab_table(P, CK, 64 * wc.WM * wc.WN * wc.KS, su, s);
     const size_t shmem = (stage > red ? stage : red) * sizeof(float);
     {   // XCD-aware tile order: what the eight L2s fetch together is 8 * input / p + filter * p for p pixel-tile groups
         P.xcd_p = 0;
-        const int force = env_int("GGAN_CORR_XCD", -1);
-        if (force != 0 && (gx * gy) % 8 == 0) {
+        if ((gx * gy) % 8 == 0) {
             double best = (gx % 8 == 0) ? (double)P.in_bytes + 8.0 * P.w_bytes : 8.0 * ((double)P.in_bytes + P.w_bytes);    // plain order
             for (int p = 1; p <= 8; p *= 2) {
-                if (gx % p || gy % (8 / p) || (force > 0 && p != force)) continue;
+                if (gx % p || gy % (8 / p)) continue;
                 const double cost = 8.0 * P.in_bytes / p + (double)P.w_bytes * p;
-                if (cost < 0.9 * best || force > 0) { best = cost; P.xcd_p = p; }
+                if (cost < 0.9 * best) { best = cost; P.xcd_p = p; }
             }
         }
     }
@@ -1325,7 +1287,7 @@ int conv_fwd_mfma(const ggan_conv_geom& g, const float* x, const float* w, const
     P.out_elems = (size_t)g.N * g.Co * g.Ho * g.Wo;
     const double fl = 2.0 * P.out_elems * g.Ci * 25.0;
     return plan_and_launch<0>(P, g.Ho, g.Wo, 2, 5, 5, 25, 1, y, bias, act, alpha, ws, ws_bytes, s, "conv_fwd_mfma", fl,
-                              "GGAN_FWD_SK", "GGAN_FWD_CFG");
+                              "GGAN_FWD_SK");
 }
 
 int conv_dgrad_mfma(const ggan_conv_geom& g, const float* gy, GyMask m, const float* w, const float* bias, float* gx,
@@ -1379,13 +1341,11 @@ int conv_dgrad_mfma(const ggan_conv_geom& g, const float* gy, GyMask m, const fl
     // all four parity classes in one workgroup (full-row float2 stores) when 32x32 tiles still give ~one workgroup per CU;
     // otherwise balanced class pairs (twice the workgroups)
     const long wgs_all = (long)cdiv(g.N * Hu * Wv, 32) * cdiv(g.Ci, 32);
-    int mode = env_int("GGAN_DGRAD_MODE", 0);
-    if (mode == 0) mode = wgs_all >= (g.plan_wgs > 0 ? g.plan_wgs : env_int("GGAN_TARGET_WGS", 200)) ? 2 : 1;
-    if (mode == 2)
+    if (wgs_all >= (g.plan_wgs > 0 ? g.plan_wgs : kTargetWgs))
         return plan_and_launch<2>(P, Hu, Wv, 1, hi[0] - lo[0] + 1, hi[1] - lo[1] + 1, 25, 1, gx, bias, act, alpha, ws, ws_bytes,
-                                  s, "conv_dgrad_mfma", fl, "GGAN_DGRAD_SK", "GGAN_DGRAD_CFG");
+                                  s, "conv_dgrad_mfma", fl, "GGAN_DGRAD_SK");
     return plan_and_launch<1>(P, Hu, Wv, 1, hi[0] - lo[0] + 1, hi[1] - lo[1] + 1, 13, 2, gx, bias, act, alpha, ws, ws_bytes,
-                              s, "conv_dgrad_mfma", fl, "GGAN_DGRAD_SK", "GGAN_DGRAD_CFG");
+                              s, "conv_dgrad_mfma", fl, "GGAN_DGRAD_SK");
 }
 
 }  // namespace ggan

@@ -19,7 +19,7 @@
 //     pairs from the second pair on.  (First version: a ring of three buffers fetched TWO chunks ahead, so that the wait at a chunk's
 //     end would retire loads a whole chunk old.  Measured slower everywhere -- 24.0 vs 22.8 us on 128->64 @8->16, the first barrier
 //     at 5560 instead of 3740 cycles: twice the bytes in flight lengthen every request's queue, and the dealt-out loads land within
-//     their chunk anyway.  GGAN_DG16_AHEAD=2 still selects it.)
+//     their chunk anyway.)
 //   * no per-launch descriptor arithmetic: the slab's per-lane byte offsets (halo lanes = out-of-range offset = zeros) depend on
 //     the geometry and the tile position only; they are built ONCE per geometry on the host (plan cache below) and read with one
 //     coalesced load per DMA instruction while the first filter blocks -- whose lane offsets are shifts of the lane id -- are
@@ -440,11 +440,6 @@ const unsigned* get_plan(const PlanKey& k, int SCP, int xinstr, int tiles_r, int
     return d;
 }
 
-int env_int(const char* name, int dflt) {
-    const char* v = getenv(name);
-    return v ? atoi(v) : dflt;
-}
-
 int launch_dg16(int scp, int kq, const Dg16Params& P, bool masked, dim3 grid, size_t shmem, hipStream_t s, double fl, double ab) {
     static std::atomic<unsigned long long> once{0};
 #define DG16_EACH(X) X(12, 4) X(16, 4) X(24, 4) X(12, 2) X(16, 2) X(24, 2)
@@ -492,14 +487,14 @@ int conv_dgrad_dg16(const ggan_conv_geom& g, const float* gy, GyMask m, const fl
     const int SCP = TC + 8;
     const int tiles_r = Hin / TR, tiles_c = Win / TC, igroups = cdiv(g.N, TI);
     const int ptiles = igroups * tiles_r * tiles_c;
-    if (target_wgs <= 0) target_wgs = env_int("GGAN_TARGET_WGS", 200);
+    if (target_wgs <= 0) target_wgs = kTargetWgs;
     // 32-channel tiles while they still give the planned number of workgroups, else 16-channel tiles; a grid far below the plan keeps
     // the older kernels (cross-workgroup split-K)
     int kq = env_int("GGAN_DG16_KQ", 0);
     if (kq != 2 && kq != 4) kq = ((CN & 31) == 0 && ptiles * (CN / 32) >= target_wgs) ? 2 : 4;
     if (kq == 2 && (CN & 31)) return 1;
     const int wgs = ptiles * (CN / (kq == 2 ? 32 : 16));
-    if (wgs * 4 < target_wgs * env_int("GGAN_DG16_MINQ", 3) && !env_int("GGAN_DG16_FORCE", 0)) return 1;     // (under 3/4 of the plan)
+    if (wgs * 4 < target_wgs * 3 && !env_int("GGAN_DG16_FORCE", 0)) return 1;     // (under 3/4 of the plan)
     const int ckc = 4 * kq;
     if (CK % ckc) return 1;
 
@@ -516,10 +511,10 @@ int conv_dgrad_dg16(const ggan_conv_geom& g, const float* gy, GyMask m, const fl
     P.tiles_r = tiles_r; P.tiles_c = tiles_c;
     P.nchunks = CK / ckc;
     // chunks the DMA runs ahead.  ONE: measured faster than two on every layer (128->64 @8->16, 64 images: 22.8 vs 24.0 us, first barrier
-    // 3740 vs 5560 cycles; 64->32 @16->32: 25.1 vs 28.0 us) -- as for the forward kinds (conv_corr.hip, GGAN_CORR_NSTG), more bytes in
+    // 3740 vs 5560 cycles; 64->32 @16->32: 25.1 vs 28.0 us) -- as for the forward kinds (conv_corr.hip, P.nstg), more bytes in
     // flight only lengthen every request's queue; the loads dealt out from the second MFMA pair on land within their chunk.
-    P.ahead = env_int("GGAN_DG16_AHEAD", 1) == 2 ? 2 : 1;
-    P.nstage = (masked || P.ahead == 2) ? 3 : 2;
+    P.ahead = 1;
+    P.nstage = masked ? 3 : 2;
     P.in_bytes = (unsigned)in_bytes; P.w_bytes = (unsigned)w_bytes;
     P.act = act; P.alpha = alpha;
     P.dbg = env_int("GGAN_DBG", 0);
@@ -543,14 +538,14 @@ int conv_dgrad_dg16(const ggan_conv_geom& g, const float* gy, GyMask m, const fl
     if ((P.dbg & 4) && ws && ws_bytes > (64u << 20)) P.stamps = (unsigned long long*)((char*)ws + ws_bytes - (32u << 20));
     const dim3 grid(ptiles, CN / (kq == 2 ? 32 : 16));
     {   // XCD-aware tile order: what the eight L2s fetch together is 8 * input / p + filter * p for p pixel-tile groups
-        const int gx = (int)grid.x, gy = (int)grid.y, force = env_int("GGAN_CORR_XCD", -1);
+        const int gx = (int)grid.x, gy = (int)grid.y;
         P.xcd_p = 0;
-        if (force != 0 && (gx * gy) % 8 == 0) {
+        if ((gx * gy) % 8 == 0) {
             double best = (gx % 8 == 0) ? (double)in_bytes + 8.0 * w_bytes : 8.0 * ((double)in_bytes + w_bytes);
             for (int p = 1; p <= 8; p *= 2) {
-                if (gx % p || gy % (8 / p) || (force > 0 && p != force)) continue;
+                if (gx % p || gy % (8 / p)) continue;
                 const double cost = 8.0 * in_bytes / p + (double)w_bytes * p;
-                if (cost < 0.9 * best || force > 0) { best = cost; P.xcd_p = p; }
+                if (cost < 0.9 * best) { best = cost; P.xcd_p = p; }
             }
         }
     }

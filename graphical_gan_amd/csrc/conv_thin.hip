@@ -620,7 +620,7 @@ int conv_dgrad_thin(const ggan_conv_geom& g, const float* gy, GyMask m, const fl
     P.gy = gy; P.ref = m.act != GGAN_ACT_NONE ? m.ref : nullptr; P.w = w; P.bias = bias; P.gx = gx;
     P.N = g.N; P.K = g.Co; P.Ci = g.Ci; P.Ho = g.Ho; P.Wo = g.Wo; P.H = g.H; P.W = g.W;
     P.mask_act = m.act; P.mask_alpha = m.alpha; P.act = act; P.alpha = alpha;
-    { const char* d = getenv("GGAN_THIN_DBG"); P.dbg = d ? atoi(d) : 0; }
+    P.dbg = env_int("GGAN_THIN_DBG", 0);
     const int NT = cdiv(25 * g.Ci, 16);
     P.MT = cdiv(4 * g.Wo, 16);
     if (P.MT > 8) return 1;
@@ -630,18 +630,15 @@ int conv_dgrad_thin(const ggan_conv_geom& g, const float* gy, GyMask m, const fl
     P.TS = NT * 16 + 4;
     P.d_k4 = make_fastdiv((uint32_t)(g.Co / 4)); P.d_w4 = make_fastdiv((uint32_t)(g.Wo / 4 > 0 ? g.Wo / 4 : 1)); P.d_W = make_fastdiv((uint32_t)g.W);
     const size_t tile = (size_t)g.Co * P.PS, tt = (size_t)P.MT * 16 * P.TS;
-    static const int w8 = [] { const char* e = getenv("GGAN_THIN_DGRAD_W8"); return e ? atoi(e) : 1; }();
-    const int ntp = w8 ? 2 * cdiv(NT, 2) : NT;      // (eight waves: the filter image padded to an even number of tiles)
+    const int ntp = 2 * cdiv(NT, 2);      // (eight waves: the filter image padded to an even number of tiles)
     const size_t shmem = ((size_t)ntp * 16 * P.KP + (tile > tt ? tile : tt)) * sizeof(float);
     if (shmem > 64 * 1024) return 1;
     const double fl = 2.0 * g.N * g.Co * g.Ho * g.Wo * (double)g.Ci * 25.0;
     const dim3 grid(g.Ho / 2, g.N);
     if (P.MT > 4 && P.MT != 8) return 1;       // one m-tile per wave, or exactly two
 #define THIN_DGRAD(NT_) \
-    if (w8 && P.MT == 8) { GGAN_LAUNCH("thin_dgrad_kernel", fl, 0, (thin_dgrad_kernel<NT_, true, 8>), grid, dim3(512), shmem, s, P); } \
-    else if (w8) { GGAN_LAUNCH("thin_dgrad_kernel", fl, 0, (thin_dgrad_kernel<NT_, false, 8>), grid, dim3(512), shmem, s, P); } \
-    else if (P.MT == 8) { GGAN_LAUNCH("thin_dgrad_kernel", fl, 0, (thin_dgrad_kernel<NT_, true, 4>), grid, dim3(NTHR), shmem, s, P); } \
-    else { GGAN_LAUNCH("thin_dgrad_kernel", fl, 0, (thin_dgrad_kernel<NT_, false, 4>), grid, dim3(NTHR), shmem, s, P); }
+    if (P.MT == 8) { GGAN_LAUNCH("thin_dgrad_kernel", fl, 0, (thin_dgrad_kernel<NT_, true, 8>), grid, dim3(512), shmem, s, P); } \
+    else { GGAN_LAUNCH("thin_dgrad_kernel", fl, 0, (thin_dgrad_kernel<NT_, false, 8>), grid, dim3(512), shmem, s, P); }
     switch (NT) {
         case 2: THIN_DGRAD(2); break;
         case 4: THIN_DGRAD(4); break;
@@ -702,7 +699,7 @@ int conv_wgrad_thin(const ggan_conv_geom& g, const float* x, const float* gy, Gy
     //  (round 6: a 32-channel first layer has only Co / 16 = 2 column groups -- 64 slabs were 128 workgroups, half of the chip, for the
     //   launch that ends the face critic's backward pass alone on the chip: 128 slabs there)
     int max_sk = (P.items >= 2048 && P.slab_stride <= 8192) ? 256 : 64;
-    if (max_sk == 64 && g.Co / 16 <= 2 && P.slab_stride <= 8192 && !getenv("GGAN_THIN_WGRAD_SK64")) max_sk = 128;
+    if (max_sk == 64 && g.Co / 16 <= 2 && P.slab_stride <= 8192) max_sk = 128;
     int sk = P.items < max_sk ? P.items : max_sk;
     if ((size_t)sk > cap_slabs) sk = (int)cap_slabs;
     if (sk < 1) sk = 1;
@@ -772,7 +769,7 @@ int conv_fwd_thin(const ggan_conv_geom& g, const float* x, const float* w, const
         if ((((uintptr_t)mask->ref) & 15) || !mask->ref) return 1;
         P.mref = mask->ref; P.mask_act = mask->act; P.mask_alpha = mask->alpha;
     }
-    { const char* d = getenv("GGAN_THIN_DBG"); P.dbg = d ? atoi(d) : 0; }
+    P.dbg = env_int("GGAN_THIN_DBG", 0);
     P.N = g.N; P.Ci = g.Ci; P.H = g.H; P.W = g.W; P.Co = g.Co; P.Ho = g.Ho; P.Wo = g.Wo; P.pad_t = g.pad_t; P.pad_l = g.pad_l;
     P.d_c4 = make_fastdiv((uint32_t)(g.Co / 4 > 0 ? g.Co / 4 : 1));
     // band of output rows: whole 16-pixel tiles, at most 8 of them; the smallest band that still gives every wave a tile
@@ -805,11 +802,8 @@ int conv_fwd_thin(const ggan_conv_geom& g, const float* x, const float* w, const
     const dim3 grid(P.nb, g.N);
     // (eight waves where a wave still owns two channel tiles: 3->64 @32 at 64 / 128 images 10.3 -> 9.2 / 13.1 -> 12.3 us; with 32 output
     //  channels a wave would be left with ONE tile -- two fragment reads per MFMA -- and the face layer measured 12.3 -> 13.9 us)
-    static const int w8 = [] { const char* e = getenv("GGAN_THIN_FWD_W8"); return e ? atoi(e) : 1; }();
-    if (w8 && NTN == 4 && MPW == 1) { GGAN_LAUNCH("thin_fwd_kernel", fl, 0, (thin_fwd_kernel<4, 1, 8>), grid, dim3(512), shmem, s, P); }
-    else if (w8 && NTN == 4 && MPW == 2) { GGAN_LAUNCH("thin_fwd_kernel", fl, 0, (thin_fwd_kernel<4, 2, 8>), grid, dim3(512), shmem, s, P); }
-    else if (NTN == 4 && MPW == 1) { GGAN_LAUNCH("thin_fwd_kernel", fl, 0, (thin_fwd_kernel<4, 1, 4>), grid, dim3(NTHR), shmem, s, P); }
-    else if (NTN == 4 && MPW == 2) { GGAN_LAUNCH("thin_fwd_kernel", fl, 0, (thin_fwd_kernel<4, 2, 4>), grid, dim3(NTHR), shmem, s, P); }
+    if (NTN == 4 && MPW == 1) { GGAN_LAUNCH("thin_fwd_kernel", fl, 0, (thin_fwd_kernel<4, 1, 8>), grid, dim3(512), shmem, s, P); }
+    else if (NTN == 4 && MPW == 2) { GGAN_LAUNCH("thin_fwd_kernel", fl, 0, (thin_fwd_kernel<4, 2, 8>), grid, dim3(512), shmem, s, P); }
     else if (NTN == 2 && MPW == 1) { GGAN_LAUNCH("thin_fwd_kernel", fl, 0, (thin_fwd_kernel<2, 1, 4>), grid, dim3(NTHR), shmem, s, P); }
     else if (NTN == 2 && MPW == 2) { GGAN_LAUNCH("thin_fwd_kernel", fl, 0, (thin_fwd_kernel<2, 2, 4>), grid, dim3(NTHR), shmem, s, P); }
     else return 1;

@@ -21,20 +21,11 @@ using namespace ggan;
 
 namespace {
 
-// Compile-time ablations for timing experiments (tools/variant_lib.sh builds a second libggan.so with -DGGAN_ABL=bits and
-// tools/stamps.py prints the per-workgroup phase times): 1 = no staging inside the chunk loop, 4 = MFMAs on register constants
-// instead of LDS fragments.  0 in the product build: the branches fold away.
-#ifndef GGAN_ABL
-#define GGAN_ABL 0
-#endif
 // conv_wgrad_split.hip includes this file with GGAN_WGRAD_SPLIT_TU set and is compiled with -mllvm -amdgpu-mfma-vgpr-form: the
 // role-split kernel's 256-register waves keep all 200 accumulators in architectural VGPRs (with AGPRs in play the allocator splits
 // the budget 128 / 128 and spills hundreds of registers), so the epilogue's parked quads are "v" operands there.
 #ifndef GGAN_WGRAD_SPLIT_TU
 #define GGAN_WGRAD_SPLIT_TU 0
-#endif
-#ifndef GGAN_SPLIT_SCHED
-#define GGAN_SPLIT_SCHED 1
 #endif
 #if GGAN_WGRAD_SPLIT_TU
 #define GGAN_ACC_REG(q) "v"(q)
@@ -46,6 +37,7 @@ constexpr int NW = 8;                      // waves per workgroup: two per SIMD,
 constexpr int NTHR = 64 * NW;
 constexpr int XU_MAX = 6;                  // float4 slab units per thread per chunk (3072 per workgroup)
 constexpr unsigned OOB = 0x7FFFFFF0u;
+constexpr int kWgradTargetWgs = 256;       // split-K workgroups a launch is planned for when ggan_conv_geom.plan_wgs_filter is 0
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
@@ -234,7 +226,6 @@ __global__ __launch_bounds__(NTHR) void wgrad_kernel(const WgradParams P) {
         //      matrix pipe waiting on the other wave alone) -----------------------------------------------------------------------
         auto load_quad = [&](int qd, float* a, float& b) {
             const int p0 = qd * 4;
-            if (GGAN_ABL & 4) { b = __int_as_float(gb + qd); for (int t = 0; t < NT; ++t) a[t] = __int_as_float(xa + t); return; }
             const int img = fdiv(p0, P.d_TRWo);
             const int rem = p0 - img * (P.TR * P.Wo);
             const int r = fdiv(rem, P.d_Wo);
@@ -251,8 +242,8 @@ __global__ __launch_bounds__(NTHR) void wgrad_kernel(const WgradParams P) {
             // every wave commits chunk ch+1 first (its registers were filled during chunk ch-1), then multiplies; the loads of
             // chunk ch+2 ride in the MFMA blocks, IPB per block, one every few MFMAs
             constexpr int NB = 2 * NIT, NITEM = XU_MAX + 2, IPB = (NITEM + NB - 1) / NB;
-            if (!(GGAN_ABL & 1) && ch + 1 < c_end) commit(buf ^ 1);
-            const ChunkBase nb = chunk_base(ch + 2, ch + 2 < c_end && !(GGAN_ABL & 1));
+            if (ch + 1 < c_end) commit(buf ^ 1);
+            const ChunkBase nb = chunk_base(ch + 2, ch + 2 < c_end);
             auto block = [&](int bi, const float* a, float bq) {
 #pragma unroll
                 for (int i = bi * IPB; i < (bi + 1) * IPB; ++i)
@@ -278,7 +269,7 @@ __global__ __launch_bounds__(NTHR) void wgrad_kernel(const WgradParams P) {
             }
         } else {
             auto stage_next = [&]() {
-                if (!(GGAN_ABL & 1) && ch + 1 < c_end) {
+                if (ch + 1 < c_end) {
                     commit(buf ^ 1);
                     if (ch + 2 < c_end) prefetch(ch + 2);
                 }
@@ -550,7 +541,6 @@ __global__ __launch_bounds__(SPLIT ? 2 * W4_NTHR : W4_NTHR) void wgrad4_kernel(c
             const int j = i - XU - GU;
             const u32x4 g = sreg[XU + j], rf = sreg[i];
             float4 gv = make_float4(__uint_as_float(g.x), __uint_as_float(g.y), __uint_as_float(g.z), __uint_as_float(g.w));
-            if (GGAN_ABL & 2) { *reinterpret_cast<float4*>(smem + bo + gl + j * G::GSTEP * G::PCp) = gv; return; }
             gv.x = __uint_as_float(rf.x) > 0.f ? gv.x : gv.x * mslope;
             gv.y = __uint_as_float(rf.y) > 0.f ? gv.y : gv.y * mslope;
             gv.z = __uint_as_float(rf.z) > 0.f ? gv.z : gv.z * mslope;
@@ -598,7 +588,7 @@ __global__ __launch_bounds__(SPLIT ? 2 * W4_NTHR : W4_NTHR) void wgrad4_kernel(c
                 for (int j = 0; j < GU; ++j) {
                     const u32x4 g = sreg[XU + j];
                     float4 gv = make_float4(__uint_as_float(g.x), __uint_as_float(g.y), __uint_as_float(g.z), __uint_as_float(g.w));
-                    if (masked && !(GGAN_ABL & 2)) {
+                    if (masked) {
                         const u32x4 rf = sreg[XU + GU + j];
                         gv.x = __uint_as_float(rf.x) > 0.f ? gv.x : gv.x * mslope;
                         gv.y = __uint_as_float(rf.y) > 0.f ? gv.y : gv.y * mslope;
@@ -622,13 +612,13 @@ __global__ __launch_bounds__(SPLIT ? 2 * W4_NTHR : W4_NTHR) void wgrad4_kernel(c
             commit(WaveTag<0>{});
             __syncthreads();
             for (int ch = c_begin; ch < c_end; ch += 2) {
-                if (!(GGAN_ABL & 1) && ch + 1 < c_end) {        // (behind the last chunk there is nothing to stage)
+                if (ch + 1 < c_end) {        // (behind the last chunk there is nothing to stage)
                     fetch(chunk_base(ch + 1, true));
                     commit(WaveTag<1>{});
                 }
                 __syncthreads();
                 if (ch + 1 >= c_end) break;
-                if (!(GGAN_ABL & 1) && ch + 2 < c_end) {
+                if (ch + 2 < c_end) {
                     fetch(chunk_base(ch + 2, true));
                     commit(WaveTag<0>{});
                 }
@@ -689,7 +679,7 @@ __global__ __launch_bounds__(SPLIT ? 2 * W4_NTHR : W4_NTHR) void wgrad4_kernel(c
                 // multiplying waves: ONE set of fragment registers, a fragment refilled for the next quad right behind its two MFMAs
                 // (200 accumulators + 27 fragments have to fit the 256 registers of a wave that shares its SIMD)
                 float a[NT], b0, b1;
-                auto tap = [&](int q, int t) { if (GGAN_ABL & 4) return __int_as_float(xa + t + q); return xq[G::q_off(q) + (t / KS) * G::SCp + (((t % KS) + 3) & 1) * G::SCh + (((t % KS) + 3) >> 1)]; };
+                auto tap = [&](int q, int t) { return xq[G::q_off(q) + (t / KS) * G::SCp + (((t % KS) + 3) & 1) * G::SCh + (((t % KS) + 3) >> 1)]; };
                 b0 = gq[0]; b1 = gq[16 * G::PCp];
 #pragma unroll
                 for (int t = 0; t < NT; ++t) a[t] = tap(0, t);
@@ -715,7 +705,6 @@ __global__ __launch_bounds__(SPLIT ? 2 * W4_NTHR : W4_NTHR) void wgrad4_kernel(c
         }
         float av[2][NT], bv[2][2];
         auto load_quad = [&](int q, float* a, float* b) {
-            if (GGAN_ABL & 4) { b[0] = __int_as_float(gb + q); b[1] = b[0]; for (int t = 0; t < NT; ++t) a[t] = __int_as_float(xa + t); return; }
             b[0] = gq[16 * q];
             b[1] = gq[16 * q + 16 * G::PCp];
             const int o = G::q_off(q);
@@ -732,14 +721,12 @@ __global__ __launch_bounds__(SPLIT ? 2 * W4_NTHR : W4_NTHR) void wgrad4_kernel(c
             const float* a = av[q & 1];
             const float* b = bv[q & 1];
             if (q + 1 < NQ) load_quad(q + 1, av[(q + 1) & 1], bv[(q + 1) & 1]);
-            if (!(GGAN_ABL & 1)) {
 #pragma unroll
-                for (int i = (q - LAG) * IPB; i < (q - LAG + 1) * IPB; ++i)
-                    if (i >= 0 && i < NITEM) commit_item(obo, i);
+            for (int i = (q - LAG) * IPB; i < (q - LAG + 1) * IPB; ++i)
+                if (i >= 0 && i < NITEM) commit_item(obo, i);
 #pragma unroll
-                for (int i = q * IPB; i < (q + 1) * IPB; ++i)
-                    if (i < NITEM && q < LB) pf_item(nb, i);
-            }
+            for (int i = q * IPB; i < (q + 1) * IPB; ++i)
+                if (i < NITEM && q < LB) pf_item(nb, i);
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
                 acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(b[0], a[t], acc[t], 0, 0, 0);
@@ -840,11 +827,6 @@ __global__ __launch_bounds__(SPLIT ? 2 * W4_NTHR : W4_NTHR) void wgrad4_kernel(c
     stamp(14);
 }
 
-int env_int(const char* name, int dflt) {
-    const char* v = getenv(name);
-    return v ? atoi(v) : dflt;
-}
-
 }  // namespace
 
 #if GGAN_WGRAD_SPLIT_TU
@@ -936,7 +918,7 @@ int conv_wgrad_mfma(const ggan_conv_geom& g, const float* x, const float* gy, Gy
         else if (geom_is(W4Geom<32>{})) four = 32;
         else if (geom_is(W4Geom<64>{})) four = 64;
     }
-    if (!four && !(env_int("GGAN_WGRAD_PC", 128) >= 128 && plan_chunk(128, TCO, NTHR)) && !plan_chunk(64, TCO, NTHR)) return 1;
+    if (!four && !plan_chunk(128, TCO, NTHR) && !plan_chunk(64, TCO, NTHR)) return 1;
     const int tco = four ? W4_TCO : TCO;
     P.d_F4 = make_fastdiv(g.W / 4); P.d_SR = make_fastdiv(P.SR); P.d_TI = make_fastdiv(P.TI);
     P.d_PC4 = make_fastdiv(P.PC / 4); P.d_TRWo = make_fastdiv(P.TR * g.Wo); P.d_Wo = make_fastdiv(g.Wo);
@@ -946,7 +928,7 @@ int conv_wgrad_mfma(const ggan_conv_geom& g, const float* x, const float* gy, Gy
     int sk = env_int("GGAN_WGRAD_SK", 0);
     if (sk <= 0) {
         // (a caller running two conv chains side by side asks for fewer workgroups per launch: ggan_conv_geom.plan_wgs_filter)
-        const int wg_target = g.plan_wgs_filter > 0 ? g.plan_wgs_filter : env_int("GGAN_WGRAD_WGS", 256);
+        const int wg_target = g.plan_wgs_filter > 0 ? g.plan_wgs_filter : kWgradTargetWgs;
         sk = cdiv(wg_target, gx * gy_);
         if (sk > P.chunks_total / 2) sk = P.chunks_total / 2;
         if (sk > 64) sk = 64;
@@ -972,15 +954,14 @@ int conv_wgrad_mfma(const ggan_conv_geom& g, const float* x, const float* gy, Gy
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad4_kernel<32>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad4_kernel<64>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     }
-    const int nit = env_int("GGAN_WGRAD_DEAL", 1) ? (P.PC == 128 ? 2 : (P.PC == 64 ? 1 : 0)) : 0;
+    const int nit = P.PC == 128 ? 2 : (P.PC == 64 ? 1 : 0);
     const double fl = 2.0 * g.N * g.Co * g.Ho * g.Wo * (double)g.Ci * 25.0;
     const double ab = 4.0 * ((double)g.N * g.Ci * g.H * g.W + (double)g.N * g.Co * g.Ho * g.Wo + 25.0 * g.Ci * g.Co);
     if (parts && ws_bytes < P.slab_stride * sizeof(float)) { set_error("conv_wgrad: partial-slab buffer too small"); return -1; }
     if (want_stamps && !parts && ws && ws_bytes > (64u << 20)) P.stamps = (unsigned long long*)((char*)ws + ws_bytes - (32u << 20));
     const dim3 grid4(gx * gy_ * P.SK);       // split-fastest workgroup numbering (decoded in the kernel)
-    const bool split_roles = env_int("GGAN_WGRAD_SPLIT", 1) != 0;          // (read per call, like GGAN_WGRAD_W4 / _SK / _WGS / _PC)
-    const int split_roles_mask = env_int("GGAN_WGRAD_SPLIT_W", 8 | 16 | 32 | 64);
-    if (split_roles && four > 0 && (split_roles_mask & four)) { const int rc = wgrad4_split_launch(four, grid4.x, shmem, s, &P, fl, ab); if (rc) return rc; }
+    const bool split_roles = env_int("GGAN_WGRAD_SPLIT", 1) != 0;          // (read per call, like GGAN_WGRAD_W4 / _SK)
+    if (split_roles && four > 0) { const int rc = wgrad4_split_launch(four, grid4.x, shmem, s, &P, fl, ab); if (rc) return rc; }
     else if (four == 16) { GGAN_LAUNCH("wgrad4_kernel<16>", fl, ab, wgrad4_kernel<16>, grid4, dim3(W4_NTHR), shmem, s, P); }
     else if (four == 8) { GGAN_LAUNCH("wgrad4_kernel<8>", fl, ab, wgrad4_kernel<8>, grid4, dim3(W4_NTHR), shmem, s, P); }
     else if (four == 32) { GGAN_LAUNCH("wgrad4_kernel<32>", fl, ab, wgrad4_kernel<32>, grid4, dim3(W4_NTHR), shmem, s, P); }

@@ -512,15 +512,6 @@ __global__ __launch_bounds__(64 * NWAVE) void gemm_group_kernel(const GemmGroup 
         default: gemm_tile<false, false, 0, 1, NWAVE>(P, bx, by, 0, As, Bs); break;
     }
 }
-static bool group_w8() {
-    static const bool v = [] { const char* e = getenv("GGAN_GEMM_GROUP_W8"); return e ? atoi(e) != 0 : true; }();
-    return v;
-}
-#define GGAN_LAUNCH_GROUP(fl, nwg, s, GG)                                                                                        \
-    do {                                                                                                                          \
-        if (group_w8()) { GGAN_LAUNCH("gemm_group_kernel<8>", fl, 0, gemm_group_kernel<8>, dim3(nwg), dim3(512), 0, s, GG); }    \
-        else { GGAN_LAUNCH("gemm_group_kernel", fl, 0, gemm_group_kernel<4>, dim3(nwg), dim3(256), 0, s, GG); }                  \
-    } while (0)
 
 // ---- the critics' heads: Linear + LeakyReLU + Linear(H -> 1) -------------------------------------------------------------------
 // forward tail: h = lrelu(sum of the split-K slabs of the first Linear + b), logits = h . w_out + b_out.  One workgroup per two rows.
@@ -762,11 +753,7 @@ size_t ggan_gemm_workspace(int M, int N, int K) {
 // Fill the parameter block of one product (operand views, float4 legality, split-K choice, FAST path); no launch.
 // mode 0: normal (split-K result reduced by the caller)   1: no split-K (grouped launches, fused column sums)
 constexpr int kSplitTarget = 256;     // workgroups a split-K product aims at (the critic head's forward asks for more: split_target)
-
-static int head_split_target() {
-    static const int v = [] { const char* e = getenv("GGAN_HEAD_WGS"); return e ? atoi(e) : 512; }();
-    return v;
-}
+constexpr int kHeadSplitTarget = 512;  // the critic head's first product (ggan_critic_head_fwd)
 
 struct GemmPlan {
     GemmParams P;
@@ -844,7 +831,7 @@ static int gemm_plan(GemmPlan& G, int mode, int ta, int tb, int M, int N, int K,
     const size_t szA2 = A2 ? (size_t)(ta ? (size_t)K * (M - a_split) : (size_t)M * (K - a_split)) * 4 : 0;
     const size_t szB = (size_t)N * K * 4;
     const bool dims4 = (K % 4 == 0) && (P.kps % 4 == 0) && (ta ? (M % 4 == 0 && (!A2 || a_split % 4 == 0)) : true) && (tb ? true : N % 4 == 0);
-    const bool small = szA < 0x7FFFFFF0ull && szA2 < 0x7FFFFFF0ull && szB < 0x7FFFFFF0ull && !getenv("GGAN_GEMM_GENERIC");
+    const bool small = szA < 0x7FFFFFF0ull && szA2 < 0x7FFFFFF0ull && szB < 0x7FFFFFF0ull;
     P.fast = !small ? 0 : ((P.vecA && P.vecB && dims4) ? 1 : 2);        // 1: 16-byte loads, 2: dword loads (any alignment / extent)
     P.a_bytes = (unsigned)szA; P.a2_bytes = (unsigned)szA2; P.b_bytes = (unsigned)szB;
     return 0;
@@ -856,12 +843,9 @@ static int gemm_launch_planned(const GemmPlan& G, int ta, int tb, hipStream_t s)
     const double fl = 2.0 * P.M * P.N * (double)P.K;
     const dim3 grid(G.gx, G.gy, P.SK), block(256);
     // eight waves (in-workgroup split of every k-step) where the grid leaves at most ~one workgroup per CU: nothing else on the SIMD
-    // hides a step's LDS / L2 round trips there.  GGAN_GEMM_W8 = 0: never, N: grids up to N workgroups (default 256)
-    static const int w8_max = [] { const char* e = getenv("GGAN_GEMM_W8"); return e ? atoi(e) : (1 << 30); }();
-    static const bool w8_colsum = [] { const char* e = getenv("GGAN_GEMM_W8_COLSUM"); return e ? atoi(e) != 0 : true; }();
-    static const int w8_min_steps = [] { const char* e = getenv("GGAN_GEMM_W8_MIN_STEPS"); return e ? atoi(e) : 2; }();
+    // hides a step's LDS / L2 round trips there
     // (a workgroup that walks ONE step has no round trip between steps to hide: the split would only add its combine)
-    const bool w8 = P.fast != 0 && (long)G.gx * G.gy * P.SK <= (long)w8_max && (!P.colsum || w8_colsum) && P.kps >= w8_min_steps * KSTEP;
+    const bool w8 = P.fast != 0 && P.kps >= 2 * KSTEP;
 #define GGAN_GEMM_CASE(TA_, TB_, MK_, NAME_)                                                                                      \
     do {                                                                                                                           \
         if (w8 && P.fast == 1) { GGAN_LAUNCH("gemm_kernel8" NAME_, fl, 0, (gemm_kernel8<TA_, TB_, MK_, 1>), grid, dim3(512), 0, s, P); }   \
@@ -893,11 +877,10 @@ static int gemm_launch(int ta, int tb, int M, int N, int K, const float* A, cons
     }
     // skinny products (gemm_skinny_k): where the 64x64 tiling would have to split K to fill the chip and K is short enough for all
     // of a wave's loads to be in flight at once -- one launch instead of product + reduce
-    static const int skinny = [] { const char* e = getenv("GGAN_GEMM_SKINNY"); return e ? atoi(e) : 1; }();
     // (M >= 32: the scripts' minibatches are 50-128 rows.  The 8-row trajectory fixture `vegan-wgan-gp` is bimodal under fp32 rounding --
     //  a pre-activation within rounding of its LeakyReLU kink, profiles/r04_notes.md -- and ANY other legal summation order of its
     //  products, this one or GGAN_GEMM_SK=16 on the old kernel, lands it on the other branch: products that small keep their order)
-    if (skinny && !ta && !colsum && (!A2 || (a_split % 16 == 0 && !a_ref)) && (!C2 || c_split % 16 == 0) && !b_ref && (!a_ref || tb) && M >= 32 &&
+    if (!ta && !colsum && (!A2 || (a_split % 16 == 0 && !a_ref)) && (!C2 || c_split % 16 == 0) && !b_ref && (!a_ref || tb) && M >= 32 &&
         K >= 64 && K <= 1024 && cdiv(M, BM) * cdiv(N, BN) < 64 &&
         cdiv(M, 16) * cdiv(N, 16) <= 1024 && !(K <= 128 && cdiv(M, BM) * cdiv(N, BN) >= 32) && (size_t)M * K * 4 < 0x7FFFFFF0ull &&
         (size_t)N * K * 4 < 0x7FFFFFF0ull) {
@@ -956,7 +939,7 @@ int ggan_critic_head_fwd(int M, int K1, int K2, int H, const float* a1, const fl
     // (twice the workgroups of the other split products: the tail kernel below sums the slabs anyway, and this product sits alone on
     //  the step's critical chain -- 9 serial k-steps per workgroup at 256, 5 at 512: 1.127 -> 1.122 ms; 1024: slower again)
     int rc = gemm_plan(G, 0, 0, 0, M, H, K1 + K2, a1, w, nullptr, h, nullptr, GGAN_ACT_NONE, 0.f, ws, ws_bytes, nullptr, nullptr, 0, 0.f,
-                       K2 ? a2 : nullptr, K2 ? K1 : 0, nullptr, 0, head_split_target());
+                       K2 ? a2 : nullptr, K2 ? K1 : 0, nullptr, 0, kHeadSplitTarget);
     if (rc) return rc;
     rc = gemm_launch_planned(G, 0, 0, s);
     if (rc) return rc;
@@ -997,7 +980,7 @@ int ggan_critic_head_fwd_bce(int M, int K1, int K2, int H, const float* a1, cons
     hipStream_t s = (hipStream_t)stream;
     GemmPlan G;
     int rc = gemm_plan(G, 0, 0, 0, M, H, K1 + K2, a1, w, nullptr, h, nullptr, GGAN_ACT_NONE, 0.f, ws, ws_bytes, nullptr, nullptr, 0, 0.f,
-                       K2 ? a2 : nullptr, K2 ? K1 : 0, nullptr, 0, head_split_target());
+                       K2 ? a2 : nullptr, K2 ? K1 : 0, nullptr, 0, kHeadSplitTarget);
     if (rc) return rc;
     rc = gemm_launch_planned(G, 0, 0, s);
     if (rc) return rc;
@@ -1040,7 +1023,7 @@ static int critic_head_bwd_impl(int M, int K1, int K2, int H, const float* g, co
         if (rc) return rc;
         na = 1;
     }
-    if (nw && na && Gw.P.fast == 1 && Ga.P.fast == 1 && !getenv("GGAN_NO_GEMM_GROUP")) {
+    if (nw && na && Gw.P.fast == 1 && Ga.P.fast == 1) {
         GemmGroup GG;
         memset(&GG, 0, sizeof(GG));
         // (the data-gradient product first: its workgroups walk K = H in 16 serial steps, the weight-gradient's only M / 32 --
@@ -1056,10 +1039,10 @@ static int critic_head_bwd_impl(int M, int K1, int K2, int H, const float* g, co
             GG.tail.first = nwg;
             nwg += 1 + cdiv(H, 16);
         }
-        GGAN_LAUNCH_GROUP(4.0 * M * K * (double)H, nwg, s, GG);
+        GGAN_LAUNCH("gemm_group_kernel<8>", 4.0 * M * K * (double)H, 0, gemm_group_kernel<8>, dim3(nwg), dim3(512), 0, s, GG);
         return 0;
     }
-    if (tail && na && !nw && Ga.P.fast == 1 && !getenv("GGAN_NO_GEMM_GROUP")) {
+    if (tail && na && !nw && Ga.P.fast == 1) {
         // generator steps (the critic's weights are frozen: the data-gradient product alone): the cost still rides in its launch
         GemmGroup GG;
         memset(&GG, 0, sizeof(GG));
@@ -1069,7 +1052,8 @@ static int critic_head_bwd_impl(int M, int K1, int K2, int H, const float* g, co
         GG.has_tail = 1;
         GG.tail = *tail;
         GG.tail.first = GG.first[1];
-        GGAN_LAUNCH_GROUP(2.0 * M * K * (double)H, GG.first[1] + 1 + cdiv(H, 16), s, GG);
+        GGAN_LAUNCH("gemm_group_kernel<8>", 2.0 * M * K * (double)H, 0, gemm_group_kernel<8>, dim3(GG.first[1] + 1 + cdiv(H, 16)), dim3(512), 0,
+                    s, GG);
         return 0;
     }
     if (tail) {

@@ -29,6 +29,7 @@ _CAPTURE_MODE = os.environ.get('GGAN_CAPTURE_MODE', 'thread_local')
 
 
 _DP_GRAPH_OK = {}
+AHEAD_TARGET_WGS = 128     # workgroups per conv launch of the nets passes issued ahead on a stream of their own (Trainer._ahead_issue)
 
 
 def _dump_graph_dot(g, path):
@@ -248,7 +249,7 @@ class Trainer(object):
         # (replicas too, since round 6: the passes read no critic weight and no gradient bucket, so the in-graph exchange -- a branch of its
         #  own on the communicator's stream, forked behind a step's pack launch and joined in front of its update -- never meets them; the
         #  cut-graph exchange (split_graph) keeps one graph per step and has no iteration graph to put them in)
-        return (not os.environ.get('GGAN_NO_NETS_AHEAD') and kinds.count('disc') >= 2 and (self.world == 1 or self.dp_graph)
+        return (kinds.count('disc') >= 2 and (self.world == 1 or self.dp_graph)
                 and not self.split_graph and not self.sync_bn
                 and hasattr(self.model, 'fork_now') and hasattr(self.model, 'feed_buffers')
                 and not getattr(c, 'K', 0) and not getattr(c, 'agg', None) and getattr(c, 'dataset', '') != 'mnist'
@@ -273,7 +274,7 @@ class Trainer(object):
                 F.workspace(self.device)
             torch.cuda.synchronize(self.device)
         self._ahead_sync_feeds()
-        st.update(i=0, nets=[], events=[], pending=None)
+        st.update(i=0, nets=[], events=[])
         return st
 
     def _ahead_issue(self, st, k):
@@ -282,7 +283,7 @@ class Trainer(object):
         saved = (m._pending_join, getattr(m, '_noise_event', None), m._early, m.fork_now)
         m.fork_now = False
         try:
-            with torch.cuda.stream(ns), F.launch_hint(int(os.environ.get('GGAN_AHEAD_WGS', '128'))):
+            with torch.cuda.stream(ns), F.launch_hint(AHEAD_TARGET_WGS):
                 st['nets'].append(self._nets(st['feeds'][k]))
                 ev = torch.cuda.Event()
                 ev.record(ns)
@@ -292,56 +293,27 @@ class Trainer(object):
 
     def _ahead_step(self):
         """(nets, feed) of the next critic step of the iteration being captured.  The chain is forked behind critic step 1's own nets
-        pass (its noise launch, the snapshot); the pass of step i + 2 is held back until critic step i + 1 has begun, so that one pass runs
-        beside each critic step instead of all of them beside the first (3.886 -> 3.836 ms; GGAN_AHEAD_BUNCH=1: all at once).  WHERE in
-        step i + 1 it is released is GGAN_AHEAD_AT: 'begin' (in front of its critic pass), 'bwd' (behind its forward: the pass then runs
-        beside the backward pass and the step's tail -- the last data gradient, the thin filter gradient, the pack launch -- where a
-        profiled iteration has one kernel in flight), 'pack' (behind its backward launches)."""
+        pass (its noise launch, the snapshot); the pass of step i + 2 is held back until critic step i + 1 has begun, and issued in front
+        of its critic pass, so that one pass runs beside each critic step instead of all of them beside the first (3.886 -> 3.836 ms;
+        releasing it behind the step's forward or behind its backward launches measured slower)."""
         st = self._ahead_run
         i, n = st['i'], len(st['feeds'])
         st['i'] += 1
         cur = torch.cuda.current_stream(self.device)
-        bunch = bool(os.environ.get('GGAN_AHEAD_BUNCH'))
-        at = self._ahead_at()
         if i == 0:
             st['snap'].copy_(self.feed['ring'][2])                        # the critic's step count in front of critic step 1
             nets = self._nets()
             st['stream'].wait_stream(cur)                                 # (behind step 1's noise launch and the snapshot)
-            if bunch or at == 'begin':
-                for k in range(n if bunch else 1):
-                    self._ahead_issue(st, k)
-            else:
-                st['pending'] = 0
+            self._ahead_issue(st, 0)
             return nets, self.feed
-        if not bunch and i < n:
-            if at == 'begin':
-                ev = torch.cuda.Event()
-                ev.record(cur)
-                st['stream'].wait_event(ev)
-                self._ahead_issue(st, i)
-            else:
-                st['pending'] = i
+        if i < n:
+            ev = torch.cuda.Event()
+            ev.record(cur)
+            st['stream'].wait_event(ev)
+            self._ahead_issue(st, i)
         cur.wait_event(st['events'][i - 1])
         self._sl0 = lib.second_leaf_count()
         return st['nets'][i - 1], st['feeds'][i - 1]
-
-    @staticmethod
-    def _ahead_at():
-        at = os.environ.get('GGAN_AHEAD_AT', 'begin')
-        assert at in ('begin', 'bwd', 'pack'), at
-        return at
-
-    def _ahead_release(self, point):
-        """issue the nets pass a critic step holds back, if `point` is where GGAN_AHEAD_AT releases it (engine._fwd_bwd calls this behind the
-        step's forward and behind its backward launches)"""
-        st = getattr(self, '_ahead_run', None)
-        if st is None or st.get('pending') is None or self._ahead_at() != point:
-            return
-        k, st['pending'] = st['pending'], None
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(self.device))
-        st['stream'].wait_event(ev)
-        self._ahead_issue(st, k)
 
     def _forward(self, feed, which, nets):
         """model.forward for a step whose backward follows at once: the critic head may then leave its cost's gradient behind with
@@ -366,7 +338,6 @@ class Trainer(object):
     def _fwd_bwd(self, which, nets=None, fuse_update=False, feed=None):
         """fuse_update: the caller applies the update next with nothing but a (single-replica: empty) exchange in between"""
         out = self._forward(self.feed if feed is None else feed, which, nets if nets is not None else self._nets())
-        self._ahead_release('bwd')
         if self.keep_outputs:        # (tests: the critic logits of a captured step -- static graph memory, valid after every replay)
             det = lambda v: [t.detach() for t in v] if isinstance(v, (list, tuple)) else v.detach()    # (no tape kept alive across steps)
             self.last_out[which] = {k: det(v) for k, v in out.items() if k in ('disc_fake', 'disc_real')}
@@ -376,7 +347,6 @@ class Trainer(object):
         with F.defer_wgrad_reduce(self.single_contrib):
             grads = opt.compute_gradients(op.cost)
             late = F.add_late_terms()        # (the penalty's value into the critic cost, on the penalty's stream: the backward pass did not wait for it)
-            self._ahead_release('pack')
             keep = opt.pack(grads, fuse_update=fuse_update)
             for ev in late:
                 torch.cuda.current_stream(self.device).wait_event(ev)
@@ -489,7 +459,7 @@ class Trainer(object):
         conv launches depends on"""
         c = self.cfg
         return '%s/%s/B%d/K%d/%s%s%s' % (getattr(c, 'dataset', '?'), getattr(c, 'mode', '?'), getattr(c, 'B', 0), getattr(c, 'K', 0) or 0,
-                                        '+'.join(kinds), ('/ahead' + ('' if self._ahead_at() == 'begin' else '-' + self._ahead_at())) if ahead else '',
+                                        '+'.join(kinds), '/ahead' if ahead else '',
                                         '/dp' if self.dp_graph else '')
 
     def _site_plan(self, kinds, ahead):
@@ -568,7 +538,6 @@ class Trainer(object):
         are (Discriminator.zx1: 2.6 M of the 4.1 M parameters) -- its bucket is exchanged while the conv stack's backward pass
         (two thirds of the critic's backward time) still runs; the conv stack's bucket follows.  Same sums as one bucket."""
         out = self._forward(self.feed if feed is None else feed, 'disc', nets if nets is not None else self._nets())
-        self._ahead_release('bwd')
         op = out['disc_train_op']
         opt = op.optimizer
         cutinfo = self.model.critic_cut()
@@ -582,7 +551,6 @@ class Trainer(object):
             with F.defer_wgrad_reduce(self.single_contrib):
                 grads = opt.compute_gradients(op.cost)
                 late = F.add_late_terms()
-                self._ahead_release('pack')
                 keep = opt.pack(grads)
                 for ev in late:
                     torch.cuda.current_stream(self.device).wait_event(ev)
@@ -598,7 +566,6 @@ class Trainer(object):
             w1 = opt.all_reduce(async_op=True, lo=off, hi=None)
             _optim._xlog('backward', 'critic conv stack')
             g2 = torch.autograd.grad([cut], opt.params[:k], grad_outputs=[g[-1]], allow_unused=True)
-            self._ahead_release('pack')
             keep_b = opt.pack_subset(g2, 0, k, bump=False)
             w2 = opt.all_reduce(async_op=True, lo=0, hi=off)
         for w in (w1, w2):
@@ -878,9 +845,9 @@ class Trainer(object):
     def _iteration_ring(self, it, kinds):
         """ring mode: the steps of an iteration with nothing issued between them -- as ONE graph replay where that is possible"""
         one_graph = (self.graph_enabled and it > 0 and (self.world == 1 or self.dp_graph) and not self.split_graph
-                     and all(self._calls[k] >= 1 for k in set(kinds)) and not os.environ.get('GGAN_NO_ITER_GRAPH'))
-        if (not one_graph and getattr(self, '_as_captured', False) and it > 0 and (self.world == 1 or self.dp_graph) and not self.split_graph
-                and all(self._calls[k] >= 1 for k in set(kinds)) and not os.environ.get('GGAN_NO_ITER_GRAPH')):
+                     and all(self._calls[k] >= 1 for k in set(kinds)))
+        if not one_graph and getattr(self, '_as_captured', False) and it > 0 and (self.world == 1 or self.dp_graph) and not self.split_graph \
+                and all(self._calls[k] >= 1 for k in set(kinds)):
             for k in kinds:
                 self._calls[k] += 1
             return self._iteration_as_captured(kinds)       # (the iteration graph's launches, issued eagerly: site plans, ahead-of-time passes)

@@ -41,7 +41,6 @@ def _c(t):
 
 
 import os as _os
-FUSED_CONV_BWD = _os.environ.get('GGAN_NO_FUSED_BWD') is None
 
 
 # Filter gradients as split-K partial slabs: inside `defer_wgrad_reduce` the filter-gradient kernels leave their slabs in a
@@ -101,7 +100,7 @@ def _skip_undefined(cls):
 
 class defer_wgrad_reduce(object):
     def __init__(self, enabled=True):
-        self.enabled = bool(enabled) and _os.environ.get('GGAN_NO_DEFER_WGRAD') is None
+        self.enabled = bool(enabled)
 
     def __enter__(self):
         if self.enabled:
@@ -218,7 +217,6 @@ class target_workgroups(object):
 # no process-wide plan (round 3 review: set / launch / restore sequences on C globals interleaved between threads).
 import threading as _threading
 _PLAN = _threading.local()
-_HINT_FILTER = _os.environ.get('GGAN_HINT_FILTER', '1') != '0'
 _PLAIN = [False]       # force_plain(): debug cross-check on the plain kernels (process-wide on purpose: a test switch)
 
 
@@ -336,8 +334,8 @@ def site_mismatches():
 def _geom(t):
     both, hint = getattr(_PLAN, 'both', 0), getattr(_PLAN, 'hint', 0)
     # (the hint plans the filter gradient too since round 5: with the four-wave kernel 128 workgroups x 4 chunks beat 256 x 2 beside a
-    #  second chain -- headline 4.29 -> 4.17 ms; GGAN_HINT_FILTER=0: filter gradients keep their default, as in rounds 3-4)
-    wgs, wgs_f = (both or hint), (both or (hint if _HINT_FILTER else 0))
+    #  second chain -- headline 4.29 -> 4.17 ms)
+    wgs = wgs_f = both or hint
     scope = _SITE['scope']
     if scope is not None:
         site = '%s:%d' % (scope, _SITE['n'])

@@ -1,12 +1,11 @@
 """Conv2D / Deconv2D family: forward, data gradient (plain and masked), filter gradient, channel / column sums."""
 import ctypes as C
 import os
-import os as _os
 import torch
 from torch.autograd import Function
 from .._lib import ACT_NONE, ACT_LRELU, ACT_RELU, check  # noqa: F401
 from ._core import (  # noqa: F401
-    _L, _p, _stream, _c, FUSED_CONV_BWD, _DEFER, _DATA_ONLY, _is_param, _skip_undefined, _wgrad_parts, workspace, _TARGET,
+    _L, _p, _stream, _c, _DEFER, _DATA_ONLY, _is_param, _skip_undefined, _wgrad_parts, workspace, _TARGET,
     _bwd_target, target_workgroups, _PLAN, _carries_hint, _planned_for, _geom, _new_out)
 from .pointwise import ActBwd  # noqa: F401
 
@@ -97,7 +96,7 @@ class ConvFwd(Function):
     @staticmethod
     def backward(ctx, gy):
         x, w, y = ctx.saved_tensors
-        if not torch.is_grad_enabled() and FUSED_CONV_BWD:
+        if not torch.is_grad_enabled():
             # plain backward: two launches -- the activation derivative is applied while gy is staged and the bias
             # gradient comes out of the filter-gradient kernel (no act_bwd / chansum passes, no intermediate tensor)
             with _planned_for(_bwd_target(ctx)):
@@ -107,7 +106,7 @@ class ConvFwd(Function):
         want_w = ctx.needs_input_grad[1] and not (_DATA_ONLY[0] and ctx.w_param)
         want_b = ctx.has_bias and ctx.needs_input_grad[2] and not (_DATA_ONLY[0] and ctx.b_param)
         if (ctx.act in (ACT_LRELU, ACT_RELU) and torch.is_grad_enabled() and ctx.needs_input_grad[0] and not want_w and not want_b
-                and not ctx.grad_rows and not _os.environ.get('GGAN_NO_DGRAD_MASKED')):
+                and not ctx.grad_rows):
             # a double backward is being recorded and only the data gradient is asked for (the gradient-penalty pass): the activation
             # derivative rides in the data-gradient launch, and in its backward's launches (ConvDgradMasked)
             with _planned_for(_bwd_target(ctx)):        # (the plan remembered for this layer's backward launches)
@@ -186,8 +185,7 @@ class ConvDgrad(Function):
         gy, w, out = ctx.saved_tensors
         d_gy = d_w = d_b = None
         reg = _DEFER[0]
-        if (ctx.act != ACT_NONE and ctx.has_bias and ctx.needs_input_grad[2] and reg is not None and not torch.is_grad_enabled()
-                and not _os.environ.get('GGAN_NO_ACT_CHANSUM')):
+        if ctx.act != ACT_NONE and ctx.has_bias and ctx.needs_input_grad[2] and reg is not None and not torch.is_grad_enabled():
             # activation derivative and the bias gradient in ONE pass: the channel sums leave as partial slabs for the pack kernel
             h = _c(h)
             N, Cc = h.shape[0], h.shape[1]

@@ -1,6 +1,5 @@
 """Conv3D of the state-space video critics (patch GEMM and implicit-GEMM paths)."""
 import ctypes as C
-import os
 import torch
 from torch.autograd import Function
 from .._lib import ACT_NONE, check  # noqa: F401
@@ -60,7 +59,7 @@ def _conv3d_patch(x, w, bias, stride_len, stride, act, alpha):
 
 
 def _igemm_ok(dims, kind):
-    return bool(_L().ggan_conv3d_igemm_ok(dims, kind)) and not os.environ.get('GGAN_CONV3D_PATCH_MATRIX')
+    return bool(_L().ggan_conv3d_igemm_ok(dims, kind))
 
 
 @_skip_undefined

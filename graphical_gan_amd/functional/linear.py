@@ -9,7 +9,7 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 from .._lib import ACT_NONE, check  # noqa: F401
 from ._core import (  # noqa: F401
-    _L, _p, _stream, _c, FUSED_CONV_BWD, _DATA_ONLY, _is_param, _skip_undefined, workspace, _new_out, HEAD_LOGITS, _PENDING_COSTS,
+    _L, _p, _stream, _c, _DATA_ONLY, _is_param, _skip_undefined, workspace, _new_out, HEAD_LOGITS, _PENDING_COSTS,
     _tail_value)
 from .pointwise import ActBwd  # noqa: F401
 from .conv import TALL_ROWS, ColSum  # noqa: F401
@@ -41,7 +41,7 @@ class Gemm(Function):
     def backward(ctx, g):
         a, b, out = ctx.saved_tensors
         ta, tb = ctx.ta, ctx.tb
-        if (ctx.act != ACT_NONE and not ta and not tb and not torch.is_grad_enabled() and FUSED_CONV_BWD
+        if (ctx.act != ACT_NONE and not ta and not tb and not torch.is_grad_enabled()
                 and a.shape[1] <= 1024 and a.shape[0] < TALL_ROWS):
             # (measured, tools/bench_gemm.py: for the long-K layers the masked operand loads cost more than the separate
             # act_bwd pass they replace, 27-48 us vs 26-39 us; for K <= 1024 the fused pair wins)

@@ -1,6 +1,5 @@
 """loss heads: sigmoid cross-entropy sums, means, distances, the gradient penalty."""
 import ctypes as C
-import os
 import torch
 from .. import _lib
 from torch.autograd import Function
@@ -71,7 +70,7 @@ class BceSum(Function):
         xs, zs, ws, ns, n = BceSum._tables(logits, labels, weights)
         ctx.labels, ctx.weights = labels, weights
         ctx.unit_grads = None
-        if any(ctx.needs_input_grad[2:]) and not os.environ.get('GGAN_NO_BCE_FWD_GRAD'):
+        if any(ctx.needs_input_grad[2:]):
             # a train op differentiates its cost with a unit seed (UNIT_SEEDS): the gradients for that case leave with the forward
             # launch; any other upstream gradient takes the backward kernel
             outs = BceSum._grad_buffers(logits, loss.device)
@@ -250,7 +249,7 @@ class MeanSum(Function):
         for x in xs:
             if x.numel() == 1:
                 wait_ready(x)          # (a one-element term whose producer ran on another stream and was not joined: LATE_EXT)
-        if n <= _lib.BCE_MAX and not os.environ.get('GGAN_NO_BCE_FWD_GRAD'):
+        if n <= _lib.BCE_MAX:
             # one launch for all terms; with it (as BceSum) the gradients for the unit seed of a train op, in ONE buffer so that
             # the halves of a batched critic's logits get adjacent slices (SplitRows.backward: no concatenation)
             outs = BceSum._grad_buffers(xs, ctx.dev) if any(ctx.needs_input_grad[1:]) else None
@@ -296,7 +295,7 @@ class GradPenalty(Function):
         slopes = torch.empty((B,), dtype=torch.float32, device=g.device)
         pen = torch.empty((1,), dtype=torch.float32, device=g.device)
         ctx.unit_grad = None
-        if ctx.needs_input_grad[0] and not os.environ.get('GGAN_NO_BCE_FWD_GRAD'):
+        if ctx.needs_input_grad[0]:
             key = (g.device.type, g.device.index)
             arrive = GradPenalty._ARRIVE.get(key)
             if arrive is None:

@@ -1,5 +1,4 @@
 """batch normalisation: NCHW and row-major (fused with Linear), sync-BN over the data-parallel group."""
-import os as _os
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
@@ -95,7 +94,7 @@ class LinearBatchNormRows(Function):
         """mirrors the limits of ggan_linear_bn_rows_fwd (linear_bn.hip): whole minibatch in one workgroup's LDS -- x [M, K + 4], the weight
         slice [K, 32] and the row-group partials must fit 160 KB (M = 128 with K >= 252 does not) -- rows in 16 equal groups, 16-byte
         aligned operands; anything else takes Linear + Batchnorm"""
-        if x.dim() != 2 or _os.environ.get('GGAN_NO_LINEAR_BN'):
+        if x.dim() != 2:
             return False
         M, K = x.shape
         N = w.shape[1]
@@ -130,7 +129,7 @@ class LinearBatchNormRows(Function):
         go = torch.empty_like(gs)
         need = ctx.needs_input_grad
         if (not need[0] and need[1] and mean.dim() == 1 and x.shape[1] in (64, 128, 256) and M <= 128 and M % 16 == 0 and N % 32 == 0
-                and x.data_ptr() % 16 == 0 and not _os.environ.get('GGAN_NO_LINEAR_BN_BWD')):
+                and x.data_ptr() % 16 == 0):
             # the input is noise (no data gradient): BatchNorm's backward and the weight-gradient product in one launch
             dw = torch.empty((x.shape[1], N), dtype=torch.float32, device=h.device)
             db = torch.empty((N,), dtype=torch.float32, device=h.device) if (ctx.has_bias and need[2]) else None

@@ -1,6 +1,5 @@
 """row glue of the objectives: joins / splits / fan-out of row blocks, mixture and reparameterisation ops, the wali-gp interpolates."""
 import ctypes as C
-import os
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
@@ -52,7 +51,7 @@ class Fanout(Function):
 
 def fanout(x, n=2):
     """n aliases of x whose gradients meet in one Fanout node (x itself n times where no gradient can flow)"""
-    if (not torch.is_tensor(x) or not x.is_cuda or not x.requires_grad or not torch.is_grad_enabled() or os.environ.get('GGAN_NO_FANOUT')):
+    if not torch.is_tensor(x) or not x.is_cuda or not x.requires_grad or not torch.is_grad_enabled():
         return (x,) * n
     return Fanout.apply(x, n)
 

@@ -20,6 +20,9 @@ from . import functional as F
 from . import tflib as lib
 from .tflib.ops.act import LRELU, RELU, TANH, SIGMOID
 
+NETS_TARGET_WGS = 128    # workgroups per conv launch of the two nets passes running side by side (GraphicalGAN._forward_nets_k)
+GP_TARGET_WGS = 128      # the same for a wali-gp critic step, whose penalty pass runs beside the [fake; real] pass (GraphicalGAN.launch_hint)
+
 
 class Config(object):
     def __init__(self, dataset='cifar10', batch_size=64, n_coms=0, mode=None, dim=None, dim_latent=128, bn=None,
@@ -88,8 +91,7 @@ class GraphicalGAN(object):
         # turns it on while it builds a single-graph step (fork_now) -- eager steps are host-bound and gain nothing
         # (round 2, after the kernels got shorter: +1.5 % with the mixture prior too; wali-gp: -6.6 % with the fork behind the noise
         #  launch and an immediate join, +1.3 % once the Extractor branch is a root of the graph and carries the critic's z path)
-        self.fork_nets = (not os.environ.get('GGAN_NO_FORK_NETS')
-                          and cfg.mode in ('ali', 'alice', 'alice-z', 'alice-x', 'wali', 'wali-gp', 'local_ep', 'local_epce')) or bool(os.environ.get('GGAN_FORCE_FORK_NETS'))
+        self.fork_nets = cfg.mode in ('ali', 'alice', 'alice-z', 'alice-x', 'wali', 'wali-gp', 'local_ep', 'local_epce')
         self.fork_now = False
 
     # ---- engine hooks: the static inputs of one session.run (what the reference feeds / samples) -----------------
@@ -98,18 +100,16 @@ class GraphicalGAN(object):
         """every parameter receives exactly one gradient contribution per backward pass (critic evaluated once on
         [fake; real]; the wali-gp penalty re-enters the critic)"""
         # (reconstruction terms reuse G / E; the wali-gp penalty pass uses second leaves of the critic's weights, see forward)
-        return bool(self.cfg.batch_critic) and (self.cfg.mode in ('ali', 'local_ep', 'wali') or
-                                                (self.cfg.mode == 'wali-gp' and not os.environ.get('GGAN_NO_SECOND_LEAF')))
+        return bool(self.cfg.batch_critic) and self.cfg.mode in ('ali', 'local_ep', 'wali', 'wali-gp')
 
     def launch_hint(self, which):
         """workgroups per conv launch the step should plan for (engine.Trainer._step_body -> functional.launch_hint -> ggan_conv_geom.plan_wgs), 0 = default:
         128 in wali-gp critic steps while a step graph is built -- there the penalty pass runs beside the [fake; real] pass, and launches
         of ~128 workgroups let the two chains run on different CUs (measured -1 % of the iteration even with the generator step, which
-        wants the default, planned the same way; GGAN_NO_LAUNCH_HINT)"""
+        wants the default, planned the same way)"""
         c = self.cfg
-        if (c.mode == 'wali-gp' and which == 'disc' and c.batch_critic and self.fork_nets and self.fork_now
-                and not os.environ.get('GGAN_NO_FORK_GP') and not os.environ.get('GGAN_NO_LAUNCH_HINT')):
-            return int(os.environ.get('GGAN_GP_TARGET_WGS', '128'))
+        if c.mode == 'wali-gp' and which == 'disc' and c.batch_critic and self.fork_nets and self.fork_now:
+            return GP_TARGET_WGS
         return 0
 
     def cut_tensors(self, nets):
@@ -301,11 +301,11 @@ class GraphicalGAN(object):
         if c.critic_deep:            # gan_inference_mnist.py:236-248: z1 -> '2' | concat -> zx1 -> zx2 -> Output
             z_out = self._lin('Discriminator.2', 512, 512, z_out, LRELU)
             out = self._lin('Discriminator.zx1', c.flat + 512, 512, (out, z_out), LRELU)
-            if c.fuse and not os.environ.get('GGAN_NO_HEAD_FUSION'):
+            if c.fuse:
                 return lib.ops.linear.LinearLReLULinear('Discriminator.zx2', 512, 512, 'Discriminator.Output', out, differentiable=twice)
             out = self._lin('Discriminator.zx2', 512, 512, out, LRELU)
             return lib.ops.linear.Linear('Discriminator.Output', 512, 1, out).reshape(-1)
-        if c.fuse and not os.environ.get('GGAN_NO_HEAD_FUSION'):
+        if c.fuse:
             # Linear on concat([out, z_out], 1) + LeakyReLU + the 512 -> 1 Output layer as one op
             return lib.ops.linear.LinearLReLULinear('Discriminator.zx1', c.flat + 512, 512, 'Discriminator.Output', (out, z_out),
                                                     differentiable=twice)
@@ -363,7 +363,7 @@ class GraphicalGAN(object):
         c = self.cfg
         out = self._lin('Discriminator.HyperInput', c.dim_latent + c.K, 512, (z, k), LRELU)     # Linear on concat([z, k], 1)
         out = self._lin('Discriminator.Hyper2', 512, 512, out, LRELU)
-        if c.fuse and not os.environ.get('GGAN_NO_HEAD_FUSION'):
+        if c.fuse:
             return lib.ops.linear.LinearLReLULinear('Discriminator.Hyper3', 512, 512, 'Discriminator.HyperOutput', out)
         out = self._lin('Discriminator.Hyper3', 512, 512, out, LRELU)
         out = lib.ops.linear.Linear('Discriminator.HyperOutput', 512, 1, out)
@@ -381,7 +381,7 @@ class GraphicalGAN(object):
     def HyperGenerator(self, hyper_k, hyper_noise, out_slot=None):
         """gmgan_inference_cifar10.py:150-153: onehot(k) @ Mu + eps."""
         mu = self._mu(0)
-        if self.cfg.fuse and F.MixMean.usable(hyper_k, mu, hyper_noise) and not os.environ.get('GGAN_NO_MIX_MEAN'):
+        if self.cfg.fuse and F.MixMean.usable(hyper_k, mu, hyper_noise):
             return F.MixMean.apply(hyper_k, mu, hyper_noise, out_slot)           # one pointwise launch (ggan_mix_mean)
         return F.Axpby.apply(F.Gemm.apply(hyper_k, mu, None, False, False, F.ACT_NONE, 0.0), hyper_noise, 1.0, 1.0, 0.0, out_slot)
 
@@ -404,7 +404,7 @@ class GraphicalGAN(object):
         if c.dataset == 'mnist':
             return feed['real_x']
         ring = feed.get('ring')            # Trainer.use_ring: minibatches pre-staged in HBM, walked by the optimizers' step counts
-        defer = defer and c.fuse and not os.environ.get('GGAN_NO_CAST_FUSION')
+        defer = defer and c.fuse
         if c.dataset == 'face':
             return lib.ops.act.cast_scale(feed['real_x_int'], 256., 2., noise=feed['dequant_u'], out=out_slot, ring=ring, defer=defer)
         return lib.ops.act.cast_scale(feed['real_x_int'], 255., 2., out=out_slot, ring=ring, defer=defer)
@@ -414,7 +414,7 @@ class GraphicalGAN(object):
         branches and the Extractor pass needs no noise, the second stream is forked here, with nothing in front of it."""
         c = self.cfg
         self._early = False
-        if not (self.fork_nets and self.fork_now) or (c.K and os.environ.get('GGAN_NO_EARLY_FORK_K')) or c.agg or c.dataset == 'mnist' or os.environ.get('GGAN_NO_EARLY_FORK'):
+        if not (self.fork_nets and self.fork_now) or c.agg or c.dataset == 'mnist':
             return
         dev = feed['p_z_noise'].device
         if dev.type != 'cuda' or not (c.batch_critic and 'z_pair' in feed):
@@ -465,13 +465,12 @@ class GraphicalGAN(object):
     def _forward_nets_k(self, feed, c, B, xs, zs):
         p_z = self.HyperGenerator(feed['k_onehot'], feed['p_z_noise'], zs[0]) if c.K else feed['p_z_noise']
         fork = self.fork_nets and self.fork_now and p_z.is_cuda
-        nets_target = int(os.environ.get('GGAN_NETS_TARGET_WGS', '128'))
-        if fork and nets_target > 0:
+        if fork:
             # The two passes run side by side on two streams, and in a generator step so do their backward passes.  A conv launch planned
             # for ~one workgroup per CU (the default, right for a launch that has the chip to itself) makes two such chains time-slice every
             # CU; planned for 128 workgroups each (forward, data and filter gradients: functional.target_workgroups is remembered by the
-            # layer for its backward) they run on different CUs: 1.125 -> 1.09 ms per CIFAR iteration.  GGAN_NETS_TARGET_WGS=0: default plan.
-            with F.target_workgroups(nets_target):
+            # layer for its backward) they run on different CUs: 1.125 -> 1.09 ms per CIFAR iteration.
+            with F.target_workgroups(NETS_TARGET_WGS):
                 return self._forward_nets(feed, c, B, xs, zs, p_z, fork)
         return self._forward_nets(feed, c, B, xs, zs, p_z, fork)
 
@@ -577,11 +576,10 @@ class GraphicalGAN(object):
         # leaves the penalty term out, the main stream is NOT joined with the penalty stream in front of the cost, and the Trainer adds the
         # term behind the backward pass (functional.LATE_EXT / add_late_terms) -- the [fake; real] pass's backward then starts where its
         # forward ends instead of where the penalty chain's first-order phase ends (headline -1.5 %; GGAN_NO_LATE_PENALTY: as before)
-        late_gp = (c.mode == 'wali-gp' and which == 'disc' and batched and self.fork_nets and self.fork_now and real_x.is_cuda
-                   and not os.environ.get('GGAN_NO_FORK_GP') and getattr(self, 'head_hint', False) and c.fuse and not c.K
+        gp_fork = c.mode == 'wali-gp' and which == 'disc' and batched and self.fork_nets and self.fork_now and real_x.is_cuda
+        late_gp = (gp_fork and getattr(self, 'head_hint', False) and c.fuse and not c.K
                    and not os.environ.get('GGAN_NO_HEAD_HINT') and not os.environ.get('GGAN_NO_LATE_PENALTY'))
-        if (c.mode == 'wali-gp' and which == 'disc' and batched and self.fork_nets and self.fork_now and real_x.is_cuda
-                and not os.environ.get('GGAN_NO_FORK_GP')):
+        if gp_fork:
             # (the SECOND stream, behind the Extractor branch whose q_z it reads -- not a third one: every further stream of the process
             #  shifts how the graphs' branches map onto the hardware queues, and the workload run next in the same process measured
             #  2.6 % slower.  The critic's short z path, which otherwise rides on that stream, stays on the main one in these steps.)
@@ -661,7 +659,7 @@ class GraphicalGAN(object):
     def _penalty(self, J, batched, real_x, fake_x, q_z, p_z, feed):
         # (the penalty pass reaches the critic's weights through second autograd leaves: the optimizer sums the two
         #  gradient contributions of every weight where it packs the bucket, not with an addition launch per weight)
-        with (lib.second_leaf() if (batched and not os.environ.get('GGAN_NO_SECOND_LEAF')) else lib.frozen()):
+        with (lib.second_leaf() if batched else lib.frozen()):
             return J.gradient_penalty(lambda xx, zz: self.Discriminator(xx, zz, twice=True), real_x, fake_x.detach() if batched else fake_x,
                                       q_z.detach() if batched else q_z, p_z.detach() if batched else p_z, feed['alpha'])
 
@@ -688,7 +686,7 @@ class GraphicalGAN(object):
         z_out = None
         pj = self._pending_join
         gp_on_side = self._gp_stream is not None and self.cfg.mode == 'wali-gp' and detach and self.fork_now
-        if pj is not None and not os.environ.get('GGAN_NO_Z_PATH_FORK') and not gp_on_side:
+        if pj is not None and not gp_on_side:
             # the Extractor pass is still running on the second stream: the critic's z path (a Linear on [p_z ; q_z]: two short
             # launches, and two more in the backward pass) follows it THERE, off this stream's chain of conv launches; the join
             # before the critic's tail then waits for z_out instead of q_z
@@ -698,7 +696,7 @@ class GraphicalGAN(object):
                 ev = torch.cuda.Event()
                 ev.record(self._side)
                 pj[2] = ev
-        fork_h = bool(c.K) and self.fork_nets and self.fork_now and x_cat.is_cuda and not os.environ.get('GGAN_NO_FORK_HYPER')
+        fork_h = bool(c.K) and self.fork_nets and self.fork_now and x_cat.is_cuda
         if fork_h:
             # the mixture critic on (z, k) is a chain of ~12 short launches per direction that reads nothing of the image critic: it
             # runs on the second stream beside the conv stack (autograd keeps each pass's backward on the stream of its forward)
@@ -708,7 +706,7 @@ class GraphicalGAN(object):
                 self._side.wait_stream(cur)
             ev_z = torch.cuda.Event()
             with torch.cuda.stream(self._side):
-                if z_out is None and not os.environ.get('GGAN_NO_Z_PATH_FORK'):
+                if z_out is None:
                     z_out = self._lin('Discriminator.z1', c.dim_latent, 512, z_cat, LRELU)      # (the image critic's z path too)
                     ev_z.record(self._side)
                 else:

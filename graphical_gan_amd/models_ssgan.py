@@ -14,7 +14,6 @@ What is done differently from a literal transcription (same arithmetic):
     hand the critics their weights without gradient edges (tflib.frozen), as TF's var_list does, and run the frame
     critic's conv data-gradient on the fake frames only (grad_rows).
 """
-import os
 
 import numpy as np
 import torch
@@ -74,7 +73,7 @@ class StateSpaceGAN(object):
         # chains of short launches (the transition operator's scan, the latent critics) go to a second stream beside the conv
         # stacks while the Trainer builds a single-graph step (fork_now); eager steps keep the reference's op order
         self._side = None
-        self.fork_nets = not os.environ.get('GGAN_NO_FORK_NETS')
+        self.fork_nets = True
         self.fork_now = False
 
     # ---- engine hooks: static inputs of one session.run ---------------------------------------------------------------
@@ -162,8 +161,7 @@ class StateSpaceGAN(object):
         c, zs = self.cfg, [z_l_0]
         name = 'Generator.Dynamic'
         P = lib.ops.linear.linear_params
-        if (c.fuse and c.dim_op == 256 and c.dim_l <= 16 and c.dim_t <= 16 and z_l_0.is_cuda
-                and not os.environ.get('GGAN_NO_DYN_SCAN')):
+        if c.fuse and c.dim_op == 256 and c.dim_l <= 16 and c.dim_t <= 16 and z_l_0.is_cuda:
             # the LEN-1 applications of the shared-weight operator as ONE scan launch per direction (functional.DynScan)
             # (while the graph is being built every application draws its initial values, as in the reference: same RNG stream)
             for _ in range(c.LEN - 1 if lib.initial_values_needed(name + '.Input.W') else 1):
@@ -346,7 +344,7 @@ class StateSpaceGAN(object):
         def extractor_side():
             real_x = F.Axpby.apply(feed['real_x_unit'], feed['real_x_unit'], 2.0 / self.cfg.x_div, 0.0, -1.0, slots[1])      # 2*(x/div-.5)
             return real_x, self.DynamicExtractor(self.Extractor(real_x, real_y)), self.G_Extractor(real_x, real_y)
-        if cur is not None and os.environ.get('GGAN_SSGAN_NETS') != 'scan_aside':
+        if cur is not None:
             # (round 6) the whole Extractor family on the second stream, the scan and the frame generator on this one: the two halves of the
             # nets pass share nothing, and -- autograd keeps a backward node on the stream of its forward -- neither do their backward
             # passes: the scan's LEN-1 sequential steps per direction (32 workgroups) and the short products of the latent paths hide behind
@@ -358,14 +356,8 @@ class StateSpaceGAN(object):
             fake_x = self.Generator(feed['p_z_g'], p_z_l, p_y, out_slot=slots[0])
             cur.wait_stream(self._side)
         else:
-            if cur is not None:
-                with torch.cuda.stream(self._side):
-                    p_z_l = self.DynamicGenerator(feed['p_z_l_0'], feed['epsilon'])
             real_x, q_z_l, q_z_g = extractor_side()
-            if cur is not None:
-                cur.wait_stream(self._side)
-            else:
-                p_z_l = self.DynamicGenerator(feed['p_z_l_0'], feed['epsilon'])
+            p_z_l = self.DynamicGenerator(feed['p_z_l_0'], feed['epsilon'])
             fake_x = self.Generator(feed['p_z_g'], p_z_l, p_y, out_slot=slots[0])
         return dict(real_x=real_x, q_z_l=q_z_l, q_z_g=q_z_g, p_z_l=p_z_l, p_z_g=feed['p_z_g'], fake_x=fake_x)
 

@@ -50,10 +50,10 @@ typedef struct {
     int k, stride, pad_t, pad_l;
     /* The launch plan travels with the call (round 4: these were process-wide setters; the library keeps no mutable state besides the
      * guarded profiler table and the caches of plan-time tables, so calls from several threads / streams do not interfere):
-     *   plan_wgs         workgroups the forward / data-gradient launch plans for (tile size, split-K); 0 = default (GGAN_TARGET_WGS or
-     *                    200, about one per CU: right for a launch that has the chip to itself).  A caller running TWO conv chains side
+     *   plan_wgs         workgroups the forward / data-gradient launch plans for (tile size, split-K); 0 = default (200,
+     *                    about one per CU: right for a launch that has the chip to itself).  A caller running TWO conv chains side
      *                    by side on two streams asks for ~128, so that each launch leaves CUs to the other chain.
-     *   plan_wgs_filter  the same for the filter-gradient launch (0 = GGAN_WGRAD_WGS or 256 split-K workgroups)
+     *   plan_wgs_filter  the same for the filter-gradient launch (0 = 256 split-K workgroups)
      *   plan_flags       GGAN_PLAN_PLAIN: the plain one-thread-per-output kernels (debug cross-check) */
     int plan_wgs, plan_wgs_filter, plan_flags;
 } ggan_conv_geom;

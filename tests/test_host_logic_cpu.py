@@ -439,3 +439,27 @@ def test_bench_loads_a_current_library_without_writing(lib_built, monkeypatch):
     monkeypatch.setattr(build, 'build', refuse)
     L = bench.native_library()
     assert L is _lib.load() and L.ggan_version() == _lib.ABI_VERSION
+
+
+def test_environment_switches_match_the_integration_table():
+    """every GGAN_* switch the package and the counterpart scripts read is a row of INTEGRATION.md section 6, and every row is still read
+    (bench.py's own GGAN_BENCH_* switches are documented there too, below the table)"""
+    import os
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    used = set()
+    for top in ('graphical_gan_amd', 'scripts'):
+        for d, dirs, files in os.walk(os.path.join(root, top)):
+            dirs[:] = [x for x in dirs if x not in ('__pycache__', 'build')]
+            for fn in files:
+                if fn.endswith(('.py', '.hip', '.h')):
+                    with open(os.path.join(d, fn)) as f:
+                        used.update(re.findall(r'''['"](GGAN_[A-Z0-9_]+)['"]''', f.read()))
+    with open(os.path.join(root, 'INTEGRATION.md')) as f:
+        text = f.read()
+    section = text[text.index('## 6. '):]
+    section = section[:section.index('\n## ')] if '\n## ' in section else section
+    rows = [ln for ln in section.splitlines() if ln.startswith('| `GGAN_')]
+    documented = {n for ln in rows for n in re.findall(r'GGAN_[A-Z0-9_]+', ln.split('|')[1]) if not n.startswith('GGAN_BENCH_')}
+    assert used - documented == set(), 'read by the code but not in INTEGRATION.md section 6'
+    assert documented - used == set(), 'in INTEGRATION.md section 6 but read nowhere'
