@@ -13,8 +13,9 @@ PACK_MAX = 64
 HEAD_BCE_MAX_ROWS = 2048             # include/ggan.h: GGAN_HEAD_BCE_MAX_ROWS
 BCE_HEADS = 2                        # include/ggan.h: GGAN_BCE_HEADS
 PACK_ARRIVE_INTS = 33 * 1024          # include/ggan.h: GGAN_PACK_ARRIVE_INTS (arrival counters of ggan_pack_adam)
+POSTERIOR_MAX_K = 8192               # include/ggan.h: GGAN_POSTERIOR_MAX_K
 BCE_MAX = 16
-ABI_VERSION = 600                    # include/ggan.h: GGAN_ABI_VERSION (struct layouts and entry points this module binds)
+ABI_VERSION = 700                    # include/ggan.h: GGAN_ABI_VERSION (struct layouts and entry points this module binds)
 
 
 class ConvGeom(C.Structure):
@@ -72,6 +73,8 @@ SIGNATURES = {
     'ggan_noise_fill': (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _P]),
     'ggan_gmm_latent_fwd': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _P]),
     'ggan_gmm_latent_bwd': (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P]),
+    'ggan_gmm_posterior_assign': (_I, [_P, _P, _F, _I, _I, _I, _I, _P, _P, _P, _P]),
+    'ggan_cluster_accuracy': (_I, [_P, _P, _P, _I, _I, _P, _P]),
     'ggan_gemm_split': (_I, [_I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _I, _P, _I, _F, _P, _Z, _P]),
     'ggan_gemm_colsum': (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
     'ggan_dyn_scan_fwd': (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P]),

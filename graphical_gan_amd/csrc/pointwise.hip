@@ -1026,6 +1026,96 @@ __global__ __launch_bounds__(256) void gmm_latent_bwd_k(const float* __restrict_
 }
 
 
+// ---- the test-set pass of the gmgan scripts (gmgan_inference_mnist.py:338,511-529): q_k_probs = softmax(q_k_logits) -- no Gumbel
+//      noise, no temperature --, the row argmax (the sample's cluster) and the running column argmax over the whole test set (the
+//      sample that labels each cluster).  A workgroup per row; the logits are summed exactly as gmm_latent_fwd_k sums them (same
+//      bits).  Column argmax across launches: one 64-bit atomicMax per (row, component) on (p bits << 32 | ~row): p >= 0, so the
+//      float's bits order like the float, and the complemented row makes the LOWEST row win a tie (np.argmax(prob_c, axis=0)). ----
+__global__ __launch_bounds__(256) void gmm_posterior_assign_k(const float* __restrict__ z, const float* __restrict__ mu, float log_pi,
+                                                              int K, int D, int row0, float* __restrict__ probs,
+                                                              int32_t* __restrict__ assign, unsigned long long* __restrict__ colbest) {
+    extern __shared__ float sv[];          // K values
+    __shared__ float red[32];
+    __shared__ float bv[4];
+    __shared__ int bi[4];
+    const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float* zb = z + (size_t)b * D;
+    for (int j = wave; j < K; j += 4) {
+        const float* mj = mu + (size_t)j * D;
+        float s = 0.f;
+        for (int d = lane; d < D; d += 64) {
+            const float t = zb[d] - mj[d];
+            s = fmaf(t, t, s);
+        }
+        s = wave_sum(s);
+        if (lane == 0) sv[j] = -0.5f * s + log_pi;
+    }
+    __syncthreads();
+    float m = -INFINITY;
+    for (int j = threadIdx.x; j < K; j += 256) m = fmaxf(m, sv[j]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    if (lane == 0) red[wave] = m;
+    __syncthreads();
+    m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    float e = 0.f;
+    for (int j = threadIdx.x; j < K; j += 256) {
+        const float t = expf(sv[j] - m);
+        sv[j] = t;
+        e += t;
+    }
+    const float inv = 1.f / block_sum(e, red + 8);
+    const unsigned grow = (unsigned)(row0 + b);
+    const unsigned long long low = 0xFFFFFFFFull - grow;
+    float best = -1.f;
+    int arg = 0;
+    for (int j = threadIdx.x; j < K; j += 256) {
+        const float p = sv[j] * inv;
+        if (probs) probs[(size_t)b * K + j] = p;
+        if (p > best) { best = p; arg = j; }            // (ascending j per thread: the first index wins a tie)
+        atomicMax(colbest + j, ((unsigned long long)__float_as_uint(p) << 32) | low);
+    }
+    // row argmax: larger p, on a tie the smaller index (np.argmax)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(best, o, 64);
+        const int oi = __shfl_xor(arg, o, 64);
+        if (ov > best || (ov == best && oi < arg)) { best = ov; arg = oi; }
+    }
+    if (lane == 0) { bv[wave] = best; bi[wave] = arg; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; ++w)
+            if (bv[w] > best || (bv[w] == best && bi[w] < arg)) { best = bv[w]; arg = bi[w]; }
+        assign[grow] = arg;
+    }
+}
+
+// Label propagation and the match count of gmgan_inference_mnist.py:518-528 in one workgroup: label_of[j] = labels[row of colbest[j]],
+// correct = #{b : label_of[assign[b]] == labels[b]} (an integer: the same on every run).
+__global__ __launch_bounds__(256) void cluster_accuracy_k(const int32_t* __restrict__ assign, const int32_t* __restrict__ labels,
+                                                          const unsigned long long* __restrict__ colbest, int N, int K,
+                                                          int32_t* __restrict__ correct) {
+    extern __shared__ int label_of[];      // K values
+    __shared__ int red[4];
+    for (int j = threadIdx.x; j < K; j += 256) {
+        const unsigned row = 0xFFFFFFFFu - (unsigned)(colbest[j] & 0xFFFFFFFFull);
+        label_of[j] = row < (unsigned)N ? labels[row] : (-2147483647 - 1);      // (an unwritten column: a label nothing carries)
+    }
+    __syncthreads();
+    int n = 0;
+    for (int b = threadIdx.x; b < N; b += 256) {
+        const int a = assign[b];
+        n += (a >= 0 && a < K && label_of[a] == labels[b]) ? 1 : 0;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = n;
+    __syncthreads();
+    if (threadIdx.x == 0) correct[0] = red[0] + red[1] + red[2] + red[3];
+}
+
+
 // ---- all the noise of one session.run in ONE launch (the TF graph draws p_z ~ N(0,1), k ~ Cat(1/K) as a one-hot, Gumbel U, the GP
 //      alpha and the dequantisation noise with separate random ops: gmgan_inference_cifar10.py:115-120,344-346).  Counter-based
 //      generator (Philox4x32-10, key = seed, counter = (element group, tensor, draw number)); the draw number lives in device
@@ -1599,6 +1689,25 @@ int ggan_gmm_latent_bwd(const float* z, const float* mu, const float* k, const f
     GGAN_CHECK_ARG(B > 0 && B <= kGmmMaxK && K > 0 && K <= kGmmMaxK && D > 0 && temp > 0.f, "bad shape");
     GGAN_LAUNCH("gmm_latent_bwd", 4.0 * B * K * D, 0, gmm_latent_bwd_k, dim3(B + (dmu ? K : 0)), dim3(256), 0, (hipStream_t)stream, z, mu, k,
                 g_logits, g_k, dz, dmu, B, K, D, 1.f / temp);
+    return 0;
+}
+
+int ggan_gmm_posterior_assign(const float* z, const float* mu, float log_pi, int B, int K, int D, int row0, float* probs,
+                              int32_t* assign, uint64_t* colbest, ggan_stream_t stream) {
+    GGAN_CHECK_ARG(z && mu && assign && colbest, "null pointer");
+    GGAN_CHECK_ARG(B > 0 && K > 0 && K <= GGAN_POSTERIOR_MAX_K && D > 0 && row0 >= 0 && (long long)row0 + B <= 0x7FFFFFFFll, "bad shape");
+    GGAN_LAUNCH("gmm_posterior_assign", 3.0 * B * K * D, 4.0 * ((double)B * D + (double)K * D + (probs ? (double)B * K : 0.0)),
+                gmm_posterior_assign_k, dim3(B), dim3(256), (size_t)K * sizeof(float), (hipStream_t)stream, z, mu, log_pi, K, D, row0,
+                probs, assign, (unsigned long long*)colbest);
+    return 0;
+}
+
+int ggan_cluster_accuracy(const int32_t* assign, const int32_t* labels, const uint64_t* colbest, int N, int K, int32_t* correct,
+                          ggan_stream_t stream) {
+    GGAN_CHECK_ARG(assign && labels && colbest && correct, "null pointer");
+    GGAN_CHECK_ARG(N > 0 && K > 0 && K <= GGAN_POSTERIOR_MAX_K, "bad shape");
+    GGAN_LAUNCH("cluster_accuracy", 0, 8.0 * N + 12.0 * K, cluster_accuracy_k, dim3(1), dim3(256), (size_t)K * sizeof(int), (hipStream_t)stream,
+                assign, labels, (const unsigned long long*)colbest, N, K, correct);
     return 0;
 }
 

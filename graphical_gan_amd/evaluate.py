@@ -1,0 +1,310 @@
+"""The observation passes of the reference's driver loops, forward only, on a Trainer's live parameters:
+
+  dev_costs          `dev gen cost` (+ `dev rec cost` / `dev reg cost` where the MODE has a rec_penalty), averaged over the dev set
+                     (gmgan_inference_mnist.py:484-504, gan_inference_cifar10.py:456-477);
+  cluster_accuracy   `testing accuracy`: the unsupervised clustering accuracy of q_k_probs = softmax(q_k_logits) on the test set
+                     (gmgan_inference_mnist.py:338,511-529) -- ggan_gmm_posterior_assign per minibatch, ggan_cluster_accuracy at the end;
+  sample_grid        generate_image: Generator(HyperGenerator(tile(eye(N_COMS)), fixed noise)) with one column per component
+                     (gmgan_inference_mnist.py:406-419), or Generator(fixed noise) with N_VIS = 2*BATCH_SIZE rows
+                     (gan_inference_cifar10.py:370-378);
+  reconstructions    reconstruct_image: real / Generator(Extractor(x)) pairs on a fixed dev minibatch (gmgan_inference_mnist.py:429-443).
+
+The passes are safe in the middle of training: they run under torch.no_grad() on the current stream only (no second stream, no
+collective), with a feed dict and a noise generator state of their own -- the Trainer's static feed buffers, ring slots and noise state
+are never written -- and with numpy's global RNG state restored afterwards (the loaders' shuffles and the layers' initial-value draws
+consume it; the training data order must not depend on whether evaluation is on).  BatchNorm uses the statistics of each evaluation
+minibatch, as the reference's graph does (tflib/ops/batchnorm.py: the scripts pass no is_training).
+
+`python -m graphical_gan_amd.evaluate CKPT --script gmgan_inference_mnist [--data-dir DIR]` scores a saved checkpoint."""
+import argparse
+import contextlib
+import os
+import time
+
+import numpy as np
+import torch
+
+from . import functional as F
+from . import tflib as lib
+
+EVAL_SEED = 7919          # offset of the evaluator's noise seeds from the settings seed (the Trainer's stream of draws is not touched)
+
+# the reference's output file names, per script: (samples, reconstructions), formatted with frame= and mode=
+_NAMES = {
+    'gan_inference_mnist': ('{mode}_mnist_samples_{frame}.png', '{mode}_mnist_reconstruction_{frame}.png'),
+    'gmgan_inference_cifar10': ('{frame}_samples_{mode}.png', '{mode}_reconstruction_{frame}.png'),
+    'gmgan_inference_svhn': ('{frame}_samples_{mode}.png', '{mode}_reconstruction_{frame}.png'),
+    'gmgan_inference_mnist': ('{frame}_samples_{mode}.png', '{frame}_reconstruction_{mode}.png'),
+    'gmgan_inference_face': ('{frame}_samples_{mode}.png', '{frame}_reconstruction_{mode}.png'),
+}
+_DEFAULT_NAMES = ('{mode}_samples_{frame}.png', '{mode}_reconstruction_{frame}.png')       # gan_inference_cifar10 / svhn / face
+_DEFAULT_NAMES_K = _NAMES['gmgan_inference_cifar10']                                         # a mixture model of no named script
+
+
+def host_cluster_accuracy(prob_c, y):
+    """gmgan_inference_mnist.py:513-529 as the reference runs it (the +1000 relabelling included): prob_c [N, K], y [N] -> accuracy.
+    (With more than 1000 components the relabelled values collide with later cluster indices and the loop relabels twice; every
+    reference script has N_COMS <= 100.  ggan_cluster_accuracy propagates the labels directly.)"""
+    prob_c, y = np.asarray(prob_c), np.asarray(y)
+    ind_max_prob = np.argmax(prob_c, axis=0)
+    labels_for_clusters = y[ind_max_prob]
+    clusters = np.argmax(prob_c, axis=1)
+    for i in range(labels_for_clusters.shape[0]):
+        clusters[clusters == i] = labels_for_clusters[i] + 1000
+    clusters = clusters - 1000
+    return float(np.mean((clusters == y).astype(np.float32)))
+
+
+def decode_cluster_accuracy(assign, labels, colbest):
+    """the rule ggan_cluster_accuracy applies, on the host: the correct count from assign [N], labels [N] and the column keys colbest [K]
+    (uint64: p bits << 32 | 0xFFFFFFFF - row)"""
+    assign, labels = np.asarray(assign, np.int64), np.asarray(labels, np.int64)
+    rows = 0xFFFFFFFF - (np.asarray(colbest).astype(np.uint64) & np.uint64(0xFFFFFFFF)).astype(np.int64)
+    label_of = np.where(rows < len(labels), labels[np.minimum(rows, len(labels) - 1)], np.iinfo(np.int64).min)
+    return int(np.sum(label_of[assign] == labels))
+
+
+def column_keys(P):
+    """the colbest keys of ggan_gmm_posterior_assign for fp32 probabilities P [N, K] (host restatement)"""
+    P = np.ascontiguousarray(P, dtype=np.float32)
+    bits = P.view(np.uint32).astype(np.uint64) << np.uint64(32)
+    keys = bits | (np.uint64(0xFFFFFFFF) - np.arange(P.shape[0], dtype=np.uint64))[:, None]
+    return keys.max(axis=0)
+
+
+def _split(b):
+    """a loader minibatch -> (images, labels or None)"""
+    if isinstance(b, (tuple, list)):
+        return b[0], (b[1] if len(b) > 1 else None)
+    return b, None
+
+
+class Evaluator(object):
+    def __init__(self, trainer, settings, keep_noise=False):
+        """trainer: an engine.Trainer of an image script (models.GraphicalGAN); settings: the script's UPPERCASE block (BATCH_SIZE, MODE,
+        N_VIS, N_COMS, SEED).  keep_noise (tests): dev_costs keeps the noise it drew per batch in self.kept."""
+        self.tr, self.S = trainer, settings
+        self.model, self.cfg, self.device = trainer.model, trainer.cfg, trainer.device
+        c = self.cfg
+        seed = int(settings.get('SEED', 0)) + EVAL_SEED
+        self.feed = self.model.feed_buffers(self.device)
+        self.feed['rng_state'] = F.noise_state(self.device, seed)
+        # fixed grid noise, drawn once from the settings seed (gmgan_inference_mnist.py:406-407, gan_inference_cifar10.py:371)
+        n_vis = int(settings.get('N_VIS', (c.K * 10) if c.K else 2 * c.B))
+        rng = np.random.RandomState(seed)
+        self.fixed_noise = torch.as_tensor(rng.normal(size=(n_vis, c.dim_latent)).astype(np.float32)).to(self.device)
+        self.fixed_k = None
+        if c.K:
+            assert n_vis % c.K == 0, 'N_VIS must be a multiple of N_COMS (gmgan_inference_mnist.py:80)'
+            self.fixed_k = torch.as_tensor(np.tile(np.eye(c.K, dtype=np.float32), (n_vis // c.K, 1))).to(self.device)
+        self.keep_noise, self.kept = keep_noise, []
+        self.fixed_data = None            # the reconstruction minibatch (host), set_fixed_data / the first dev minibatch
+        self.last_seconds = 0.0           # wall time of the last pass (device work included)
+
+    # ---- plumbing ------------------------------------------------------------------------------------------------------------------
+    @contextlib.contextmanager
+    def _guard(self):
+        """a pass: no tape, the current stream only, the model's step-building state and numpy's RNG state as they were"""
+        m = self.model
+        saved = (m._pending_join, getattr(m, '_noise_event', None), m._early, m.fork_now, getattr(m, 'head_hint', False))
+        np_state = np.random.get_state()
+        m.fork_now, m._early, m._pending_join, m.head_hint = False, False, None, False
+        t0 = time.time()
+        try:
+            with torch.no_grad():
+                yield
+        finally:
+            m._pending_join, m._noise_event, m._early, m.fork_now, m.head_hint = saved
+            np.random.set_state(np_state)
+            self.last_seconds = time.time() - t0
+
+    def _stage(self, batches, want_labels=False):
+        """minibatches (host arrays or device tensors, optionally (images, labels) tuples) -> (device [n, B, D] in the placeholder's
+        dtype, device int32 labels [n*B] or None).  One upload per pass; a trailing partial minibatch is dropped, as the loaders do."""
+        c = self.cfg
+        xs, ys = [], []
+        for b in batches:
+            x, y = _split(b)
+            if x.shape[0] != c.B:
+                continue
+            xs.append(x)
+            ys.append(y)
+        if not xs:
+            raise ValueError('no full minibatch of %d rows to evaluate on' % c.B)
+        dt = torch.float32 if c.dataset == 'mnist' else torch.int32
+        if all(torch.is_tensor(x) for x in xs):
+            X = torch.stack([x.to(self.device, dt).reshape(c.B, -1) for x in xs])
+        else:
+            X = torch.as_tensor(np.stack([np.asarray(x).reshape(c.B, -1) for x in xs]).astype(np.float32 if c.dataset == 'mnist' else np.int32))
+            X = X.to(self.device)
+        Y = None
+        if want_labels:
+            if any(y is None for y in ys):
+                raise ValueError('cluster accuracy needs labelled minibatches')
+            Y = torch.as_tensor(np.concatenate([np.asarray(y).reshape(-1) for y in ys]).astype(np.int32)).to(self.device)
+        return X, Y
+
+    def _load(self, x):
+        self.model.set_batch(self.feed, x)
+        self.model.sample_noise(self.feed)
+        if self.keep_noise:
+            self.kept.append({k: v.detach().cpu().numpy().copy() for k, v in self.feed.items()
+                              if torch.is_tensor(v) and k != 'rng_state' and k not in ('x_pair', 'z_pair', 'k_pair')})
+
+    # ---- the passes ----------------------------------------------------------------------------------------------------------------
+    def dev_costs(self, batches):
+        """mean over the dev minibatches of gen_cost, and of rec_penalty and gen_cost - rec_penalty where the MODE has one ->
+        {'dev gen cost': .., 'dev rec cost': .., 'dev reg cost': ..}.  One host synchronisation per pass."""
+        with self._guard():
+            X, _ = self._stage(batches)
+            n = X.shape[0]
+            vals = torch.zeros((n, 2), dtype=torch.float32, device=self.device)
+            has_rec = False
+            self.kept = []
+            for i in range(n):
+                self._load(X[i])
+                out = self.model.forward(self.feed, 'gen')
+                vals[i, 0].copy_(out['gen_cost'].reshape(()))
+                rec = out.get('rec_penalty')
+                if rec is not None:
+                    has_rec = True
+                    vals[i, 1].copy_(rec.reshape(()))
+            assert not F.pending_costs(), 'an evaluation cost was left owing its value'
+            v = vals.cpu().numpy()
+        res = {'dev gen cost': float(np.mean(v[:, 0]))}
+        if has_rec:             # (gmgan_inference_mnist.py:488-496: per batch, in float32, as session.run returns them)
+            res['dev rec cost'] = float(np.mean(v[:, 1]))
+            res['dev reg cost'] = float(np.mean(v[:, 0] - v[:, 1]))
+        return res
+
+    def cluster_accuracy(self, batches, return_probs=False):
+        """testing accuracy on labelled minibatches -> float, or (float, probs [N, K] numpy) with return_probs"""
+        c = self.cfg
+        if not c.K:
+            raise ValueError('cluster accuracy needs a mixture prior (N_COMS)')
+        with self._guard():
+            X, Y = self._stage(batches, want_labels=True)
+            n, B = X.shape[0], c.B
+            N = n * B
+            assign = torch.empty((N,), dtype=torch.int32, device=self.device)
+            colbest = torch.zeros((c.K,), dtype=torch.int64, device=self.device)
+            correct = torch.zeros((1,), dtype=torch.int32, device=self.device)
+            probs = torch.empty((N, c.K), dtype=torch.float32, device=self.device) if return_probs else None
+            log_pi = float(np.log(np.float32(1.0) / np.float32(c.K)))          # (as HyperExtractor)
+            mu = self.model._mu()
+            for i in range(n):
+                self._load(X[i])
+                q_z = self.model.Extractor(self.model.real_x(self.feed))
+                F.gmm_posterior_assign_(q_z, mu, log_pi, i * B, assign, colbest, probs[i * B:(i + 1) * B] if probs is not None else None)
+            F.cluster_accuracy_(assign, Y, colbest, correct)
+            acc = int(correct.item()) / float(N)
+            if return_probs:
+                self.last_assign, self.last_colbest, self.last_labels = assign.cpu().numpy(), colbest.cpu().numpy(), Y.cpu().numpy()
+                return acc, probs.cpu().numpy()
+        return acc
+
+    def _to_unit(self, x):
+        """generator output -> [0, 1] images for save_images"""
+        lo = 0.0 if self.cfg.out_act == 'sigmoid' else -1.0
+        return np.clip((x - lo) / (1.0 - lo), 0, 1)
+
+    def sample_grid(self):
+        """the fixed-noise samples of generate_image -> numpy [N_VIS, OUTPUT_DIM] (generator output range).  gmgan: row r is component
+        r % N_COMS, so that a grid of N_VIS / N_COMS rows and N_COMS columns has one component per column."""
+        with self._guard():
+            p_z = self.model.HyperGenerator(self.fixed_k, self.fixed_noise) if self.cfg.K else self.fixed_noise
+            return self.model.Generator(p_z).float().cpu().numpy()
+
+    def set_fixed_data(self, batch):
+        images, _ = _split(batch)
+        self.fixed_data = np.asarray(images.cpu() if torch.is_tensor(images) else images).reshape(self.cfg.B, -1)
+
+    def reconstructions(self, batch=None):
+        """reconstruct_image: (real [B, D], Generator(Extractor(real)) [B, D]) on the fixed dev minibatch, as numpy"""
+        if batch is not None:
+            self.set_fixed_data(batch)
+        assert self.fixed_data is not None, 'no reconstruction minibatch: pass one or call set_fixed_data'
+        with self._guard():
+            X, _ = self._stage([self.fixed_data])
+            self.model.set_batch(self.feed, X[0])
+            self.model.sample_noise(self.feed)
+            real_x = self.model.real_x(self.feed)
+            q = self.model.Extractor(real_x, eps=self.feed['q_eps']) if self.cfg.agg else self.model.Extractor(real_x)
+            q_z = q[0] if isinstance(q, tuple) else q
+            rec = self.model.Generator(q_z)
+            return real_x.float().cpu().numpy(), rec.float().cpu().numpy()
+
+    def save_images(self, out_dir, frame, script=None):
+        """writes the sample grid and the reconstruction pairs under the reference's file names; returns the paths"""
+        c = self.cfg
+        name = os.path.splitext(os.path.basename(script or self.S.get('SCRIPT', '')))[0]
+        fs, fr = _NAMES.get(name, _DEFAULT_NAMES_K if c.K else _DEFAULT_NAMES)
+        mode = self.S.get('MODE', c.mode)
+        shape = (-1, c.C, c.S, c.S)
+        paths = []
+        grid = self._to_unit(self.sample_grid()).reshape(shape)
+        p = os.path.join(out_dir, fs.format(frame=frame, mode=mode))
+        lib.save_images.save_images(grid, p, size=[grid.shape[0] // c.K, c.K] if c.K else None)
+        paths.append(p)
+        if self.fixed_data is not None:
+            real, rec = self.reconstructions()
+            pairs = np.empty((2 * c.B, c.output_dim), dtype=np.float32)
+            pairs[0::2], pairs[1::2] = self._to_unit(real), self._to_unit(rec)
+            p = os.path.join(out_dir, fr.format(frame=frame, mode=mode))
+            lib.save_images.save_images(pairs.reshape(shape), p)
+            paths.append(p)
+        return paths
+
+
+# ---- command line: score a saved checkpoint ----------------------------------------------------------------------------------------
+def main(argv=None):
+    """builds the script's model, restores the checkpoint's weights, runs the evaluation passes once and prints them"""
+    from . import checkpoint, run
+    from .engine import Trainer
+    ap = argparse.ArgumentParser(prog='python -m graphical_gan_amd.evaluate', description=main.__doc__)
+    ap.add_argument('ckpt', help='a params_<it>.npz written by run.train / checkpoint.save')
+    ap.add_argument('--script', required=True, help='the image script the checkpoint was trained with, e.g. gmgan_inference_mnist')
+    ap.add_argument('--data-dir', default=os.environ.get('GGAN_DATA_DIR', ''))
+    ap.add_argument('--mode', default=None, help="the script's MODE (default: the script's own)")
+    ap.add_argument('--out-dir', default=None, help='also write the sample grid and the reconstructions here')
+    ap.add_argument('--set', action='append', default=[], metavar='KEY=VALUE', help='override an UPPERCASE setting (int / float / str)')
+    a = ap.parse_args(argv)
+    over = {}
+    for kv in a.set:
+        k, v = kv.split('=', 1)
+        for conv in (int, float):
+            try:
+                v = conv(v)
+                break
+            except ValueError:
+                pass
+        over[k] = v
+    if a.mode:
+        over['MODE'] = a.mode
+    S = run.reference_block(a.script, **over)
+    S.update(DATA_DIR=a.data_dir, SCRIPT=a.script)
+    tr = Trainer(run.config(S), device=lib.get_device(), graph=False)
+    checkpoint.restore(a.ckpt, tr)
+    res = evaluate_once(tr, S, out_dir=a.out_dir)
+    for k in sorted(res):
+        print('%s\t%s' % (k, res[k]))
+    return res
+
+
+def evaluate_once(tr, S, out_dir=None, frame='eval'):
+    """every pass the script's data allow, once -> {name: value}"""
+    from . import run
+    ev = Evaluator(tr, S)
+    dev, test = run.eval_sets(S, tr.model, tr.device)
+    res = dict(ev.dev_costs(dev))
+    if tr.cfg.K and test is not None:
+        res['testing accuracy'] = ev.cluster_accuracy(test)
+    if out_dir:
+        os.makedirs(out_dir, exist_ok=True)
+        ev.set_fixed_data(dev[0])
+        ev.save_images(out_dir, frame)
+    return res
+
+
+if __name__ == '__main__':
+    main()

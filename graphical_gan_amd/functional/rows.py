@@ -3,7 +3,7 @@ import ctypes as C
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
-from .._lib import ACT_NONE, check  # noqa: F401
+from .._lib import ACT_NONE, POSTERIOR_MAX_K, check  # noqa: F401
 from ._core import _L, _p, _stream, _dev, _c, _DATA_ONLY, _is_param, _skip_undefined, _new_out, _adjacent  # noqa: F401
 from .linear import Gemm  # noqa: F401
 
@@ -315,3 +315,30 @@ class RowLerp(Function):
         gx = RowLerp.apply(g, z, alpha) if ctx.needs_input_grad[0] else None
         gy = RowLerp.apply(z, g, alpha) if ctx.needs_input_grad[1] else None
         return gx, gy, None
+
+
+# ---- the test-set pass of the gmgan scripts (forward only: no autograd) -------------------------------------------------------------
+def gmm_posterior_assign_(z, mu, log_pi, row0, assign, colbest, probs=None):
+    """q_k_probs = softmax(q_k_logits) of the rows row0 .. row0+B-1 (gmgan_inference_mnist.py:338; the logits of GmmLatent, no Gumbel
+    noise, no temperature) in ONE launch (ggan_gmm_posterior_assign): assign[row0 + b] = the row's argmax, colbest (uint64 as int64[K],
+    zeroed by the caller at the start of a pass) takes the running column argmax; probs (optional [B, K]) receives p.  In place."""
+    z, mu = _c(z), _c(mu)
+    B, D = z.shape
+    K = mu.shape[0]
+    assert tuple(mu.shape) == (K, D) and K <= POSTERIOR_MAX_K, (z.shape, mu.shape)
+    assert assign.dtype == torch.int32 and assign.is_contiguous() and row0 >= 0 and row0 + B <= assign.numel()
+    assert colbest.dtype == torch.int64 and colbest.is_contiguous() and colbest.numel() == K
+    if probs is not None:
+        assert probs.dtype == torch.float32 and probs.is_contiguous() and tuple(probs.shape) == (B, K)
+    check(_L().ggan_gmm_posterior_assign(_p(z), _p(mu), float(log_pi), B, K, D, int(row0), _p(probs), _p(assign), _p(colbest), _stream()),
+          'ggan_gmm_posterior_assign')
+
+
+def cluster_accuracy_(assign, labels, colbest, correct):
+    """gmgan_inference_mnist.py:518-528 on the device (ggan_cluster_accuracy): correct[0] = the number of rows whose cluster's label (the
+    label of the row that maximises that cluster's probability) is their own.  assign / labels int32[N], colbest int64[K]."""
+    N, K = assign.numel(), colbest.numel()
+    assert labels.dtype == torch.int32 and labels.numel() == N and labels.is_contiguous() and assign.dtype == torch.int32
+    assert correct.dtype == torch.int32 and correct.numel() >= 1 and K <= POSTERIOR_MAX_K
+    check(_L().ggan_cluster_accuracy(_p(assign), _p(labels), _p(colbest), N, K, _p(correct), _stream()), 'ggan_cluster_accuracy')
+    return correct

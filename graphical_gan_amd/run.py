@@ -61,6 +61,60 @@ def _batches(S, model, device):
     return forever(), 'synthetic'
 
 
+# ---- the evaluation passes of the reference's driver loops (evaluate.py) ------------------------------------------------------------
+EVAL_KEYS = ('DEV_EVERY', 'ACCURACY_EVERY', 'SAMPLE_EVERY')
+
+
+def eval_plan(S):
+    """{key: every} of the evaluation passes a settings block switches on, or None (the keys are absent by default: no pass runs)"""
+    plan = {k: int(S[k]) for k in EVAL_KEYS if S.get(k)}
+    return plan or None
+
+
+def eval_due(plan, it):
+    """the passes that fire after iteration `it`: it % N == N - 1, the reference's cadence (gmgan_inference_mnist.py:484,507,511)"""
+    return [k for k, n in sorted((plan or {}).items()) if it % n == n - 1]
+
+
+def eval_settings(script):
+    """the cadence the reference's image script runs its passes at (dev costs every 100 iterations; samples / reconstructions every
+    5000; the testing accuracy every 5000, gmgan_inference_mnist only), each overridable by $GGAN_<KEY> (e.g. GGAN_DEV_EVERY=10)"""
+    name = os.path.splitext(os.path.basename(script))[0]
+    S = dict(DEV_EVERY=100, SAMPLE_EVERY=5000, SCRIPT=name)
+    if name == 'gmgan_inference_mnist':
+        S['ACCURACY_EVERY'] = 5000
+    for k in EVAL_KEYS:
+        if os.environ.get('GGAN_' + k):
+            S[k] = int(os.environ['GGAN_' + k])
+    return S
+
+
+def eval_sets(S, model, device):
+    """(dev minibatches, labelled test minibatches or None) for the evaluation passes: tflib.mnist.load's dev and test generators, the
+    test split of the CIFAR-10 / SVHN loaders, celebA's dev split -- or, without the dataset, a synthetic dev set of the training ring's
+    shapes and no test set.  Host lists of one epoch each; numpy's global RNG state (which the loaders' shuffles consume) is restored."""
+    ds, B = S['DATASET'], S['BATCH_SIZE']
+    state = np.random.get_state()
+    try:
+        if S.get('SYNTHETIC') == 'force':
+            raise FileNotFoundError('synthetic data requested')
+        if ds == 'mnist':
+            _, dev, test = lib.mnist.load(B, B)
+            return list(dev()), list(test())
+        if ds in ('cifar10', 'svhn'):
+            _, dev = getattr(lib, ds).load(B, S.get('DATA_DIR', ''))
+            dev = list(dev())
+            return dev, dev
+        if ds == 'face':
+            _, dev = lib.celebA.load(B, S.get('DATA_DIR', ''))
+            return list(dev()), None
+        raise ValueError('no evaluation passes for dataset %r' % ds)
+    except FileNotFoundError:
+        return [t for t in model.synthetic_ring(device, n=8, seed=4321)], None
+    finally:
+        np.random.set_state(state)
+
+
 # ---- the reference scripts' UPPERCASE hyper-parameter blocks, as data ------------------------------------------------------------
 # per script: what differs between the image scripts (gan_inference_cifar10.py:39-79, gan_inference_svhn.py:32-72,
 # gan_inference_mnist.py:31-70, gan_inference_face.py:33-50, gmgan_inference_cifar10.py:39-87, gmgan_inference_svhn.py:33-81,
@@ -181,6 +235,17 @@ def train(S, cfg, model=None, out_dir=None):
     if timed:
         ev0 = torch.cuda.Event(enable_timing=True)
         ev0.record(torch.cuda.current_stream(device))
+    plan = eval_plan(S)
+    evaluator = None
+    if plan and (tr.world == 1 or torch.distributed.get_rank() == 0):     # (replicas: rank 0 evaluates and logs)
+        from .evaluate import Evaluator
+        evaluator = Evaluator(tr, S)
+        ev_dev, ev_test = eval_sets(S, tr.model, device)
+        evaluator.set_fixed_data(ev_dev[0])
+        if 'ACCURACY_EVERY' in plan and (ev_test is None or not tr.cfg.K):
+            print('[run] testing accuracy skipped: %s' % ('no mixture prior (N_COMS)' if not tr.cfg.K else 'no labelled test set (%s data)' % source))
+            plan.pop('ACCURACY_EVERY')
+    eval_ms = 0.0            # wall time of the evaluation passes (kept out of `time`)
     for it in range(S['ITERS']):
         if (it == 2 and isinstance(batches, DevicePrefetcher) and S.get('RING_FEED', True) and tr.graph_enabled
                 and isinstance(tr.feed, dict) and 'real_x_int' in tr.feed and tr.world == 1):
@@ -195,9 +260,13 @@ def train(S, cfg, model=None, out_dir=None):
                 ev = torch.cuda.Event(enable_timing=True)
                 ev.record(torch.cuda.current_stream(device))
                 ev.synchronize()
-                lib.plot.plot('time', ev0.elapsed_time(ev) * 1e-3 / (it + 1))
+                lib.plot.plot('time', (ev0.elapsed_time(ev) - eval_ms) * 1e-3 / (it + 1))
             else:
-                lib.plot.plot('time', (time.time() - t0) / (it + 1))
+                lib.plot.plot('time', (time.time() - t0 - eval_ms * 1e-3) / (it + 1))
+            lib.plot.flush(out_dir, os.path.join(out_dir, 'logfile.txt') if out_dir else None)
+        due = eval_due(plan, it) if evaluator is not None else ()
+        if due:
+            eval_ms += _evaluate(evaluator, due, ev_dev, ev_test, it, out_dir, device)
             lib.plot.flush(out_dir, os.path.join(out_dir, 'logfile.txt') if out_dir else None)
         lib.plot.tick()
         if out_dir and S.get('SAVE_EVERY') and (it + 1) % S['SAVE_EVERY'] == 0:
@@ -214,3 +283,20 @@ def train(S, cfg, model=None, out_dir=None):
     tr.flush()
     torch.cuda.synchronize()
     return tr
+
+
+def _evaluate(ev, due, dev, test, it, out_dir, device):
+    """the passes due after iteration `it`, logged through lib.plot under the reference's names -> milliseconds they took"""
+    if device.type == 'cuda':
+        torch.cuda.synchronize(device)          # (the training work queued so far is not the passes' time)
+    t0 = time.time()
+    if 'DEV_EVERY' in due:
+        for k, v in ev.dev_costs(dev).items():
+            lib.plot.plot(k, v)
+    if 'ACCURACY_EVERY' in due:
+        lib.plot.plot('testing accuracy', ev.cluster_accuracy(test))
+    if 'SAMPLE_EVERY' in due and out_dir:
+        ev.save_images(out_dir, it)
+    if device.type == 'cuda':
+        torch.cuda.synchronize(device)
+    return (time.time() - t0) * 1e3

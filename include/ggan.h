@@ -36,8 +36,9 @@ enum { GGAN_ACT_NONE = 0, GGAN_ACT_LRELU = 1, GGAN_ACT_RELU = 2, GGAN_ACT_TANH =
 
 /* The ABI's version: changes whenever a struct layout or an entry point's meaning changes (500: ggan_conv_geom carries the launch plan,
  * ggan_prof_rec the grid; 600: a profiler record is one problem SHAPE -- (kernel, grid, flop per launch) --, ggan_noise_fill_steps is
- * gone).  A binding compares it with the header it was written against before the first call. */
-#define GGAN_ABI_VERSION 600
+ * gone; 700: ggan_gmm_posterior_assign / ggan_cluster_accuracy, the test-set pass).  A binding compares it with the header it was
+ * written against before the first call. */
+#define GGAN_ABI_VERSION 700
 int ggan_version(void);
 const char* ggan_last_error(void);
 /* ---- convolution geometry ------------------------------------------------------------------
@@ -419,6 +420,21 @@ int ggan_gmm_latent_fwd(const float* z, const float* mu, const float* gumbel_u, 
                         float log_pi, float temp, ggan_stream_t stream);
 int ggan_gmm_latent_bwd(const float* z, const float* mu, const float* k, const float* g_logits, const float* g_k, float* dz,
                         float* dmu, int B, int K, int D, float temp, ggan_stream_t stream);
+/* The test-set pass of the gmgan scripts (gmgan_inference_mnist.py:338 q_k_probs = tf.nn.softmax(q_k_logits), :511-529 the clustering
+ * accuracy), one launch per minibatch of B rows that are rows row0 .. row0+B-1 of the test set:
+ *   logits[b,j] = -.5*||z_b - mu_j||^2 + log_pi  (summed as ggan_gmm_latent_fwd sums them: the same bits), p = softmax(logits) with no
+ *   Gumbel noise and no temperature; probs[b,:] = p (probs: [B,K] of THIS launch, may be NULL); assign[row0+b] = argmax_j p (first index
+ *   on a tie, np.argmax(prob_c, axis=1)); colbest[j] = max over every row seen of (float bits of p[b,j]) << 32 | (0xFFFFFFFF - row):
+ *   the running column argmax, lowest row on a tie (np.argmax(prob_c, axis=0)).  The caller zeroes colbest at the start of a pass.
+ *   K <= GGAN_POSTERIOR_MAX_K, any B.
+ * ggan_cluster_accuracy then propagates labels and counts: label_of[j] = labels[0xFFFFFFFF - (colbest[j] & 0xFFFFFFFF)],
+ *   correct[0] = #{b < N : label_of[assign[b]] == labels[b]} (:518-528; a component no row is assigned to keeps its label and never
+ *   matches; a column whose probabilities all underflowed to 0 decodes to row 0, as np.argmax does). */
+#define GGAN_POSTERIOR_MAX_K 8192
+int ggan_gmm_posterior_assign(const float* z, const float* mu, float log_pi, int B, int K, int D, int row0, float* probs,
+                              int32_t* assign, uint64_t* colbest, ggan_stream_t stream);
+int ggan_cluster_accuracy(const int32_t* assign, const int32_t* labels, const uint64_t* colbest, int N, int K, int32_t* correct,
+                          ggan_stream_t stream);
 
 /* reconstruction distances of tflib/utils/distance.py:3-17 (`distance(x, y, 'l1'|'l2')` = reduce_mean(|x-y|^p)), used by the
  * alice / local_epce / vegan objectives as rec_penalty: out[0] (+)= weight * mean(|x-y|^p), p = 1 | 2; the backward writes
