@@ -14,8 +14,9 @@ HEAD_BCE_MAX_ROWS = 2048             # include/ggan.h: GGAN_HEAD_BCE_MAX_ROWS
 BCE_HEADS = 2                        # include/ggan.h: GGAN_BCE_HEADS
 PACK_ARRIVE_INTS = 33 * 1024          # include/ggan.h: GGAN_PACK_ARRIVE_INTS (arrival counters of ggan_pack_adam)
 POSTERIOR_MAX_K = 8192               # include/ggan.h: GGAN_POSTERIOR_MAX_K
+MODE_K = {'CONCRETE': 0, 'STRAIGHT_THROUGHT_CONCRETE': 1, 'STRAIGHT_THROUGHT': 2}   # include/ggan.h: GGAN_MODE_K_*
 BCE_MAX = 16
-ABI_VERSION = 700                    # include/ggan.h: GGAN_ABI_VERSION (struct layouts and entry points this module binds)
+ABI_VERSION = 800                    # include/ggan.h: GGAN_ABI_VERSION (struct layouts and entry points this module binds)
 
 
 class ConvGeom(C.Structure):
@@ -73,6 +74,8 @@ SIGNATURES = {
     'ggan_noise_fill': (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _P]),
     'ggan_gmm_latent_fwd': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _P]),
     'ggan_gmm_latent_bwd': (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P]),
+    'ggan_gmm_latent_st_fwd': (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _I, _P]),
+    'ggan_gmm_latent_st_bwd': (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _I, _P]),
     'ggan_gmm_posterior_assign': (_I, [_P, _P, _F, _I, _I, _I, _I, _P, _P, _P, _P]),
     'ggan_cluster_accuracy': (_I, [_P, _P, _P, _I, _I, _P, _P]),
     'ggan_gemm_split': (_I, [_I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _I, _P, _I, _F, _P, _Z, _P]),

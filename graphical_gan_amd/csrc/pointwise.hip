@@ -1026,6 +1026,141 @@ __global__ __launch_bounds__(256) void gmm_latent_bwd_k(const float* __restrict_
 }
 
 
+// ---- the straight-through MODE_K values of the same HyperExtractor (gmgan_inference_cifar10.py:164-171, include/ggan.h GGAN_MODE_K_*):
+//        STRAIGHT_THROUGHT_CONCRETE  s = the softmax above, h = one_hot(argmax s), k = (h - s) + s, s kept in `soft` for the backward
+//        STRAIGHT_THROUGHT           h = one_hot(argmax logits), k = (h - logits) + logits              (no noise, no temperature)
+//      The same launch shape as gmm_latent_fwd_k plus a block argmax (first index on a tie).  k is TF's float32
+//      stop_gradient(h - v) + v, a subtraction then an addition (no fast-math in this build: the order holds): exactly 0 where h = 0,
+//      fl(fl(1 - v) + v) at the argmax, which may miss 1 by an ulp of v (v = logits ~ -D under ST: ~1e-5).  (The CONCRETE kernels above
+//      stay as they are: folding them into these templates compiled them to reordered instructions.) ----
+enum { kModeKConcrete = 0, kModeKStc = 1, kModeKSt = 2 };            // include/ggan.h GGAN_MODE_K_*
+
+// (value, index) argmax over the workgroup, the larger value or on a tie the smaller index (tf.argmax / np.argmax); best / arg:
+// this thread's candidate, found over ascending indices with `>`.  Every thread returns the result.
+__device__ __forceinline__ int block_argmax_first(float best, int arg, float* bv /* 4 */, int* bi /* 4 */) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(best, o, 64);
+        const int oi = __shfl_xor(arg, o, 64);
+        if (ov > best || (ov == best && oi < arg)) { best = ov; arg = oi; }
+    }
+    if (lane == 0) { bv[wave] = best; bi[wave] = arg; }
+    __syncthreads();
+    best = bv[0];
+    arg = bi[0];
+    for (int w = 1; w < 4; ++w)
+        if (bv[w] > best || (bv[w] == best && bi[w] < arg)) { best = bv[w]; arg = bi[w]; }
+    return arg;
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void gmm_latent_st_fwd_k(const float* __restrict__ z, const float* __restrict__ mu,
+                                                           const float* __restrict__ u, float* __restrict__ logits, float* __restrict__ k,
+                                                           float* __restrict__ soft, int K, int D, float log_pi, float inv_temp) {
+    __shared__ float sv[kGmmMaxK];
+    __shared__ float red[32];
+    __shared__ float bv[4];
+    __shared__ int bi[4];
+    const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float* zb = z + (size_t)b * D;
+    for (int j = wave; j < K; j += 4) {
+        const float* mj = mu + (size_t)j * D;
+        float s = 0.f;
+        for (int d = lane; d < D; d += 64) {
+            const float t = zb[d] - mj[d];
+            s = fmaf(t, t, s);
+        }
+        s = wave_sum(s);
+        if (lane == 0) {
+            const float lg = -0.5f * s + log_pi;
+            if (logits) logits[(size_t)b * K + j] = lg;
+            if constexpr (MODE == kModeKSt) {
+                sv[j] = lg;
+            } else {
+                const float g = -logf(-logf(u[(size_t)b * K + j] + 1e-20f) + 1e-20f);
+                sv[j] = (lg + g) * inv_temp;
+            }
+        }
+    }
+    __syncthreads();
+    if constexpr (MODE == kModeKStc) {
+        float m = -INFINITY;
+        for (int j = threadIdx.x; j < K; j += 256) m = fmaxf(m, sv[j]);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+        if (lane == 0) red[wave] = m;
+        __syncthreads();
+        m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+        float e = 0.f;
+        for (int j = threadIdx.x; j < K; j += 256) {
+            const float t = expf(sv[j] - m);
+            sv[j] = t;
+            e += t;
+        }
+        const float inv = 1.f / block_sum(e, red + 8);
+        for (int j = threadIdx.x; j < K; j += 256) {          // (each thread rewrites only the j it reads below: no barrier)
+            const float p = sv[j] * inv;                       // (the bits gmm_latent_fwd_k writes as k)
+            soft[(size_t)b * K + j] = p;
+            sv[j] = p;
+        }
+    }
+    // argmax over sv (the float32 softmax output under STC, the logits under ST): ascending j per thread, `>` keeps the first
+    float best = -INFINITY;
+    int arg = 0x7FFFFFFF;
+    for (int j = threadIdx.x; j < K; j += 256)
+        if (sv[j] > best) { best = sv[j]; arg = j; }
+    const int hot = block_argmax_first(best, arg, bv, bi);
+    for (int j = threadIdx.x; j < K; j += 256) {
+        const float v = sv[j], h = j == hot ? 1.f : 0.f;
+        k[(size_t)b * K + j] = (h - v) + v;
+    }
+}
+
+// Backward of STRAIGHT_THROUGHT: k = stop_gradient(h - logits) + logits hands dk to the logits unchanged,
+// dlog[b, j] = gl[b, j] + gk[b, j]; then dz / dmu as in gmm_latent_bwd_k (blocks [0, B) rows, [B, B + K) components, dmu summed
+// over the batch in row order: deterministic).  STRAIGHT_THROUGHT_CONCRETE needs no kernel of its own: it is gmm_latent_bwd_k on
+// the saved soft s.
+__global__ __launch_bounds__(256) void gmm_latent_st_bwd_k(const float* __restrict__ z, const float* __restrict__ mu,
+                                                           const float* __restrict__ gl, const float* __restrict__ gk,
+                                                           float* __restrict__ dz, float* __restrict__ dmu, int B, int K, int D) {
+    __shared__ float sv[kGmmMaxK];
+    if ((int)blockIdx.x < B) {
+        const int b = blockIdx.x;
+        for (int j = threadIdx.x; j < K; j += 256) {
+            float v = gl ? gl[(size_t)b * K + j] : 0.f;
+            if (gk) v += gk[(size_t)b * K + j];
+            sv[j] = v;
+        }
+        __syncthreads();
+        if (dz) {
+            for (int d = threadIdx.x; d < D; d += 256) {
+                const float zv = z[(size_t)b * D + d];
+                float acc = 0.f;
+                for (int j = 0; j < K; ++j) acc = fmaf(sv[j], zv - mu[(size_t)j * D + d], acc);
+                dz[(size_t)b * D + d] = -acc;
+            }
+        }
+        return;
+    }
+    if (!dmu) return;
+    const int j = blockIdx.x - B;
+    float* col = sv;                       // B <= kGmmMaxK values
+    for (int b = threadIdx.x; b < B; b += 256) {
+        float v = gl ? gl[(size_t)b * K + j] : 0.f;
+        if (gk) v += gk[(size_t)b * K + j];
+        col[b] = v;
+    }
+    __syncthreads();
+    for (int d = threadIdx.x; d < D; d += 256) {
+        const float mv = mu[(size_t)j * D + d];
+        float acc = 0.f;
+        for (int b = 0; b < B; ++b) acc = fmaf(col[b], z[(size_t)b * D + d] - mv, acc);
+        dmu[(size_t)j * D + d] = acc;
+    }
+}
+
+
 // ---- the test-set pass of the gmgan scripts (gmgan_inference_mnist.py:338,511-529): q_k_probs = softmax(q_k_logits) -- no Gumbel
 //      noise, no temperature --, the row argmax (the sample's cluster) and the running column argmax over the whole test set (the
 //      sample that labels each cluster).  A workgroup per row; the logits are summed exactly as gmm_latent_fwd_k sums them (same
@@ -1689,6 +1824,33 @@ int ggan_gmm_latent_bwd(const float* z, const float* mu, const float* k, const f
     GGAN_CHECK_ARG(B > 0 && B <= kGmmMaxK && K > 0 && K <= kGmmMaxK && D > 0 && temp > 0.f, "bad shape");
     GGAN_LAUNCH("gmm_latent_bwd", 4.0 * B * K * D, 0, gmm_latent_bwd_k, dim3(B + (dmu ? K : 0)), dim3(256), 0, (hipStream_t)stream, z, mu, k,
                 g_logits, g_k, dz, dmu, B, K, D, 1.f / temp);
+    return 0;
+}
+
+int ggan_gmm_latent_st_fwd(const float* z, const float* mu, const float* gumbel_u, float* logits, float* k, float* soft, int B, int K,
+                           int D, float log_pi, float temp, int mode, ggan_stream_t stream) {
+    GGAN_CHECK_ARG(mode == GGAN_MODE_K_STC || mode == GGAN_MODE_K_ST, "mode is not a straight-through MODE_K");
+    GGAN_CHECK_ARG(z && mu && k && (mode == GGAN_MODE_K_ST || (gumbel_u && soft)), "null pointer");
+    GGAN_CHECK_ARG(B > 0 && K > 0 && K <= kGmmMaxK && D > 0 && (mode == GGAN_MODE_K_ST || temp > 0.f), "bad shape");
+    if (mode == GGAN_MODE_K_STC) {
+        GGAN_LAUNCH("gmm_latent_stc_fwd", 3.0 * B * K * D, 0, gmm_latent_st_fwd_k<kModeKStc>, dim3(B), dim3(256), 0, (hipStream_t)stream, z,
+                    mu, gumbel_u, logits, k, soft, K, D, log_pi, 1.f / temp);
+    } else {
+        GGAN_LAUNCH("gmm_latent_st_fwd", 3.0 * B * K * D, 0, gmm_latent_st_fwd_k<kModeKSt>, dim3(B), dim3(256), 0, (hipStream_t)stream, z,
+                    mu, nullptr, logits, k, nullptr, K, D, log_pi, 1.f);
+    }
+    return 0;
+}
+
+int ggan_gmm_latent_st_bwd(const float* z, const float* mu, const float* soft, const float* g_logits, const float* g_k, float* dz,
+                           float* dmu, int B, int K, int D, float temp, int mode, ggan_stream_t stream) {
+    GGAN_CHECK_ARG(mode == GGAN_MODE_K_STC || mode == GGAN_MODE_K_ST, "mode is not a straight-through MODE_K");
+    GGAN_CHECK_ARG(z && mu && (mode == GGAN_MODE_K_ST || soft) && (g_logits || g_k) && (dz || dmu), "null pointer");
+    GGAN_CHECK_ARG(B > 0 && B <= kGmmMaxK && K > 0 && K <= kGmmMaxK && D > 0 && (mode == GGAN_MODE_K_ST || temp > 0.f), "bad shape");
+    if (mode == GGAN_MODE_K_STC)          // the CONCRETE backward on the soft assignment the forward kept
+        return ggan_gmm_latent_bwd(z, mu, soft, g_logits, g_k, dz, dmu, B, K, D, temp, stream);
+    GGAN_LAUNCH("gmm_latent_st_bwd", 2.0 * B * K * D, 0, gmm_latent_st_bwd_k, dim3(B + (dmu ? K : 0)), dim3(256), 0, (hipStream_t)stream, z,
+                mu, g_logits, g_k, dz, dmu, B, K, D);
     return 0;
 }
 

@@ -3,6 +3,7 @@ import ctypes as C
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
+from .. import _lib
 from .._lib import ACT_NONE, POSTERIOR_MAX_K, check  # noqa: F401
 from ._core import _L, _p, _stream, _dev, _c, _DATA_ONLY, _is_param, _skip_undefined, _new_out, _adjacent  # noqa: F401
 from .linear import Gemm  # noqa: F401
@@ -195,6 +196,55 @@ class GmmLatent(Function):
         gk = _c(g_k) if g_k is not None else None
         check(_L().ggan_gmm_latent_bwd(_p(z), _p(mu), _p(k), _p(gl), _p(gk), _p(dz), _p(dmu), B, K, D, ctx.temp, _stream()),
               'ggan_gmm_latent_bwd')
+        return (dz, dmu) + (None,) * (n_in - 2)
+
+
+class GmmLatentST(Function):
+    """HyperExtractor under the straight-through MODE_K values (ggan_gmm_latent_st_*): mode = 'STRAIGHT_THROUGHT_CONCRETE' (the
+    Gumbel-softmax s, its hard one-hot h in the forward value (h - s) + s, the gradient through s) or 'STRAIGHT_THROUGHT' (h = one-hot of
+    the logits' argmax, value (h - logits) + logits, the gradient to the logits unchanged; gumbel_u None, temp unused).  Returns (logits, k)."""
+
+    @staticmethod
+    def forward(ctx, z, mu, gumbel_u, log_pi, temp, mode, slot=None):
+        m = _lib.MODE_K[mode]
+        assert m in (1, 2), mode
+        z, mu = _c(z), _c(mu)
+        B, D = z.shape
+        K = mu.shape[0]
+        assert tuple(mu.shape) == (K, D)
+        st = m == 2
+        if st:
+            assert gumbel_u is None, 'STRAIGHT_THROUGHT draws no Gumbel noise'
+            soft = None
+        else:
+            gumbel_u = _c(gumbel_u)
+            assert tuple(gumbel_u.shape) == (B, K)
+            soft = torch.empty((B, K), dtype=torch.float32, device=z.device)      # s: what the backward differentiates
+        logits = torch.empty((B, K), dtype=torch.float32, device=z.device)
+        k = _new_out(slot, (B, K), z.device)
+        check(_L().ggan_gmm_latent_st_fwd(_p(z), _p(mu), _p(gumbel_u), _p(logits), _p(k), _p(soft), B, K, D, float(log_pi),
+                                          float(temp), m, _stream()), 'ggan_gmm_latent_st_fwd')
+        ctx.temp, ctx.mode = float(temp), m
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(z, mu, *([] if st else [soft]))
+        return logits, k
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_logits, g_k):
+        z, mu = ctx.saved_tensors[:2]
+        soft = ctx.saved_tensors[2] if ctx.mode == 1 else None
+        n_in = len(ctx.needs_input_grad)
+        if (g_logits is None and g_k is None) or not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
+            return (None,) * n_in
+        B, D = z.shape
+        K = mu.shape[0]
+        dz = torch.empty_like(z) if ctx.needs_input_grad[0] else None
+        dmu = torch.empty_like(mu) if ctx.needs_input_grad[1] else None
+        gl = _c(g_logits) if g_logits is not None else None
+        gk = _c(g_k) if g_k is not None else None
+        check(_L().ggan_gmm_latent_st_bwd(_p(z), _p(mu), _p(soft), _p(gl), _p(gk), _p(dz), _p(dmu), B, K, D, ctx.temp, ctx.mode,
+                                          _stream()), 'ggan_gmm_latent_st_bwd')
         return (dz, dmu) + (None,) * (n_in - 2)
 
 

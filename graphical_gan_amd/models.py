@@ -26,8 +26,11 @@ GP_TARGET_WGS = 128      # the same for a wali-gp critic step, whose penalty pas
 
 class Config(object):
     def __init__(self, dataset='cifar10', batch_size=64, n_coms=0, mode=None, dim=None, dim_latent=128, bn=None,
-                 temp=0.1, fuse=True, lr=None, batch_critic=True):
+                 temp=0.1, fuse=True, lr=None, batch_critic=True, mode_k='CONCRETE'):
         self.dataset, self.B, self.K, self.dim_latent, self.temp, self.fuse = dataset, batch_size, n_coms, dim_latent, temp, fuse
+        # MODE_K of the mixture scripts (gmgan_inference_cifar10.py:81-86,160-171): how the gradient passes the assignment q_k
+        assert mode_k in ('CONCRETE', 'STRAIGHT_THROUGHT_CONCRETE', 'STRAIGHT_THROUGHT'), mode_k
+        self.mode_k = mode_k
         if dataset == 'cifar10':
             self.C, self.S, self.dim, self.nl, self.bn, self.out_act = 3, 32, 64, 3, True, 'tanh'
         elif dataset == 'svhn':          # g(m)gan_inference_svhn.py: the CIFAR nets with BN_FLAG = False (:69-72)
@@ -146,7 +149,8 @@ class GraphicalGAN(object):
             # assignment pair [one-hot prior draw ; q_k] of the batched critic (same idea as z_pair)
             feed['k_pair'] = torch.zeros(2 * B, c.K, device=device)
             feed['k_onehot'] = feed['k_pair'][:B]
-            feed['gumbel_u'] = torch.zeros(B, c.K, device=device)
+            if c.mode_k != 'STRAIGHT_THROUGHT':      # (that mode draws no Gumbel noise: the later draws keep their place in the stream)
+                feed['gumbel_u'] = torch.zeros(B, c.K, device=device)
         if c.mode in ('wali-gp', 'vegan-wgan-gp'):
             feed['alpha'] = torch.zeros(B, 1, device=device)
         if c.latent_critic:          # the Gaussian noise layers of the latent critic: one set of draws per critic call
@@ -169,7 +173,9 @@ class GraphicalGAN(object):
             f['rng_state'] = F.noise_state(f['p_z_noise'].device)
         specs = [(f['p_z_noise'], F.NOISE_NORMAL, 0., 1.)]
         if c.K:
-            specs += [(f['k_onehot'], F.NOISE_ONEHOT, 0., 0.), (f['gumbel_u'], F.NOISE_UNIFORM, 0., 1.)]
+            specs.append((f['k_onehot'], F.NOISE_ONEHOT, 0., 0.))
+            if 'gumbel_u' in f:
+                specs.append((f['gumbel_u'], F.NOISE_UNIFORM, 0., 1.))
         if 'alpha' in f:
             specs.append((f['alpha'], F.NOISE_UNIFORM, 0., 1.))
         specs += [(f[k], F.NOISE_NORMAL, 0., 1.) for k in sorted(f) if k.startswith('dn_')]
@@ -386,10 +392,14 @@ class GraphicalGAN(object):
         return F.Axpby.apply(F.Gemm.apply(hyper_k, mu, None, False, False, F.ACT_NONE, 0.0), hyper_noise, 1.0, 1.0, 0.0, out_slot)
 
     def HyperExtractor(self, latent_z, gumbel_u, out_slot=None):
-        """gmgan_inference_cifar10.py:156-173 (MODE_K='CONCRETE'): component logits and the Gumbel-softmax assignment, one
-        launch per direction (ggan_gmm_latent_*; the TF graph spends a dozen [B,K] / [B,K,D] pointwise ops on it)."""
+        """gmgan_inference_cifar10.py:156-173: component logits and the assignment of Config.mode_k -- the Gumbel-softmax relaxation
+        (CONCRETE) or its straight-through variants --, one launch per direction (ggan_gmm_latent_* / ggan_gmm_latent_st_*; the TF graph
+        spends a dozen [B,K] / [B,K,D] pointwise ops on it).  gumbel_u: None under STRAIGHT_THROUGHT."""
         c = self.cfg
-        return F.GmmLatent.apply(latent_z, self._mu(1), gumbel_u, float(np.log(np.float32(1.0) / np.float32(c.K))), c.temp, out_slot)
+        log_pi = float(np.log(np.float32(1.0) / np.float32(c.K)))
+        if c.mode_k == 'CONCRETE':
+            return F.GmmLatent.apply(latent_z, self._mu(1), gumbel_u, log_pi, c.temp, out_slot)
+        return F.GmmLatentST.apply(latent_z, self._mu(1), gumbel_u, log_pi, c.temp, c.mode_k, out_slot)
 
     @staticmethod
     def _var_lists():
@@ -499,7 +509,7 @@ class GraphicalGAN(object):
                 out = dict(real_x=real_x, q_z=q_z, p_z=p_z, q_z_src=q_src)
                 if c.K:
                     ks = F.RowSlot(feed['k_pair'], B, 2 * B) if (c.batch_critic and 'k_pair' in feed) else None
-                    _, out['q_k'] = self.HyperExtractor(q_z_h, feed['gumbel_u'], ks)
+                    _, out['q_k'] = self.HyperExtractor(q_z_h, feed.get('gumbel_u'), ks)
                 ev_end = torch.cuda.Event()
                 ev_end.record(self._side)
             self._pending_join = [cur, ev_x, ev_end]
@@ -523,7 +533,7 @@ class GraphicalGAN(object):
         out = dict(real_x=real_x, q_z=q_z, p_z=p_z, q_z_src=q_src)
         if c.K:
             ks = F.RowSlot(feed['k_pair'], B, 2 * B) if (c.batch_critic and 'k_pair' in feed) else None
-            _, q_k = self.HyperExtractor(q_z_h, feed['gumbel_u'], ks)
+            _, q_k = self.HyperExtractor(q_z_h, feed.get('gumbel_u'), ks)
             out['q_k'] = q_k
         if fork:
             cur.wait_stream(self._side)

@@ -205,14 +205,20 @@ def config(S):
                         dim_l=S['DIM_LATENT_L'], n_c=S['N_C'], pos_mode=S['POS_MODE'], op_dyn_mode=S['OP_DYN_MODE'], lr=S['LR'],
                         channels=S['OUTPUT_SHAPE'][0], dataset=S['DATASET'], mode=S['MODE'], lamb=S['LAMBDA'], ali_mode=S['ALI_MODE'])
     from .models import Config
-    if S.get('MODE_K', 'CONCRETE') != 'CONCRETE':
-        raise NotImplementedError('MODE_K = %r: only the CONCRETE relaxation is built (DESIGN.md 0)' % S['MODE_K'])
+    mode_k = S.get('MODE_K', 'CONCRETE')
+    if mode_k == 'REINFORCE':
+        raise NotImplementedError('MODE_K = %r: the score-function estimator is not built (DESIGN.md 0)' % mode_k)
+    if mode_k not in ('CONCRETE', 'STRAIGHT_THROUGHT_CONCRETE', 'STRAIGHT_THROUGHT'):
+        raise ValueError('MODE_K = %r is none of the reference\'s values' % mode_k)
+    if mode_k != 'CONCRETE' and S['DATASET'] == 'face':
+        # (gmgan_inference_face.py:52,100-104 hard-codes the CONCRETE branch: the script has no MODE_K switch)
+        raise NotImplementedError('MODE_K = %r: gmgan_inference_face builds only the CONCRETE relaxation' % mode_k)
     if S['MODE'] == 'vae':
         raise NotImplementedError('MODE vae: the reference Generator returns no decoder statistics (DESIGN.md 8)')
     assert S.get('DISTANCE_X', 'l2') == 'l2' and S.get('LAMBDA', 1.) == 1. and S.get('BETA1', .5) == .5 and S.get('Z_SAMPLES', 100) == 100, S
     assert S.get('DIM_G', S.get('DIM')) == S.get('DIM_D', S.get('DIM')), 'one model width'
     return Config(S['DATASET'], batch_size=S['BATCH_SIZE'], n_coms=S.get('N_COMS', 0), mode=S['MODE'], dim=S.get('DIM', S.get('DIM_G')),
-                  dim_latent=S['DIM_LATENT'], bn=S['BN_FLAG'], temp=S.get('TEMP', 0.1), lr=S['LR'])
+                  dim_latent=S['DIM_LATENT'], bn=S['BN_FLAG'], temp=S.get('TEMP', 0.1), lr=S['LR'], mode_k=mode_k)
 
 
 def train(S, cfg, model=None, out_dir=None):

@@ -36,9 +36,10 @@ enum { GGAN_ACT_NONE = 0, GGAN_ACT_LRELU = 1, GGAN_ACT_RELU = 2, GGAN_ACT_TANH =
 
 /* The ABI's version: changes whenever a struct layout or an entry point's meaning changes (500: ggan_conv_geom carries the launch plan,
  * ggan_prof_rec the grid; 600: a profiler record is one problem SHAPE -- (kernel, grid, flop per launch) --, ggan_noise_fill_steps is
- * gone; 700: ggan_gmm_posterior_assign / ggan_cluster_accuracy, the test-set pass).  A binding compares it with the header it was
+ * gone; 700: ggan_gmm_posterior_assign / ggan_cluster_accuracy, the test-set pass; 800: ggan_gmm_latent_st_fwd / _bwd, the
+ * straight-through MODE_K values).  A binding compares it with the header it was
  * written against before the first call. */
-#define GGAN_ABI_VERSION 700
+#define GGAN_ABI_VERSION 800
 int ggan_version(void);
 const char* ggan_last_error(void);
 /* ---- convolution geometry ------------------------------------------------------------------
@@ -420,6 +421,20 @@ int ggan_gmm_latent_fwd(const float* z, const float* mu, const float* gumbel_u, 
                         float log_pi, float temp, ggan_stream_t stream);
 int ggan_gmm_latent_bwd(const float* z, const float* mu, const float* k, const float* g_logits, const float* g_k, float* dz,
                         float* dmu, int B, int K, int D, float temp, ggan_stream_t stream);
+/* The straight-through MODE_K values of HyperExtractor (gmgan_inference_cifar10.py:164-171, the same lines in the mnist / svhn
+ * scripts), replacing its softmax / argmax / one_hot / stop_gradient ops with one launch per direction; logits as above.
+ *   GGAN_MODE_K_STC (MODE_K = 'STRAIGHT_THROUGHT_CONCRETE', :164-167): soft[b,:] = s = the CONCRETE softmax of (logits + gumbel(u)) / temp,
+ *     h = one_hot(argmax_j s[b,j]), k = (h - s) + s.  The argmax runs over the float32 s, the first index on a tie.
+ *   GGAN_MODE_K_ST (MODE_K = 'STRAIGHT_THROUGHT', :169-171): h = one_hot(argmax_j logits[b,j]), k = (h - logits) + logits; gumbel_u,
+ *     soft and temp are not read (the script draws no noise and defines no TEMP in this mode).
+ *   k is TF's float32 stop_gradient(h - v) + v, a subtraction then an addition: 0 where h = 0, fl(fl(1 - v) + v) at the argmax.
+ * Backward (mode as in the forward): STC is ggan_gmm_latent_bwd on soft (the gradient flows through the softmax, not through h);
+ * ST passes g_k to the logits unchanged, dlogits = g_logits + g_k (soft, temp not read).  NULL rules and K, B <= 256 as above. */
+enum { GGAN_MODE_K_CONCRETE = 0, GGAN_MODE_K_STC = 1, GGAN_MODE_K_ST = 2 };
+int ggan_gmm_latent_st_fwd(const float* z, const float* mu, const float* gumbel_u, float* logits, float* k, float* soft, int B, int K,
+                           int D, float log_pi, float temp, int mode, ggan_stream_t stream);
+int ggan_gmm_latent_st_bwd(const float* z, const float* mu, const float* soft, const float* g_logits, const float* g_k, float* dz,
+                           float* dmu, int B, int K, int D, float temp, int mode, ggan_stream_t stream);
 /* The test-set pass of the gmgan scripts (gmgan_inference_mnist.py:338 q_k_probs = tf.nn.softmax(q_k_logits), :511-529 the clustering
  * accuracy), one launch per minibatch of B rows that are rows row0 .. row0+B-1 of the test set:
  *   logits[b,j] = -.5*||z_b - mu_j||^2 + log_pi  (summed as ggan_gmm_latent_fwd sums them: the same bits), p = softmax(logits) with no

@@ -8,7 +8,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from graphical_gan_amd import run
 
 MODE = 'local_ep'  # local_ep, local_epce
-SETTINGS = run.reference_block(__file__, MODE=MODE)
+MODE_K = 'CONCRETE'  # CONCRETE, STRAIGHT_THROUGHT_CONCRETE, STRAIGHT_THROUGHT (REINFORCE is not built)
+SETTINGS = run.reference_block(__file__, MODE=MODE, MODE_K=MODE_K)
 # edit the block here, e.g. SETTINGS['N_COMS'] = 10 -- or pass it to reference_block, which then derives N_VIS etc. from it
 SETTINGS.update(DATA_DIR=os.environ.get('GGAN_DATA_DIR', ''), OUT_DIR=os.environ.get('GGAN_OUT_DIR', ''), SAVE_EVERY=10000, LOG_EVERY=100)
 SETTINGS.update(run.eval_settings(__file__))     # dev costs / samples / reconstructions (/ testing accuracy) at the reference's cadence
