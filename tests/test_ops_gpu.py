@@ -703,7 +703,8 @@ def test_row_slots_make_the_critic_concatenation_free(gpu):
     assert torch.equal(gc, torch.ones_like(c)) and torch.equal(gd, torch.ones_like(d))
 
 
-@pytest.mark.parametrize('shape,act', [((8, 24), 0), ((7, 40), 1), ((4, 6, 4, 4), 2)])
+@pytest.mark.parametrize('shape,act', [((8, 24), 0), ((7, 40), 1), ((4, 6, 4, 4), 2),
+                                       ((50, 128, 7, 7), 1), ((50, 256, 4, 4), 1)])     # (the MNIST critic's BN2 / BN3)
 def test_batchnorm_second_derivative(gpu, shape, act):
     """ggan_bn_bwd_bwd through autograd: L = sum(w * d(sum(g0 * BN(x)))/dx) differentiated w.r.t. x, g0 and scale, against the
     oracle tape (which is closed under differentiation), float64."""
@@ -767,8 +768,14 @@ def test_linear_on_a_pair_of_inputs_equals_linear_on_their_concatenation(gpu, M,
     y2 = F.Gemm2.apply(t1, t2, tw, tb, F.ACT_LRELU, 0.2)
     e1, e2 = torch.autograd.grad(y2, [t1, t2], grad_outputs=_t(g, gpu), create_graph=True)
     assert _rel(e1.detach().cpu().numpy(), da[:, :K1]) < TOL and _rel(e2.detach().cpu().numpy(), da[:, K1:]) < TOL
+    # ... and their second derivative: e = gm w^T with gm = g * act'(pre) (the mask of the kernel's own output), so
+    # d(|e1|^2 + |e2|^2)/dw = 2 e^T gm
     (hw,) = torch.autograd.grad((e1 * e1).sum() + (e2 * e2).sum(), [tw])
-    assert np.isfinite(hw.cpu().numpy()).all() and float(hw.abs().max()) > 0
+    on = y2.detach().cpu().numpy() > 0
+    assert np.count_nonzero(on != (pre > 0)) <= 8
+    gk = g * np.where(on, 1.0, 0.2)
+    hw_ref = 2 * (gk @ w.T).T @ gk
+    assert _rel(hw.cpu().numpy(), hw_ref) <= 1e-4, _rel(hw.cpu().numpy(), hw_ref)
 
 
 @pytest.mark.parametrize('B,K,D', [(64, 30, 128), (5, 7, 16), (128, 100, 128)])
