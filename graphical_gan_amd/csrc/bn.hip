@@ -496,6 +496,303 @@ __global__ __launch_bounds__(kSyncThreads) void bn_bwd_bwd_k(const float* __rest
     if (threadIdx.x == 0) gscale2[c] = invstd * sum_ha;
 }
 
+
+// ---- row-grouped, chip-wide batch norm (ggan_bn_split_*): the state-space critics see [fake; real] in ONE batch, each half with
+//      its own statistics (groups = 2), and their 5-D NDHWC volumes read as [rows, C] run to 65 536 rows x 64 channels -- shapes on
+//      which the one-workgroup-per-channel (NCHW) or per-32-channel (rows) kernels above occupy 2..64 workgroups of a 256-CU chip.
+//      Three launches per direction, no atomics, every sum in a fixed order (bit-identical run to run and under graph replay):
+//        1. slab partials over ~1024 workgroups: forward (count, mean, M2) of a slab of x - x0 (x0: the group's first value, so that
+//           the slab means are O(std) and their merge loses no digits to a large common mean) -- mean first, then the centred
+//           squares, the second read of the slab coming from cache; backward (sum g, sum g*xhat, sum xhat);
+//        2. per (group, channel) the slabs merged in a fixed tree (forward: Chan's pairwise formula, never E[x^2] - E[x]^2);
+//        3. the elementwise pass (normalise + activation epilogue; backward: the data gradient).
+//      Element (n, c, p) of x [N, C, HW] sits at (n*C + c)*HW + p; group g holds n in [g*Ng, (g+1)*Ng), Ng = N / groups.
+constexpr int kSpCols = 64;      // rows layout: channels per workgroup (one 256-B row segment per wave)
+constexpr int kSpLanes = 4;      // rows layout: row lanes per workgroup (256 threads)
+constexpr int kSpThreads = 256;  // NCHW layout: threads per (slab, channel)
+constexpr int kSpMerge = 16;     // merge stage: slab lanes per channel column (64 x 16 threads)
+constexpr int kSpTarget = 1024;  // slab workgroups aimed at per launch (4 per CU)
+
+// BatchNorm's affine output before the activation: the forward's epilogue and the backward's activation mask use this one expression
+__device__ __forceinline__ float sp_affine(float x, float mean, float invstd, float g, float b) { return g * ((x - mean) * invstd) + b; }
+
+// (na, ma, qa) <- (na, ma, qa) (+) (nb, mb, qb): Chan et al.'s pairwise update of (count, mean, M2)
+__device__ __forceinline__ void chan_merge(float& na, float& ma, float& qa, float nb, float mb, float qb) {
+    const float n = na + nb;
+    if (nb == 0.f) return;
+    if (na == 0.f) { na = nb; ma = mb; qa = qb; return; }
+    const float d = mb - ma, f = nb / n;
+    ma = ma + d * f;
+    qa = qa + qb + d * d * na * f;
+    na = n;
+}
+
+struct SpDims {
+    int N, C, HW, G, Ng;   // Ng = N / G
+    int S, slab;           // slabs per group; images (NCHW) or rows (HW == 1) per slab (the last one may be short)
+};
+
+// forward stage 1, rows layout: part[((g*S + s)*3 + {0,1,2})*C + c] = (count, mean, M2) of slab s of group g
+__global__ __launch_bounds__(kSpCols * kSpLanes) void bn_sp_stats_rows_k(const float* __restrict__ x, float* __restrict__ part, SpDims d) {
+    __shared__ float sm[kSpLanes][kSpCols];
+    const int c = blockIdx.x * kSpCols + threadIdx.x, s = blockIdx.y, g = blockIdx.z, ty = threadIdx.y;
+    const bool ok = c < d.C;
+    const int r0 = g * d.Ng + s * d.slab, r1 = min(r0 + d.slab, (g + 1) * d.Ng);
+    const float k0 = ok ? x[(size_t)g * d.Ng * d.C + c] : 0.f;      // the group's shift (its first value): slab means stay O(std)
+    float t = 0.f;
+    if (ok) for (int r = r0 + ty; r < r1; r += kSpLanes) t += x[(size_t)r * d.C + c] - k0;
+    sm[ty][threadIdx.x] = t;
+    __syncthreads();
+    const float cnt = (float)(r1 - r0);
+    const float mean = (sm[0][threadIdx.x] + sm[1][threadIdx.x] + sm[2][threadIdx.x] + sm[3][threadIdx.x]) / cnt;
+    __syncthreads();
+    float q = 0.f;
+    if (ok) for (int r = r0 + ty; r < r1; r += kSpLanes) {
+        const float e = (x[(size_t)r * d.C + c] - k0) - mean;
+        q += e * e;
+    }
+    sm[ty][threadIdx.x] = q;
+    __syncthreads();
+    if (ty == 0 && ok) {
+        float* o = part + (size_t)(g * d.S + s) * 3 * d.C + c;
+        o[0] = cnt;
+        o[d.C] = mean;
+        o[2 * d.C] = sm[0][threadIdx.x] + sm[1][threadIdx.x] + sm[2][threadIdx.x] + sm[3][threadIdx.x];
+    }
+}
+
+// forward stage 1, NCHW layout: one workgroup per (channel, slab, group), the slab's images walked as one flat range
+__global__ __launch_bounds__(kSpThreads) void bn_sp_stats_nchw_k(const float* __restrict__ x, float* __restrict__ part, SpDims d) {
+    __shared__ float sm[32];
+    const int c = blockIdx.x, s = blockIdx.y, g = blockIdx.z;
+    const int n0 = g * d.Ng + s * d.slab, n1 = min(n0 + d.slab, (g + 1) * d.Ng);
+    const int total = (n1 - n0) * d.HW;
+    const float* xc = x + ((size_t)n0 * d.C + c) * d.HW;
+    const size_t img = (size_t)d.C * d.HW;
+    const float k0 = x[((size_t)g * d.Ng * d.C + c) * d.HW];        // the group's shift (its first value): slab means stay O(std)
+    float t = 0.f;
+    for (int i = threadIdx.x; i < total; i += kSpThreads) {
+        const int n = i / d.HW;
+        t += xc[n * img + (i - n * d.HW)] - k0;
+    }
+    const float cnt = (float)total;
+    const float mean = block_sum(t, sm) / cnt;
+    float q = 0.f;
+    for (int i = threadIdx.x; i < total; i += kSpThreads) {
+        const int n = i / d.HW;
+        const float e = (xc[n * img + (i - n * d.HW)] - k0) - mean;
+        q += e * e;
+    }
+    const float m2 = block_sum(q, sm);
+    if (threadIdx.x == 0) {
+        float* o = part + (size_t)(g * d.S + s) * 3 * d.C + c;
+        o[0] = cnt;
+        o[d.C] = mean;
+        o[2 * d.C] = m2;
+    }
+}
+
+// forward stage 2: grid (C / 64, G); lane ty merges slabs ty, ty+16, ... in order, then lane 0 merges the 16 lanes in order
+__global__ __launch_bounds__(kSpCols * kSpMerge) void bn_sp_merge_k(const float* __restrict__ x, const float* __restrict__ part,
+                                                                   float* __restrict__ save_mean, float* __restrict__ save_invstd, SpDims d,
+                                                                   float eps) {
+    __shared__ float sm[3][kSpMerge][kSpCols];
+    const int c = blockIdx.x * kSpCols + threadIdx.x, g = blockIdx.y, ty = threadIdx.y;
+    const bool ok = c < d.C;
+    float n = 0.f, m = 0.f, q = 0.f;
+    if (ok) for (int s = ty; s < d.S; s += kSpMerge) {
+        const float* p = part + (size_t)(g * d.S + s) * 3 * d.C + c;
+        chan_merge(n, m, q, p[0], p[d.C], p[2 * d.C]);
+    }
+    sm[0][ty][threadIdx.x] = n;
+    sm[1][ty][threadIdx.x] = m;
+    sm[2][ty][threadIdx.x] = q;
+    __syncthreads();
+    if (ty != 0 || !ok) return;
+    for (int l = 1; l < kSpMerge; ++l) chan_merge(n, m, q, sm[0][l][threadIdx.x], sm[1][l][threadIdx.x], sm[2][l][threadIdx.x]);
+    save_mean[g * d.C + c] = x[((size_t)g * d.Ng * d.C + c) * d.HW] + m;      // (the partials are of x - the group's first value)
+    save_invstd[g * d.C + c] = 1.f / sqrtf(q / n + eps);
+}
+
+// forward stage 3: y = act(scale * (x - mean_g) * invstd_g + offset), 4 consecutive elements per thread step
+__global__ __launch_bounds__(256) void bn_sp_apply_k(const float* __restrict__ x, const float* __restrict__ scale,
+                                                     const float* __restrict__ offset, const float* __restrict__ save_mean,
+                                                     const float* __restrict__ save_invstd, float* __restrict__ y, SpDims d, int act,
+                                                     float alpha) {
+    // (32-bit index arithmetic: the host refuses tensors of 2^31 elements or more)
+    const uint32_t total = (uint32_t)d.N * d.C * d.HW, grp = (uint32_t)d.Ng * d.C * d.HW, HW = d.HW, C = d.C;
+    const uint32_t stride = gridDim.x * blockDim.x * 4;
+    for (uint32_t e0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4; e0 < total; e0 += stride) {
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) {
+            const uint32_t e = e0 + j;
+            if (e >= total) break;
+            const uint32_t c = (e / HW) % C, gc = (e / grp) * C + c;
+            y[e] = act_apply(sp_affine(x[e], save_mean[gc], save_invstd[gc], scale[c], offset[c]), act, alpha);
+        }
+    }
+}
+
+// dL/d(affine output) of element e: gy with the epilogue's activation differentiated at the recomputed affine output (lrelu / relu:
+// its sign is the sign of the activated output that ggan_bn_bwd_act reads back, so y need not be kept)
+__device__ __forceinline__ float sp_gy(const float* __restrict__ gy, float xv, size_t e, float mean, float invstd, float g, float b,
+                                       int act, float alpha) {
+    const float v = gy[e];
+    return act == GGAN_ACT_NONE ? v : act_grad(v, sp_affine(xv, mean, invstd, g, b), act, alpha);
+}
+
+// backward stage 1, rows layout: part[((g*S + s)*3 + {0,1,2})*C + c] = (sum g, sum g*xhat, sum xhat) over slab s of group g
+__global__ __launch_bounds__(kSpCols * kSpLanes) void bn_sp_bwd_stats_rows_k(const float* __restrict__ x, const float* __restrict__ gy,
+                                                                          const float* __restrict__ scale, const float* __restrict__ offset,
+                                                                          const float* __restrict__ save_mean,
+                                                                          const float* __restrict__ save_invstd, float* __restrict__ part,
+                                                                          SpDims d, int act, float alpha) {
+    __shared__ float sm[3][kSpLanes][kSpCols];
+    const int c = blockIdx.x * kSpCols + threadIdx.x, s = blockIdx.y, g = blockIdx.z, ty = threadIdx.y;
+    const bool ok = c < d.C;
+    const int r0 = g * d.Ng + s * d.slab, r1 = min(r0 + d.slab, (g + 1) * d.Ng);
+    float s1 = 0.f, s2 = 0.f, s3 = 0.f;
+    if (ok) {
+        const float mean = save_mean[g * d.C + c], invstd = save_invstd[g * d.C + c], gs = scale[c], go = offset[c];
+        for (int r = r0 + ty; r < r1; r += kSpLanes) {
+            const size_t e = (size_t)r * d.C + c;
+            const float xv = x[e], xh = (xv - mean) * invstd, gv = sp_gy(gy, xv, e, mean, invstd, gs, go, act, alpha);
+            s1 += gv;
+            s2 += gv * xh;
+            s3 += xh;
+        }
+    }
+    sm[0][ty][threadIdx.x] = s1;
+    sm[1][ty][threadIdx.x] = s2;
+    sm[2][ty][threadIdx.x] = s3;
+    __syncthreads();
+    if (ty == 0 && ok) {
+        float* o = part + (size_t)(g * d.S + s) * 3 * d.C + c;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) o[k * d.C] = sm[k][0][threadIdx.x] + sm[k][1][threadIdx.x] + sm[k][2][threadIdx.x] + sm[k][3][threadIdx.x];
+    }
+}
+
+// backward stage 1, NCHW layout
+__global__ __launch_bounds__(kSpThreads) void bn_sp_bwd_stats_nchw_k(const float* __restrict__ x, const float* __restrict__ gy,
+                                                                    const float* __restrict__ scale, const float* __restrict__ offset,
+                                                                    const float* __restrict__ save_mean, const float* __restrict__ save_invstd,
+                                                                    float* __restrict__ part, SpDims d, int act, float alpha) {
+    __shared__ float sm[32];
+    const int c = blockIdx.x, s = blockIdx.y, g = blockIdx.z;
+    const int n0 = g * d.Ng + s * d.slab, n1 = min(n0 + d.slab, (g + 1) * d.Ng);
+    const int total = (n1 - n0) * d.HW;
+    const size_t base = ((size_t)n0 * d.C + c) * d.HW, img = (size_t)d.C * d.HW;
+    const float mean = save_mean[g * d.C + c], invstd = save_invstd[g * d.C + c], gs = scale[c], go = offset[c];
+    float s1 = 0.f, s2 = 0.f, s3 = 0.f;
+    for (int i = threadIdx.x; i < total; i += kSpThreads) {
+        const int n = i / d.HW;
+        const size_t e = base + n * img + (i - n * d.HW);
+        const float xv = x[e], xh = (xv - mean) * invstd, gv = sp_gy(gy, xv, e, mean, invstd, gs, go, act, alpha);
+        s1 += gv;
+        s2 += gv * xh;
+        s3 += xh;
+    }
+    s1 = block_sum(s1, sm);
+    s2 = block_sum(s2, sm);
+    s3 = block_sum(s3, sm);
+    if (threadIdx.x == 0) {
+        float* o = part + (size_t)(g * d.S + s) * 3 * d.C + c;
+        o[0] = s1;
+        o[d.C] = s2;
+        o[2 * d.C] = s3;
+    }
+}
+
+// backward stage 2: grid (C / 64); the groups [0, sgroups) in order, each one's slabs summed in a fixed tree.  coef[{0,1,2}][g][c] =
+// (k, mean g, mean g*xhat) of the data gradient for g < gx_groups; gscale / goffset (optional) summed over all groups in order;
+// chansum (optional) = sum of gx over the groups [0, gx_groups), k * (sum g - cnt * mean g - mean g*xhat * sum xhat) per group
+__global__ __launch_bounds__(kSpCols * kSpMerge) void bn_sp_bwd_merge_k(const float* __restrict__ part, const float* __restrict__ scale,
+                                                                       const float* __restrict__ save_invstd, float* __restrict__ coef,
+                                                                       float* __restrict__ gscale, float* __restrict__ goffset,
+                                                                       float* __restrict__ chansum, SpDims d, int sgroups, int gx_groups) {
+    __shared__ float sm[3][kSpMerge][kSpCols];
+    const int c = blockIdx.x * kSpCols + threadIdx.x, ty = threadIdx.y;
+    const bool ok = c < d.C;
+    const float cnt = (float)d.Ng * (float)d.HW;
+    float a_go = 0.f, a_gs = 0.f, a_cs = 0.f;
+    for (int g = 0; g < sgroups; ++g) {
+        float s1 = 0.f, s2 = 0.f, s3 = 0.f;
+        if (ok) for (int s = ty; s < d.S; s += kSpMerge) {
+            const float* p = part + (size_t)(g * d.S + s) * 3 * d.C + c;
+            s1 += p[0];
+            s2 += p[d.C];
+            s3 += p[2 * d.C];
+        }
+        __syncthreads();
+        sm[0][ty][threadIdx.x] = s1;
+        sm[1][ty][threadIdx.x] = s2;
+        sm[2][ty][threadIdx.x] = s3;
+        __syncthreads();
+        if (ty == 0 && ok) {
+            s1 = s2 = s3 = 0.f;
+            for (int l = 0; l < kSpMerge; ++l) {
+                s1 += sm[0][l][threadIdx.x];
+                s2 += sm[1][l][threadIdx.x];
+                s3 += sm[2][l][threadIdx.x];
+            }
+            a_go += s1;
+            a_gs += s2;
+            if (g < gx_groups) {
+                const float k = scale[c] * save_invstd[g * d.C + c], mg = s1 / cnt, mgx = s2 / cnt;
+                const size_t gc = (size_t)g * d.C + c, plane = (size_t)d.G * d.C;
+                coef[gc] = k;
+                coef[plane + gc] = mg;
+                coef[2 * plane + gc] = mgx;
+                a_cs += k * (s1 - cnt * mg - mgx * s3);
+            }
+        }
+    }
+    if (ty != 0 || !ok) return;
+    if (gscale) gscale[c] = a_gs;
+    if (goffset) goffset[c] = a_go;
+    if (chansum) chansum[c] = a_cs;
+}
+
+// backward stage 3: gx = k * (g - mean g - xhat * mean g*xhat) over the leading gx_groups groups
+__global__ __launch_bounds__(256) void bn_sp_bwd_apply_k(const float* __restrict__ x, const float* __restrict__ gy,
+                                                         const float* __restrict__ scale, const float* __restrict__ offset,
+                                                         const float* __restrict__ save_mean, const float* __restrict__ save_invstd,
+                                                         const float* __restrict__ coef, float* __restrict__ gx, SpDims d, int gx_groups,
+                                                         int act, float alpha) {
+    const uint32_t grp = (uint32_t)d.Ng * d.C * d.HW, total = grp * (uint32_t)gx_groups, plane = (uint32_t)d.G * d.C;
+    const uint32_t HW = d.HW, C = d.C, stride = gridDim.x * blockDim.x * 4;
+    for (uint32_t e0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4; e0 < total; e0 += stride) {
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) {
+            const uint32_t e = e0 + j;
+            if (e >= total) break;
+            const uint32_t c = (e / HW) % C, gc = (e / grp) * C + c;
+            const float mean = save_mean[gc], invstd = save_invstd[gc], xv = x[e];
+            const float gv = sp_gy(gy, xv, e, mean, invstd, scale[c], offset[c], act, alpha);
+            gx[e] = coef[gc] * (gv - coef[plane + gc] - ((xv - mean) * invstd) * coef[2 * plane + gc]);
+        }
+    }
+}
+
+// slab plan: ~kSpTarget stage-1 workgroups; NCHW slabs are whole images, rows slabs whole rows (at least one per row lane)
+SpDims sp_plan(int N, int C, int HW, int G) {
+    SpDims d{N, C, HW, G, N / G, 1, N / G};
+    const int tiles = HW > 1 ? C : cdiv(C, kSpCols);
+    int want = std::max(1, kSpTarget / std::max(1, tiles * G));
+    if (HW > 1) want = std::min(want, std::max(1, (int)(((size_t)d.Ng * HW) / 2048)));     // >= ~2K elements per NCHW slab
+    else want = std::min(want, cdiv(d.Ng, kSpLanes));
+    want = std::max(1, std::min(want, d.Ng));
+    d.slab = cdiv(d.Ng, want);
+    d.S = cdiv(d.Ng, d.slab);
+    return d;
+}
+
+int sp_apply_grid(size_t elems) {
+    const size_t quads = cdivz(elems, 4);
+    return (int)std::min<size_t>(cdivz(quads, 256), 2048);
+}
+
 }  // namespace
 
 extern "C" {
@@ -602,6 +899,71 @@ int ggan_bn_bwd_bwd(const float* x, const float* gy, const float* y, int y_act, 
     const GyMask mk{y_act != GGAN_ACT_NONE ? y : nullptr, y_act, y_alpha};
     GGAN_LAUNCH("bn_bwd_bwd", 0, 32.0 * N * C * HW, bn_bwd_bwd_k, dim3(C), dim3(kSyncThreads), 0, (hipStream_t)stream, x, gy, mk, h, scale,
                 save_mean, save_invstd, ggy, gx2, gscale2, N, C, HW);
+    return 0;
+}
+
+
+int ggan_bn_split_fwd_train(const float* x, const float* scale, const float* offset, float* y, float* save_mean, float* save_invstd,
+                            int N, int C, int HW, int groups, float eps, int act, float alpha, void* ws, size_t ws_bytes,
+                            ggan_stream_t stream) {
+    GGAN_CHECK_ARG(x && scale && offset && y && save_mean && save_invstd, "null pointer");
+    GGAN_CHECK_ARG(N > 0 && C > 0 && HW > 0 && groups > 0 && N % groups == 0, "bad shape");
+    GGAN_CHECK_ARG((size_t)N * C * HW < ((size_t)1 << 31), "tensor too large");
+    hipStream_t s = (hipStream_t)stream;
+    const SpDims d = sp_plan(N, C, HW, groups);
+    ws = ws_scratch(ws, ws_bytes);
+    GGAN_CHECK_ARG(ws && (size_t)3 * groups * d.S * C * sizeof(float) <= ws_bytes, "workspace too small");
+    float* part = (float*)ws;
+    const double bytes = 4.0 * N * C * HW;
+    if (HW > 1) {
+        GGAN_LAUNCH("bn_split_stats", 0, bytes, bn_sp_stats_nchw_k, dim3(C, d.S, groups), dim3(kSpThreads), 0, s, x, part, d);
+    } else {
+        GGAN_LAUNCH("bn_split_stats", 0, bytes, bn_sp_stats_rows_k, dim3(cdiv(C, kSpCols), d.S, groups), dim3(kSpCols, kSpLanes), 0, s,
+                    x, part, d);
+    }
+    GGAN_LAUNCH("bn_split_merge", 0, 12.0 * groups * d.S * C, bn_sp_merge_k, dim3(cdiv(C, kSpCols), groups), dim3(kSpCols, kSpMerge), 0,
+                s, x, (const float*)part, save_mean, save_invstd, d, eps);
+    GGAN_LAUNCH("bn_split_apply", 0, 2.0 * bytes, bn_sp_apply_k, dim3(sp_apply_grid((size_t)N * C * HW)), dim3(256), 0, s, x, scale,
+                offset, (const float*)save_mean, (const float*)save_invstd, y, d, act, alpha);
+    return 0;
+}
+
+int ggan_bn_split_bwd_act(const float* x, const float* gy, int act, float alpha, const float* scale, const float* offset,
+                          const float* save_mean, const float* save_invstd, float* gx, float* gscale, float* goffset,
+                          float* gx_chansum, int N, int C, int HW, int groups, int gx_groups, void* ws, size_t ws_bytes,
+                          ggan_stream_t stream) {
+    GGAN_CHECK_ARG(x && gy && scale && offset && save_mean && save_invstd, "null pointer");
+    GGAN_CHECK_ARG(act == GGAN_ACT_NONE || act == GGAN_ACT_LRELU || act == GGAN_ACT_RELU, "fused activation must be none / lrelu / relu");
+    GGAN_CHECK_ARG(N > 0 && C > 0 && HW > 0 && groups > 0 && N % groups == 0, "bad shape");
+    GGAN_CHECK_ARG((size_t)N * C * HW < ((size_t)1 << 31), "tensor too large");
+    GGAN_CHECK_ARG(gx_groups >= 0 && gx_groups <= groups && (gx || gx_groups == 0), "gx_groups out of range / gx missing");
+    GGAN_CHECK_ARG(!gx_chansum || HW > 1, "gx_chansum is only produced for NCHW inputs (HW > 1)");
+    // the statistics pass reads every group when a parameter gradient is asked for, else only the groups whose gx is written (the
+    // trailing groups' gy may be unwritten: the consumer's backward ran for the leading rows only)
+    const int sgroups = (gscale || goffset) ? groups : gx_groups;
+    if (sgroups == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    const SpDims d = sp_plan(N, C, HW, groups);
+    ws = ws_scratch(ws, ws_bytes);
+    const size_t part_floats = (size_t)3 * groups * d.S * C;
+    GGAN_CHECK_ARG(ws && (part_floats + (size_t)3 * groups * C) * sizeof(float) <= ws_bytes, "workspace too small");
+    float* part = (float*)ws;
+    float* coef = part + part_floats;
+    const double bytes = 8.0 * N * C * HW / groups * sgroups;
+    if (HW > 1) {
+        GGAN_LAUNCH("bn_split_bwd_stats", 0, bytes, bn_sp_bwd_stats_nchw_k, dim3(C, d.S, sgroups), dim3(kSpThreads), 0, s, x, gy, scale,
+                    offset, save_mean, save_invstd, part, d, act, alpha);
+    } else {
+        GGAN_LAUNCH("bn_split_bwd_stats", 0, bytes, bn_sp_bwd_stats_rows_k, dim3(cdiv(C, kSpCols), d.S, sgroups), dim3(kSpCols, kSpLanes),
+                    0, s, x, gy, scale, offset, save_mean, save_invstd, part, d, act, alpha);
+    }
+    GGAN_LAUNCH("bn_split_bwd_merge", 0, 12.0 * sgroups * d.S * C, bn_sp_bwd_merge_k, dim3(cdiv(C, kSpCols)), dim3(kSpCols, kSpMerge), 0,
+                s, (const float*)part, scale, save_invstd, coef, gscale, goffset, gx_chansum, d, sgroups, gx_groups);
+    if (gx_groups > 0) {
+        const size_t elems = (size_t)N / groups * gx_groups * C * HW;
+        GGAN_LAUNCH("bn_split_bwd_apply", 0, 12.0 * elems, bn_sp_bwd_apply_k, dim3(sp_apply_grid(elems)), dim3(256), 0, s, x, gy, scale,
+                    offset, save_mean, save_invstd, (const float*)coef, gx, d, gx_groups, act, alpha);
+    }
     return 0;
 }
 

@@ -25,7 +25,7 @@ from .conv import (  # noqa: F401
 from .linear import (  # noqa: F401
     Gemm, _fused_linear_backward, Gemm2, _CONSTS, cached_const, Gemm2Dgrad, _HEAD_HINT, head_bce_hint, CriticHead, DynScan,
     gemm_colsum_, linear)
-from .norm import BatchNormTrain, BatchNormBwd, LinearBatchNormRows, _all_gather_rows, SyncBatchNormTrain  # noqa: F401
+from .norm import BatchNormTrain, BatchNormGroupedTrain, BatchNormBwd, LinearBatchNormRows, _all_gather_rows, SyncBatchNormTrain  # noqa: F401
 from .rows import (  # noqa: F401
     JoinRows, Fanout, fanout, SplitRows, CastScaleI32, Axpby, MixMean, GmmLatent, GmmLatentST, MixRbfMmd2, Reparam, AGG_KL, AGG_IKL, AGG_JSD,
     AggDiv, RowLerp, gmm_posterior_assign_, cluster_accuracy_)

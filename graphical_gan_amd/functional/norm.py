@@ -3,7 +3,7 @@ import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 from .._lib import ACT_NONE, check  # noqa: F401
-from ._core import _L, _p, _stream, _c, _skip_undefined  # noqa: F401
+from ._core import _L, _p, _stream, _c, _skip_undefined, workspace  # noqa: F401
 from .linear import Gemm, gemm_colsum_  # noqa: F401
 
 
@@ -46,6 +46,62 @@ class BatchNormTrain(Function):
         if csum is not None:
             gx._ggan_chansum = csum      # picked up by the producing layer's backward if gx reaches it unchanged
         return gx, gs.view(ctx.pshape), go.view(ctx.pshape), None, None, None
+
+
+@_skip_undefined
+class BatchNormGroupedTrain(Function):
+    """Training-mode BN over every axis but the channel axis, with the leading axis cut into `groups` equal contiguous parts that get
+    their own batch statistics and share scale / offset (ggan_bn_split_fwd_train / ggan_bn_split_bwd_act: slab partials over the whole
+    chip + a fixed-order merge).  x: [N, C, H, W] (NCHW) or [N, C] rows -- a channels-last volume is passed as [rows, C].  The state-space
+    critics evaluate [fake; real] in one batch with groups = 2, so that each half is normalised on its own as in the reference's two
+    calls.  grad_rows (optional, a multiple of N / groups): only the leading grad_rows rows need a data gradient (generator steps); gx
+    is left unwritten past them.  act: NONE / LRELU / RELU.  No double backward: no state-space objective differentiates twice."""
+
+    @staticmethod
+    def forward(ctx, x, scale, offset, eps, act, alpha, groups=1, grad_rows=None):
+        x = _c(x)
+        N, Cc = x.shape[0], x.shape[1]
+        HW = x.numel() // (N * Cc)
+        if N % groups:
+            raise ValueError('BatchNormGroupedTrain: %d rows do not split into %d groups' % (N, groups))
+        gx_groups = groups
+        if grad_rows is not None and grad_rows < N:
+            if grad_rows % (N // groups):
+                raise ValueError('BatchNormGroupedTrain: grad_rows %d is not a whole number of groups of %d' % (grad_rows, N // groups))
+            gx_groups = grad_rows // (N // groups)
+        sc, of = _c(scale).reshape(-1), _c(offset).reshape(-1)
+        y = torch.empty_like(x)
+        mean = torch.empty((groups, Cc), dtype=torch.float32, device=x.device)
+        invstd = torch.empty_like(mean)
+        ws = workspace(x.device)
+        check(_L().ggan_bn_split_fwd_train(_p(x), _p(sc), _p(of), _p(y), _p(mean), _p(invstd), N, Cc, HW, groups, eps, act, alpha,
+                                           _p(ws), ws.numel(), _stream()), 'ggan_bn_split_fwd_train')
+        ctx.dims = (N, Cc, HW, groups, gx_groups)
+        ctx.act, ctx.alpha = act, alpha
+        ctx.pshape = tuple(scale.shape)
+        ctx.save_for_backward(x, sc, of, mean, invstd)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        if torch.is_grad_enabled():
+            raise NotImplementedError('BatchNormGroupedTrain has no double backward (no state-space objective needs one)')
+        x, sc, of, mean, invstd = ctx.saved_tensors
+        N, Cc, HW, groups, gx_groups = ctx.dims
+        need = ctx.needs_input_grad
+        gy = _c(gy)
+        gx = torch.empty_like(x) if need[0] else None
+        gs = torch.empty((Cc,), dtype=torch.float32, device=x.device) if need[1] else None
+        go = torch.empty((Cc,), dtype=torch.float32, device=x.device) if need[2] else None
+        csum = torch.empty((Cc,), dtype=torch.float32, device=x.device) if (need[0] and HW > 1) else None
+        ws = workspace(x.device)
+        check(_L().ggan_bn_split_bwd_act(_p(x), _p(gy), ctx.act, ctx.alpha, _p(sc), _p(of), _p(mean), _p(invstd), _p(gx), _p(gs), _p(go),
+                                         _p(csum), N, Cc, HW, groups, gx_groups if need[0] else 0, _p(ws), ws.numel(), _stream()),
+              'ggan_bn_split_bwd_act')
+        if csum is not None and gx_groups == groups:
+            gx._ggan_chansum = csum      # picked up by the producing layer's backward if gx reaches it unchanged
+        return (gx, gs.view(ctx.pshape) if gs is not None else None, go.view(ctx.pshape) if go is not None else None,
+                None, None, None, None, None)[:ctx._n_in]
 
 
 class BatchNormBwd(Function):

@@ -1,7 +1,7 @@
 """State-space GAN on moving-MNIST sequences: the net + loss wiring of ssgan_inference_moving_mnist.py against this
 package's `tflib` (same layer names, so registry keys match the reference's checkpoints).
 
-  hyper-parameters   ssgan_inference_moving_mnist.py:27-56 (MODE='local_ep', POS_MODE, OP_DYN_MODE, BN flags off)
+  hyper-parameters   ssgan_inference_moving_mnist.py:27-56 (MODE='local_ep', POS_MODE, OP_DYN_MODE, BN_FLAG_G/E/D: bn_g/e/d)
   nets               :98-349      (ImplicitOperator, ConcatOperator, Dynamic{Generator,Extractor}, Generator, Extractor,
                                    G_Extractor, Discriminator, DynamicDiscrminator, ZGDiscrminator)
   losses             :510-547     weighted_local_epce over LEN+1 factors with ratio = [1]*(LEN-1)+[1,LEN] (:78-79)
@@ -10,9 +10,12 @@ What is done differently from a literal transcription (same arithmetic):
   * every frame net runs on all B*LEN frames at once (the reference does too) and the LEN-1 transition critics, which
     share one set of weights, are evaluated in ONE call on the stacked pairs [(LEN-1)*B, 2*dim_l] instead of LEN-1 calls;
     their equal-weight BCE terms collapse into one term (sum_i r*mean_B(.) == r*(LEN-1)*mean over the stack);
-  * each of the three critics is evaluated once per step on [fake; real] (rows independent: no BatchNorm); generator steps
-    hand the critics their weights without gradient edges (tflib.frozen), as TF's var_list does, and run the frame
-    critic's conv data-gradient on the fake frames only (grad_rows).
+  * each of the three critics is evaluated once per step on [fake; real]; with BN_FLAG_D the critic's BatchNorm layers
+    normalise the two halves with their own statistics (groups=2: the reference calls the critic once per half), so the
+    rows stay independent of the other half; generator steps hand the critics their weights without gradient edges
+    (tflib.frozen), as TF's var_list does, and run the frame critic's conv data-gradient on the fake frames only (grad_rows).
+  * with a BN flag on, a conv / deconv / linear layer followed by BatchNorm runs without its fused activation: the
+    activation is the BatchNorm's epilogue.
 """
 
 import numpy as np
@@ -28,9 +31,10 @@ class SSConfig(object):
 
     def __init__(self, batch_size=50, length=16, dim=32, dim_op=256, dim_g=128, dim_l=8, n_c=10,
                  pos_mode='naive_mean_field', op_dyn_mode='res', lr=1e-4, fuse=True, channels=1, dataset='moving_mnist',
-                 mode='local_ep', lamb=0.1, ali_mode='concat_x'):
+                 mode='local_ep', lamb=0.1, ali_mode='concat_x', bn_g=False, bn_e=False, bn_d=False):
         """defaults: ssgan_inference_moving_mnist.py:26-53.  channels=3, n_c=0, length=31, op_dyn_mode='res_w',
-        dataset='chairs': ssgan_inference_chairs.py:28-54 (RGB frames, no class labels)."""
+        dataset='chairs': ssgan_inference_chairs.py:28-54 (RGB frames, no class labels).  bn_g / bn_e / bn_d: BN_FLAG_G / _E / _D
+        (:31-34), BatchNorm in the frame generator / the extractors / the frame and sequence critics."""
         self.dataset = dataset
         assert mode in ('local_ep', 'local_epce-z', 'ali', 'alice-z'), mode
         self.mode, self.lamb = mode, lamb                      # *-z: + LAMBDA * l2(real_x, G(q_z_g, q_z_l, real_y)) (:549-558)
@@ -51,6 +55,7 @@ class SSConfig(object):
         self.lr, self.beta1 = lr, 0.5
         self.critic_iters = 1
         self.fuse = fuse
+        self.bn_g, self.bn_e, self.bn_d = bool(bn_g), bool(bn_e), bool(bn_d)
 
     def ratio(self):
         r = np.asarray([1.0] * (self.LEN - 1) + [1, self.LEN])
@@ -121,12 +126,19 @@ class StateSpaceGAN(object):
             return lib.ops.linear.Linear(name, nin, nout, x, activation=act)
         return F.ActFwd.apply(lib.ops.linear.Linear(name, nin, nout, x), act, 0.2)
 
-    def _conv(self, name, cin, cout, x, grad_rows=None):
+    def _conv(self, name, cin, cout, x, grad_rows=None, bn=None):
+        """5x5 stride-2 conv + LeakyReLU; bn = (BatchNorm name, groups): conv -> BatchNorm -> LeakyReLU, the activation in the
+        BatchNorm's epilogue"""
+        if bn is not None:
+            out = lib.ops.conv2d.Conv2D(name, cin, cout, 5, x, stride=2, grad_rows=grad_rows)
+            return lib.ops.batchnorm.Batchnorm(bn[0], [0, 2, 3], out, activation=LRELU, groups=bn[1], grad_rows=grad_rows)
         if self.cfg.fuse:
             return lib.ops.conv2d.Conv2D(name, cin, cout, 5, x, stride=2, activation=LRELU, grad_rows=grad_rows)
         return F.ActFwd.apply(lib.ops.conv2d.Conv2D(name, cin, cout, 5, x, stride=2, grad_rows=grad_rows), LRELU, 0.2)
 
-    def _deconv(self, name, cin, cout, x, act, out=None):
+    def _deconv(self, name, cin, cout, x, act, out=None, bn=None):
+        if bn is not None:       # deconv -> BatchNorm (groups = 1: the generator runs on one batch) -> act
+            return lib.ops.batchnorm.Batchnorm(bn, [0, 2, 3], lib.ops.deconv2d.Deconv2D(name, cin, cout, 5, x), activation=act, groups=1)
         if self.cfg.fuse:
             return lib.ops.deconv2d.Deconv2D(name, cin, cout, 5, x, activation=act, out=out)
         return F.ActFwd.apply(lib.ops.deconv2d.Deconv2D(name, cin, cout, 5, x), act, 0.0)
@@ -197,53 +209,68 @@ class StateSpaceGAN(object):
 
     def Generator(self, z_g, z_l, labels, out_slot=None):
         c, d = self.cfg, self.cfg.dim
-        out = self._lin('Generator.Input', c.dim_g + c.dim_l + c.n_c, c.flat, self._z_rows(z_g, z_l, labels), RELU)
+        bn = (lambda i: 'Generator.BN%d' % i) if c.bn_g else (lambda i: None)
+        if c.bn_g:
+            out = lib.ops.linear.Linear('Generator.Input', c.dim_g + c.dim_l + c.n_c, c.flat, self._z_rows(z_g, z_l, labels))
+            out = lib.ops.batchnorm.Batchnorm('Generator.BN1', [0], out, activation=RELU, groups=1)
+        else:
+            out = self._lin('Generator.Input', c.dim_g + c.dim_l + c.n_c, c.flat, self._z_rows(z_g, z_l, labels), RELU)
         out = out.reshape(c.B * c.LEN, 8 * d, 4, 4)
-        out = self._deconv('Generator.2', 8 * d, 4 * d, out, RELU)
-        out = self._deconv('Generator.3', 4 * d, 2 * d, out, RELU)
-        out = self._deconv('Generator.4', 2 * d, d, out, RELU)
+        out = self._deconv('Generator.2', 8 * d, 4 * d, out, RELU, bn=bn(2))
+        out = self._deconv('Generator.3', 4 * d, 2 * d, out, RELU, bn=bn(3))
+        out = self._deconv('Generator.4', 2 * d, d, out, RELU, bn=bn(4))
         out = self._deconv('Generator.5', d, c.C, out, TANH, out=out_slot)
         return out.reshape(c.B, c.LEN, c.output_dim)
 
-    def _conv_stack(self, pre, x, cin, grad_rows=None):
+    def _conv_stack(self, pre, x, cin, grad_rows=None, bn=False, groups=1):
+        """bn: BatchNorm '<pre>.BN2..4' after the last three convs, each of the `groups` equal parts of the batch on its own"""
         d = self.cfg.dim
+        b = (lambda i: (pre + '.BN%d' % i, groups)) if bn else (lambda i: None)
         out = self._conv(pre + '.1', cin, d, x, grad_rows)
-        out = self._conv(pre + '.2', d, 2 * d, out, grad_rows)
-        out = self._conv(pre + '.3', 2 * d, 4 * d, out, grad_rows)
-        return self._conv(pre + '.4', 4 * d, 8 * d, out, grad_rows)
+        out = self._conv(pre + '.2', d, 2 * d, out, grad_rows, bn=b(2))
+        out = self._conv(pre + '.3', 2 * d, 4 * d, out, grad_rows, bn=b(3))
+        return self._conv(pre + '.4', 4 * d, 8 * d, out, grad_rows, bn=b(4))
 
     def Extractor(self, inputs, labels):
         c = self.cfg
-        out = self._conv_stack('Extractor', inputs.reshape(c.B * c.LEN, c.C, 64, 64), c.C).reshape(c.B * c.LEN, c.flat)
+        out = self._conv_stack('Extractor', inputs.reshape(c.B * c.LEN, c.C, 64, 64), c.C, bn=c.bn_e).reshape(c.B * c.LEN, c.flat)
         out = torch.cat([out, self.expand_labels(labels)], 1)
         return self._lin('Extractor.Output', c.flat + c.n_c, c.dim_l, out).reshape(c.B, c.LEN, c.dim_l)
 
     def G_Extractor(self, inputs, labels):
         c = self.cfg
-        out = self._conv_stack('Extractor.G', inputs.reshape(c.B, c.C * c.LEN, 64, 64), c.C * c.LEN).reshape(c.B, c.flat)
+        out = self._conv_stack('Extractor.G', inputs.reshape(c.B, c.C * c.LEN, 64, 64), c.C * c.LEN, bn=c.bn_e).reshape(c.B, c.flat)
         return self._lin('Extractor.G.Output', c.flat + c.n_c, c.dim_g, torch.cat([out, labels], 1))
 
     def Discriminator(self, x, z_g, z_l, labels):
         c = self.cfg
         return self._frame_critic(x.reshape(c.B * c.LEN, c.output_dim), self._z_rows(z_g, z_l, labels), self.expand_labels(labels))
 
-    def _frame_critic(self, frames, z_rows, label_rows, grad_rows=None):
+    def _frame_critic(self, frames, z_rows, label_rows, grad_rows=None, groups=1):
         """the frame critic on any number of (frame, latent row, label row) triples; grad_rows: only the leading frames carry
-        a gradient (generator steps: [fake; real])"""
+        a gradient (generator steps: [fake; real]); groups: equal parts of the batch with their own BatchNorm statistics"""
         c, n = self.cfg, frames.shape[0]
-        out = self._conv_stack('Discriminator', frames.reshape(n, c.C, 64, 64), c.C, grad_rows).reshape(n, c.flat)
+        out = self._conv_stack('Discriminator', frames.reshape(n, c.C, 64, 64), c.C, grad_rows, bn=c.bn_d,
+                               groups=groups).reshape(n, c.flat)
         z_out = self._lin('Discriminator.z1', c.dim_g + c.dim_l + c.n_c, 512, z_rows, LRELU)
         out = torch.cat([out, z_out, label_rows], 1)
         out = self._lin('Discriminator.zx1', c.flat + 512 + c.n_c, 512, out, LRELU)
         return self._lin('Discriminator.Output', 512, 1, out).reshape(-1)
 
-    def SequenceDiscriminator(self, x, z_g, z_l, labels, grad_rows=None):
+    def SequenceDiscriminator(self, x, z_g, z_l, labels, grad_rows=None, groups=1):
         """ALI_MODE = 'concat_x' (:407-449): the frames of a sequence as input channels, one logit per sequence; works on any
-        number of (sequence, z_g, z_l, labels) rows (the critic step hands it [fake; real])"""
+        number of (sequence, z_g, z_l, labels) rows (the critic step hands it [fake; real], groups=2: with BN_FLAG_D each half
+        has its own BatchNorm statistics)"""
         c, n = self.cfg, x.shape[0]
         if c.ali_mode == '3dcnn':        # :352-405: the sequence as an NLHWC volume (one channel: the transpose is a reshape)
             out, cin, s24 = x.reshape(n, c.LEN, 64, 64, 1), 1, (2 if c.LEN == 16 else 1)
             for i, (cout, sl) in enumerate(((c.dim, 2), (2 * c.dim, s24), (4 * c.dim, 2), (8 * c.dim, s24))):
+                if c.bn_d and i > 0:     # Conv3D -> Batchnorm 'Discriminator.BN2..4' over [0,1,2,3] -> LeakyReLU (epilogue)
+                    out = lib.ops.conv3d.Conv3D('Discriminator.%d' % (i + 1), 4, cin, cout, 4, out, stride=2, stride_len=sl,
+                                                grad_rows=grad_rows)
+                    out, cin = lib.ops.batchnorm.Batchnorm('Discriminator.BN%d' % (i + 1), [0, 1, 2, 3], out, activation=LRELU,
+                                                           groups=groups, grad_rows=grad_rows), cout
+                    continue
                 out = lib.ops.conv3d.Conv3D('Discriminator.%d' % (i + 1), 4, cin, cout, 4, out, stride=2, stride_len=sl,
                                             activation=LRELU if c.fuse else None, grad_rows=grad_rows)
                 out, cin = (out if c.fuse else lib.ops.act.LeakyReLU(out)), cout
@@ -253,13 +280,14 @@ class StateSpaceGAN(object):
             return self._lin('Discriminator.Output', 512, 1, out).reshape(-1)
         if c.ali_mode == 'concat_z':     # :451-497: per-frame conv stack + a 4x4 VALID conv to DIM_LATENT_G features per frame
             fr = None if grad_rows is None else grad_rows * c.LEN
-            out = self._conv_stack('Discriminator', x.reshape(n * c.LEN, c.C, 64, 64), c.C, fr)
+            out = self._conv_stack('Discriminator', x.reshape(n * c.LEN, c.C, 64, 64), c.C, fr, bn=c.bn_d, groups=groups)
             out = lib.ops.conv2d.Conv2D('Discriminator.5', 8 * c.dim, c.dim_g, 4, out, stride=1, padding='VALID').reshape(n, c.LEN * c.dim_g)
             z = torch.cat([z_g, z_l.reshape(n, c.LEN * c.dim_l), labels], 1)
             z_out = self._lin('Discriminator.z1', c.dim_g + c.dim_l * c.LEN + c.n_c, 512, z, LRELU)
             out = self._lin('Discriminator.zx1', c.LEN * c.dim_g + 512 + c.n_c, 512, torch.cat([out, z_out, labels], 1), LRELU)
             return self._lin('Discriminator.Output', 512, 1, out).reshape(-1)
-        out = self._conv_stack('Discriminator', x.reshape(n, c.C * c.LEN, 64, 64), c.C * c.LEN, grad_rows).reshape(n, c.flat)
+        out = self._conv_stack('Discriminator', x.reshape(n, c.C * c.LEN, 64, 64), c.C * c.LEN, grad_rows, bn=c.bn_d,
+                               groups=groups).reshape(n, c.flat)
         z = torch.cat([z_g, z_l.reshape(n, c.LEN * c.dim_l), labels], 1)
         z_out = self._lin('Discriminator.z1', c.dim_g + c.dim_l * c.LEN + c.n_c, 512, z, LRELU)
         out = self._lin('Discriminator.zx1', c.flat + 512, 512, (out, z_out), LRELU)
@@ -278,7 +306,7 @@ class StateSpaceGAN(object):
             if which in ('gen', 'disc'):
                 assert which == 'disc' or not real_x.requires_grad, 'grad_rows: the real sequences must be data'
                 d = self.SequenceDiscriminator(F.JoinRows.apply(fake_x, real_x), torch.cat([p_z_g, q_z_g], 0), torch.cat([p_z_l, q_z_l], 0),
-                                               torch.cat([p_y, real_y], 0), grad_rows=c.B if which == 'gen' else None)
+                                               torch.cat([p_y, real_y], 0), grad_rows=c.B if which == 'gen' else None, groups=2)
                 d_fake, d_real = F.SplitRows.apply(d, c.B)
             else:
                 d_fake = self.SequenceDiscriminator(fake_x, p_z_g, p_z_l, p_y)
@@ -374,8 +402,8 @@ class StateSpaceGAN(object):
         J.ONLY[0] = which
         with (lib.frozen('Discriminator') if which == 'gen' else lib.frozen()):
             if which in ('gen', 'disc'):
-                # every critic once, on [fake; real] (rows are independent: no BatchNorm); in generator steps the conv
-                # data-gradient is needed for the fake frames only
+                # every critic once, on [fake; real] (with BN_FLAG_D each half has its own BatchNorm statistics: groups=2); in
+                # generator steps the conv data-gradient is needed for the fake frames only
                 nf = c.B * c.LEN
                 assert which == 'disc' or not real_x.requires_grad, 'grad_rows: the real frames must be data'
                 # the two latent critics (MLP chains of short launches) run on the second stream beside the frame critic's conv stack
@@ -393,7 +421,7 @@ class StateSpaceGAN(object):
                 d = self._frame_critic(F.JoinRows.apply(fake_x.reshape(nf, -1), real_x.reshape(nf, -1)),
                                        torch.cat([self._z_rows(p_z_g, p_z_l, p_y), self._z_rows(q_z_g, q_z_l, real_y)], 0),
                                        torch.cat([self.expand_labels(p_y), self.expand_labels(real_y)], 0),
-                                       grad_rows=nf if which == 'gen' else None)
+                                       grad_rows=nf if which == 'gen' else None, groups=2)
                 if cur is not None:
                     cur.wait_stream(self._side)
                 (tf_, tr_), (zf, zr), (df, dr) = (F.SplitRows.apply(t, (c.LEN - 1) * c.B), F.SplitRows.apply(zg, c.B),

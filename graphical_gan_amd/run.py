@@ -200,10 +200,14 @@ def config(S):
     not silently ignored"""
     if S['DATASET'] in ('moving_mnist', 'chairs'):
         from .models_ssgan import SSConfig
-        assert not S.get('BN_FLAG') and S.get('DIM_LATENT_T', S['DIM_LATENT_L']) == S['DIM_LATENT_L'] and S.get('BETA1', .5) == .5
+        assert S.get('DIM_LATENT_T', S['DIM_LATENT_L']) == S['DIM_LATENT_L'] and S.get('BETA1', .5) == .5
+        # BN_FLAG_G / _E / _D default to BN_FLAG, as the scripts derive them (:31-34); BN_FLAG_OP (chairs :37) is read by no net of
+        # the reference, so it is accepted and has no effect
+        bn = bool(S.get('BN_FLAG', False))
         return SSConfig(batch_size=S['BATCH_SIZE'], length=S['LEN'], dim=S['DIM'], dim_op=S['DIM_OP'], dim_g=S['DIM_LATENT_G'],
                         dim_l=S['DIM_LATENT_L'], n_c=S['N_C'], pos_mode=S['POS_MODE'], op_dyn_mode=S['OP_DYN_MODE'], lr=S['LR'],
-                        channels=S['OUTPUT_SHAPE'][0], dataset=S['DATASET'], mode=S['MODE'], lamb=S['LAMBDA'], ali_mode=S['ALI_MODE'])
+                        channels=S['OUTPUT_SHAPE'][0], dataset=S['DATASET'], mode=S['MODE'], lamb=S['LAMBDA'], ali_mode=S['ALI_MODE'],
+                        bn_g=S.get('BN_FLAG_G', bn), bn_e=S.get('BN_FLAG_E', bn), bn_d=S.get('BN_FLAG_D', bn))
     from .models import Config
     mode_k = S.get('MODE_K', 'CONCRETE')
     if mode_k == 'REINFORCE':

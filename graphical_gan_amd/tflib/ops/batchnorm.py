@@ -1,7 +1,13 @@
 """Batchnorm (tflib/ops/batchnorm.py:6-87).  The scripts never pass `is_training`, so the reference always
 runs the training branch with batch statistics (:51-52); moving statistics are created (and returned by
 params_with_name) but never written.  axes [0,2,3] -> fused NCHW branch, axes [0] -> the non-fused branch with
-[1,F]-shaped parameters."""
+[1,F]-shaped parameters, axes [0,1,2,3] on a 5-D channels-last volume (the 3dcnn critic of the state-space scripts) -> the
+non-fused branch with [1,1,1,1,C]-shaped parameters and no moving statistics.
+
+`groups=` (an extension, like `activation=`): the batch axis is cut into that many equal parts, each normalised with its own
+statistics (the state-space critics see [fake; real] in one batch; the reference calls them once per half); `grad_rows=`: only the
+leading rows need a data gradient.  Any `groups` -- and every 5-D input -- takes the row-grouped chip-wide kernels
+(functional.BatchNormGroupedTrain); a call without it takes the path it always took."""
 import numpy as np
 
 from ... import functional as F
@@ -30,12 +36,29 @@ def _bn(x, scale, offset, act, alpha):
     return F.SyncBatchNormTrain.apply(x, scale, offset, 1e-5, act, float(alpha), group)
 
 
+def _bn_grouped(x, scale, offset, act, alpha, groups, grad_rows):
+    if not (_SYNC_GROUP is None or _SYNC_GROUP is False):
+        raise NotImplementedError('Batchnorm(groups=...) / 5-D Batchnorm with cross-replica statistics is not built')
+    return F.BatchNormGroupedTrain.apply(x, scale, offset, 1e-5, act, float(alpha), int(groups), grad_rows)
+
+
 def Batchnorm(name, axes, inputs, is_training=None, stats_iter=None, update_moving_stats=True, fused=True,
-              activation=None, alpha=0.2):
+              activation=None, alpha=0.2, groups=None, grad_rows=None):
     act = F.ACT_NONE if activation is None else activation
     if is_training is not None:
         raise NotImplementedError('Batchnorm(is_training=...) is not used by any reference script and is not built')
     axes = list(axes)
+    if axes == [0, 1, 2, 3] and inputs.dim() == 5:
+        # tf.nn.moments over every axis but the last + tf.nn.batch_normalization (eps 1e-5): the volume is [rows, C]
+        shape = [1, 1, 1, 1, inputs.shape[4]]
+        offset = _param(name + '.offset', np.zeros(shape, dtype='float32'))
+        scale = _param(name + '.scale', np.ones(shape, dtype='float32'))
+        rows = inputs.reshape(-1, inputs.shape[4])
+        per_volume = rows.shape[0] // inputs.shape[0]
+        out = _bn_grouped(rows, scale, offset, act, alpha, groups or 1, grad_rows * per_volume if grad_rows else None)
+        if act in (F.ACT_LRELU, F.ACT_RELU):
+            _tap(name, out)
+        return out.reshape(inputs.shape)
     if (axes == [0, 2, 3] or axes == [0, 2]) and fused is True:
         x = inputs.unsqueeze(3) if axes == [0, 2] else inputs
         c = x.shape[1]
@@ -43,7 +66,7 @@ def Batchnorm(name, axes, inputs, is_training=None, stats_iter=None, update_movi
         scale = _param(name + '.scale', np.ones(c, dtype='float32'))
         _param(name + '.moving_mean', np.zeros(c, dtype='float32'), trainable=False)
         _param(name + '.moving_variance', np.ones(c, dtype='float32'), trainable=False)
-        out = _bn(x, scale, offset, act, alpha)
+        out = _bn(x, scale, offset, act, alpha) if groups is None else _bn_grouped(x, scale, offset, act, alpha, groups, grad_rows)
         if act in (F.ACT_LRELU, F.ACT_RELU):
             _tap(name, out)
         return out[:, :, :, 0] if axes == [0, 2] else out
@@ -51,5 +74,10 @@ def Batchnorm(name, axes, inputs, is_training=None, stats_iter=None, update_movi
         shape = [1, inputs.shape[1]]
         offset = _param(name + '.offset', np.zeros(shape, dtype='float32'))
         scale = _param(name + '.scale', np.ones(shape, dtype='float32'))
-        return _bn(inputs, scale, offset, act, alpha)
+        if groups is None:
+            return _bn(inputs, scale, offset, act, alpha)
+        out = _bn_grouped(inputs, scale, offset, act, alpha, groups, grad_rows)
+        if act in (F.ACT_LRELU, F.ACT_RELU):
+            _tap(name, out)
+        return out
     raise Exception('unsupported')

@@ -249,6 +249,25 @@ int ggan_bn_bwd_bwd(const float* x, const float* gy, const float* y, int y_act, 
                     const float* save_mean, const float* save_invstd, float* ggy, float* gx2, float* gscale2, int N, int C, int HW,
                     ggan_stream_t stream);
 
+/* Row-grouped training-mode BatchNorm over the whole chip (the state-space critics' [fake; real] batches, the 3dcnn critic's NDHWC
+ * volumes read as [rows, C], the frame generators' [B*LEN, C, H, W] maps).  x [N, C, HW] (HW = 1: rows x channels); the leading
+ * dimension is cut into `groups` equal contiguous parts, each normalised with its OWN batch statistics (biased variance, merged from
+ * per-slab (count, mean, M2) by Chan's formula); scale / offset [C] are shared.  save_mean / save_invstd: [groups, C].  Three launches,
+ * no atomics, fixed summation order (bit-identical run to run).  ws: the caller's workspace (GGAN_WS_RESERVED bytes skipped; needs
+ * 12 * groups * C * (slabs + 1) bytes after it, a few hundred KB at most).  act: NONE / LRELU / RELU epilogue, as ggan_bn_fwd_train. */
+int ggan_bn_split_fwd_train(const float* x, const float* scale, const float* offset, float* y, float* save_mean, float* save_invstd,
+                            int N, int C, int HW, int groups, float eps, int act, float alpha, void* ws, size_t ws_bytes,
+                            ggan_stream_t stream);
+/* Its backward.  gy = dL/d(activated output); the activation (NONE / LRELU / RELU) is differentiated on load at the affine output
+ * recomputed from x (no forward output kept).  gscale / goffset [C] (may be NULL: then neither is computed) are summed over all groups.
+ * gx is written for the leading gx_groups groups only (0..groups; the rest is left untouched and, when gscale and goffset are NULL,
+ * the trailing groups' gy is not read).  gx_chansum (may be NULL; HW > 1 only): sum of gx per channel over the written groups = the
+ * bias gradient of the layer that feeds this BatchNorm. */
+int ggan_bn_split_bwd_act(const float* x, const float* gy, int act, float alpha, const float* scale, const float* offset,
+                          const float* save_mean, const float* save_invstd, float* gx, float* gscale, float* goffset,
+                          float* gx_chansum, int N, int C, int HW, int groups, int gx_groups, void* ws, size_t ws_bytes,
+                          ggan_stream_t stream);
+
 /* Cross-replica ("sync") BatchNorm, SURVEY.md 8(e): statistics over the GLOBAL batch of `world` equal-sized replicas.  The
  * reference has no multi-GPU path; this is the mode under which N GPUs x B/N reproduce 1 GPU x B.  The host all-gathers the
  * 2*C floats each *_stats call produces ([2][C]: forward (mean, M2), backward (sum g, sum g*xhat)) into [world][2][C] and hands
