@@ -113,7 +113,7 @@ class Trainer(object):
         self.feed = self.model.feed_buffers(self.device)
         if hasattr(self.model, 'cfg') and isinstance(self.feed, dict) and ('p_z_noise' in self.feed or 'p_z_g' in self.feed):
             self.feed['rng_state'] = F.noise_state(self.device, seed)      # functional.noise_fill_: all noise of a step in one launch
-        self._graphs = {}
+        self._graphs, self._iter_graph = {}, None      # captured steps (per kind) / the captured iteration
         self._calls = {'gen': 0, 'disc': 0}
         self.world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         # data-parallel runs split the step graph around the gradient all-reduce; the flag lets a single GPU exercise
@@ -141,8 +141,9 @@ class Trainer(object):
                 self.graph_enabled = False   # direct communicator it is an enqueue on the step's stream and is captured like a kernel
             if hasattr(self.model, 'fork_nets'):
                 self.model.fork_nets = False      # keep the statistics exchanges of the two passes in one stream order
-        elif self.comm is not None:
-            rccl.release_stats()                  # (a Trainer with cross-replica BatchNorm before this one left the communicator serial)
+        else:
+            lib.ops.batchnorm.set_sync_group(None)   # (a Trainer with cross-replica BatchNorm before this one: its statistics exchange, and the
+                                                     #  communicator's serial mode, end here)
         # the pack kernel may sum the filter-gradient slabs only if every parameter receives ONE gradient contribution per
         # backward pass (true when the critic sees [fake; real] as one batch; the wali-gp penalty re-enters the critic)
         self.single_contrib = bool(self.model.single_contribution)
@@ -214,8 +215,12 @@ class Trainer(object):
         from . import optim as _optim
         self._ring_epoch = _optim.STATE_EPOCH[0]
         self.feed['ring'] = (ring, ctr['gen'], ctr.get('disc'), -taken)
-        self._graphs = {}                      # (captured steps read the staging buffer)
-        self._iter_graph = None
+        self.drop_graphs()                     # (captured steps read the staging buffer)
+
+    def drop_graphs(self):
+        """forget the captured step and iteration graphs: the next steps capture again (what a capture baked in -- learning rates, where
+        the minibatch comes from, the site plan -- has changed)"""
+        self._graphs, self._iter_graph = {}, None
 
     def _sample_noise(self):
         self.model.sample_noise(self.feed)
@@ -279,17 +284,12 @@ class Trainer(object):
 
     def _ahead_issue(self, st, k):
         """the nets pass of critic step k + 2 on the chain's stream: one chain (Generator, then Extractor), nothing forked off it"""
-        m, ns = self.model, st['stream']
-        saved = (m._pending_join, getattr(m, '_noise_event', None), m._early, m.fork_now)
-        m.fork_now = False
-        try:
-            with torch.cuda.stream(ns), F.launch_hint(AHEAD_TARGET_WGS):
-                st['nets'].append(self._nets(st['feeds'][k]))
-                ev = torch.cuda.Event()
-                ev.record(ns)
-                st['events'].append(ev)
-        finally:
-            m._pending_join, m._noise_event, m._early, m.fork_now = saved
+        ns = st['stream']
+        with self.model.single_stream(), torch.cuda.stream(ns), F.launch_hint(AHEAD_TARGET_WGS):
+            st['nets'].append(self._nets(st['feeds'][k]))
+            ev = torch.cuda.Event()
+            ev.record(ns)
+            st['events'].append(ev)
 
     def _ahead_step(self):
         """(nets, feed) of the next critic step of the iteration being captured.  The chain is forked behind critic step 1's own nets
@@ -335,9 +335,11 @@ class Trainer(object):
             raise RuntimeError('a hinted critic head still owes its cost value after the backward pass (functional.head_bce_hint): '
                                'the cost was not differentiated through that head')
 
-    def _fwd_bwd(self, which, nets=None, fuse_update=False, feed=None):
-        """fuse_update: the caller applies the update next with nothing but a (single-replica: empty) exchange in between"""
-        out = self._forward(self.feed if feed is None else feed, which, nets if nets is not None else self._nets())
+    def _fwd_bwd(self, which, nets=None, fuse_update=False, feed=None, out=None):
+        """fuse_update: the caller applies the update next with nothing but a (single-replica: empty) exchange in between.
+        out: the step's forward pass, already built (_disc_two_buckets)"""
+        if out is None:
+            out = self._forward(self.feed if feed is None else feed, which, nets if nets is not None else self._nets())
         if self.keep_outputs:        # (tests: the critic logits of a captured step -- static graph memory, valid after every replay)
             det = lambda v: [t.detach() for t in v] if isinstance(v, (list, tuple)) else v.detach()    # (no tape kept alive across steps)
             self.last_out[which] = {k: det(v) for k, v in out.items() if k in ('disc_fake', 'disc_real')}
@@ -403,55 +405,39 @@ class Trainer(object):
         opt.update()
         return cost
 
-    def _step_as_captured(self, which):
-        """eager_as_captured for the one-graph-per-step workloads: the step as its graph launches it (site plan of a [which] graph)"""
-        self.flush()
-        F.set_site_plan(self._site_plan([which], False))
-        try:
-            cost, _, _ = self._step_body(which)
-        finally:
-            F.set_site_plan(None)
-        return cost
-
     def _optimizers(self):
         from .optim import _optimizers
         return list(_optimizers.values())
 
-    def _capture(self, which):
-        # two-stream nets pass inside the step graph (models.GraphicalGAN.forward_nets): single-graph steps only -- with the
-        # graph cut for the gradient exchange it measured slower (40.1 k vs 41.7 k img/s on the forced-split path)
-        forkable = hasattr(self.model, 'fork_now') and not self.split_graph and not self.sync_bn
-        if forkable:
-            self.model.fork_now = True
+    @contextlib.contextmanager
+    def _forked(self):
+        """the two-stream nets pass (models.GraphicalGAN.forward_nets), and with it the launch plans of side-by-side conv chains, while a
+        single-graph step or iteration is warmed up, rehearsed, captured or launched as captured -- eager steps are host-bound and gain
+        nothing, and with the graph cut for the gradient exchange it measured slower (40.1 k vs 41.7 k img/s on the forced-split path)"""
+        m = self.model
+        if not hasattr(m, 'fork_now') or self.split_graph or self.sync_bn:
+            yield
+            return
+        prev = m.fork_now
+        m.fork_now = True
         try:
-            return self._capture_impl(which)
+            yield
         finally:
-            if forkable:
-                self.model.fork_now = False
+            m.fork_now = prev
 
     @contextlib.contextmanager
     def eager_as_captured(self):
         """eager steps that launch what the captured graphs launch: the two-stream nets pass (and with it the launch plan of side-by-side
         conv chains, models.launch_hint / functional.target_workgroups) is otherwise switched on for captures only.  bench.py brackets
         the kernels of such steps with HIP events, so that its per-kernel table is the timed graph's kernel mix."""
-        forkable = hasattr(self.model, 'fork_now') and not self.split_graph and not self.sync_bn
         prev_graph, self.graph_enabled = self.graph_enabled, False
         self._as_captured = True
-        if forkable:
-            self.model.fork_now = True
         try:
-            yield
+            with self._forked():
+                yield
         finally:
             self.graph_enabled = prev_graph
             self._as_captured = False
-            if forkable:
-                self.model.fork_now = False
-
-    def _step_body(self, which, ordinal=0):
-        """one whole step as it is captured into a single graph: forward, backward, pack, (gradient exchange), update.
-        ordinal: which of the iteration's steps of this kind it is -- the scope of its launch sites (functional.site_scope)"""
-        with self._launch_hint(which), F.site_scope('%s%d' % (which, ordinal)):
-            return self._step_body_impl(which)
 
     # ---- launch plans per launch site (round 6) ---------------------------------------------------------------------------------
     def site_plan_key(self, kinds, ahead):
@@ -492,12 +478,12 @@ class Trainer(object):
         with F.launch_hint(int(hint)):
             yield
 
-    def _step_body_impl(self, which):
-        st, nets = None, None
+    def _step_launches(self, which):
+        """one whole step as it is captured into a single graph: forward, backward, pack, (gradient exchange), update"""
         if self.dp_graph and which == 'gen':
             # two gradient buckets inside the one graph: the Generator's bucket is on the wire (the process group's
             # stream: a parallel branch of the graph) while the Extractor's backward pass still runs
-            nets = nets if nets is not None else self._nets()
+            nets = self._nets()
             cut = self.model.cut_tensors(nets) if hasattr(self.model, 'cut_tensors') else None
             # (two buckets in the generator step mean two autograd passes, Generator half then Extractor half -- and those two backward
             #  chains otherwise run SIDE BY SIDE on two streams, planned for half the chip each: one rank, forced exchange, 1.20 ms with
@@ -519,7 +505,7 @@ class Trainer(object):
                 cost, opt, keep = self._fwd_bwd(which, nets)
                 opt.all_reduce()
         else:
-            feed = None
+            nets, feed = None, None
             if which == 'disc' and getattr(self, '_ahead_run', None) is not None:
                 nets, feed = self._ahead_step()
             if self.dp_graph and which == 'disc' and hasattr(self.model, 'critic_cut') and not os.environ.get('GGAN_ONE_BUCKET'):
@@ -545,18 +531,12 @@ class Trainer(object):
         if cutinfo is not None:
             conv = tuple('Discriminator.%d.' % (i + 1) for i in range(cutinfo[1]))
             sp = opt.split_at(lambda p: getattr(p, 'param_name', '').startswith(conv))
+        if sp is None:
+            cost, opt, keep = self._fwd_bwd('disc', out=out)
+            opt.all_reduce()
+            return cost, opt, (keep, out)
         if opt._one is None or opt._one.shape != op.cost.shape:
             opt._one = F.unit_seed(op.cost)
-        if sp is None:
-            with F.defer_wgrad_reduce(self.single_contrib):
-                grads = opt.compute_gradients(op.cost)
-                late = F.add_late_terms()
-                keep = opt.pack(grads)
-                for ev in late:
-                    torch.cuda.current_stream(self.device).wait_event(ev)
-            opt.all_reduce()
-            self._costs_settled()
-            return out['disc_cost'].detach(), opt, (keep, out)
         k, off = sp
         cut = cutinfo[0]
         self._no_second_leaves(opt)
@@ -575,50 +555,35 @@ class Trainer(object):
         self._costs_settled()
         return out['disc_cost'].detach(), opt, (keep_a, keep_b, g, g2, out)
 
-    def _capture_impl(self, which):
-        # warm-up eagerly on a side stream (allocator + lazy init), restoring optimizer state afterwards
-        if getattr(self, '_cap_stream', None) is None:
-            self._cap_stream = F.shared_stream(self.device, 'capture')  # warm-up AND capture run on this stream, so the
-        s = self._cap_stream                                            # per-stream scratch buffers exist before capture
+    @contextlib.contextmanager
+    def _restored(self):
+        """the optimizers' state (theta, m, v, step counts) and the device noise state as they were in front of the block: warm-up steps and
+        the dress rehearsal of a capture leave no trace (a graph=True and a graph=False run with the same seed take the same steps and draw
+        the same noise sequence).  Snapshot and restore are issued on the current stream."""
+        snap = [(o, o.theta.clone(), o.m.clone(), o.v.clone(), o.step.clone()) for o in self._optimizers()]
+        rng = self.feed.get('rng_state') if isinstance(self.feed, dict) else None
+        rng_snap = rng.clone() if torch.is_tensor(rng) else None
+        yield
+        for o, th, m, v, st in snap:
+            o.theta.copy_(th); o.m.copy_(m); o.v.copy_(v); o.step.copy_(st)
+        if rng_snap is not None:
+            rng.copy_(rng_snap)
+
+    def _capture_cut(self, which):
+        """the step cut into graphs around its gradient exchange (split_graph), after two eager warm-up steps on the capture stream
+        (allocator, lazy init, per-stream scratch buffers)"""
+        s = F.shared_stream(self.device, 'capture')
         s.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(s):
-            # (the optimizers exist: the first call of each kind ran eagerly)
-            snap = [(o, o.theta.clone(), o.m.clone(), o.v.clone(), o.step.clone()) for o in self._optimizers()]
-            # (the device noise state too: a graph=True and a graph=False run with the same seed draw the same noise sequence)
-            rng = self.feed.get('rng_state') if isinstance(self.feed, dict) else None
-            rng_snap = rng.clone() if torch.is_tensor(rng) else None
+        with torch.cuda.stream(s), self._restored():
             self._eager(which)
-            if self.split_graph:
-                self._eager(which)
-            else:
-                # dress rehearsal: the step exactly as it will be captured (site plans included), once, eagerly -- every plan-time cache
-                # and lazily set function attribute then exists before the capture (see _capture_iteration)
-                F.set_site_plan(self._site_plan([which], False))
-                try:
-                    self._step_body(which)
-                finally:
-                    F.set_site_plan(None)
-            for o, th, m, v, st in snap:
-                o.theta.copy_(th); o.m.copy_(m); o.v.copy_(v); o.step.copy_(st)
-            if rng_snap is not None:
-                rng.copy_(rng_snap)
+            self._eager(which)
         torch.cuda.current_stream(self.device).wait_stream(s)
         torch.cuda.synchronize(self.device)
-        g1 = torch.cuda.CUDAGraph()
-        if not self.split_graph:
-            F.set_site_plan(self._site_plan([which], False))
-            lib.drop_taps([which])
-            try:
-                with torch.cuda.graph(g1, stream=s, capture_error_mode=_CAPTURE_MODE):
-                    cost, opt, keep = self._step_body(which)
-            finally:
-                F.set_site_plan(None)
-            return dict(g0=None, g1=g1, g1b=None, split=None, g2=None, cost=cost, opt=opt, keep=keep)
         # data parallel: [forward + backward + pack] -> all-reduce -> [Adam].  Every step is cut once more, after the
         # Extractor/Generator passes (g0): they read no critic variable, so they run while the previous critic step's gradient
         # exchange is still on the wire (step()) -- under the next generator step, or under the next critic step when
         # CRITIC_ITERS > 1.
-        g0 = torch.cuda.CUDAGraph()
+        g0, g1 = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
         with torch.cuda.graph(g0, stream=s, capture_error_mode=_CAPTURE_MODE):
             nets = self._nets()
         g1b, st = None, None
@@ -649,15 +614,20 @@ class Trainer(object):
                 work.wait()              # the current stream waits; the host does not block
             g2.replay()
 
-    def step(self, which):
-        """One gen or disc session.run on the current contents of the static buffers -> 0-dim cost tensor."""
-        self._calls[which] += 1
+    def _count(self, kinds):
+        """the steps [kinds] are about to be taken"""
+        for k in kinds:
+            self._calls[k] += 1
         if self._calls['gen'] >= 2 and (self._calls['disc'] >= 2 or not getattr(self.cfg, 'critic_iters', 1)):
             lib.end_build_phase()        # both step kinds have been built once (critic-free modes: the generator step): from here on
                                          # the layer calls draw no initial values
+
+    def step(self, which):
+        """One gen or disc session.run on the current contents of the static buffers -> 0-dim cost tensor."""
+        self._count([which])
         if not self.graph_enabled:
             if getattr(self, '_as_captured', False) and self._calls[which] > 1 and not self.split_graph:
-                return self._step_as_captured(which)
+                return self._launch_as_captured([which])[which + '_cost']
             return self._eager(which)
         rec = self._graphs.get(which)
         if rec is None:
@@ -665,11 +635,10 @@ class Trainer(object):
                 # the very first call of each kind runs eagerly AND counts as a real step
                 return self._eager(which)
             self.flush()
-            rec = self._capture(which)
-            self._graphs[which] = rec
-        if rec['g2'] is None:            # single GPU: the whole step is one graph
-            rec['g1'].replay()
-            return rec['cost']
+            rec = self._graphs[which] = self._capture_cut(which) if self.split_graph else self._capture_single([which])
+        if 'g' in rec:                   # the whole step is one graph
+            rec['g'].replay()
+            return rec['costs'][which + '_cost']
         if rec['g0'] is not None:
             rec['g0'].replay()           # overlaps the pending critic-gradient all-reduce
         self.flush()
@@ -703,13 +672,16 @@ class Trainer(object):
         return self.step('disc')
 
     def _iteration_body(self, kinds, ahead):
-        """the steps of one iteration as they are captured into ONE graph (and rehearsed eagerly in front of the capture): each step under
-        its site scope, the critic steps' nets passes ahead of time when `ahead` is the state _ahead_prepare made"""
+        """the launches of a single-graph step or iteration: the steps [kinds] in order, each under its launch hint and its site scope
+        (functional.site_scope: which of the graph's steps of its kind it is), with the in-graph gradient exchange when there are replicas,
+        and the critic steps' nets passes ahead of time when `ahead` is the state _ahead_prepare made.  The dress rehearsal, the capture
+        and eager_as_captured all issue it."""
         costs, keeps, seen = {}, [], {}
         self._ahead_run = ahead
         try:
             for k in kinds:
-                cost, opt, keep = self._step_body(k, seen.get(k, 0))    # (with the in-graph gradient exchange when there are replicas)
+                with self._launch_hint(k), F.site_scope('%s%d' % (k, seen.get(k, 0))):
+                    cost, opt, keep = self._step_launches(k)
                 seen[k] = seen.get(k, 0) + 1
                 costs[k + '_cost'] = cost
                 keeps.append((opt, keep))
@@ -720,87 +692,51 @@ class Trainer(object):
             keeps.append((None, (ahead['nets'], ahead['events'])))
         return costs, keeps
 
-    def _iteration_as_captured(self, kinds):
-        """eager_as_captured: one iteration launched eagerly exactly as the iteration graph launches it -- site plans, ahead-of-time passes --
-        on the capture stream (whose per-stream workspaces exist); the steps DO update the weights"""
-        forkable = hasattr(self.model, 'fork_now') and not self.sync_bn
-        s = self._cap_stream if getattr(self, '_cap_stream', None) is not None else F.shared_stream(self.device, 'capture')
-        self._cap_stream = s
+    def _launch_as_captured(self, kinds):
+        """eager_as_captured: the steps [kinds] launched eagerly exactly as their single graph launches them -- site plans, ahead-of-time
+        passes -- on the capture stream (whose per-stream workspaces exist); the steps DO update the weights"""
+        s, cur = F.shared_stream(self.device, 'capture'), torch.cuda.current_stream(self.device)
         use_ahead = self._ahead_ok(kinds)
-        F.set_site_plan(self._site_plan(kinds, use_ahead))
-        if forkable:
-            self.model.fork_now = True
-        try:
-            s.wait_stream(torch.cuda.current_stream(self.device))
+        with self._forked(), F.site_plan(self._site_plan(kinds, use_ahead)):
+            s.wait_stream(cur)
             with torch.cuda.stream(s):
                 costs, _ = self._iteration_body(kinds, self._ahead_prepare(kinds) if use_ahead else None)
-            torch.cuda.current_stream(self.device).wait_stream(s)
-            return costs
-        finally:
-            F.set_site_plan(None)
-            if forkable:
-                self.model.fork_now = False
+            cur.wait_stream(s)
+        return costs
 
-    def _capture_iteration(self, kinds):
-        """one HIP graph for a whole iteration (ring mode, one GPU): [generator step, critic step x CRITIC_ITERS], each
-        forward + backward + pack + Adam -- no graph-launch gap between the steps"""
-        forkable = hasattr(self.model, 'fork_now') and not self.sync_bn
-        if forkable:
-            self.model.fork_now = True
-        try:
-            if getattr(self, '_cap_stream', None) is None:
-                self._cap_stream = F.shared_stream(self.device, 'capture')
-            s = self._cap_stream
-            s.wait_stream(torch.cuda.current_stream(self.device))
-            with torch.cuda.stream(s):
-                snap = [(o, o.theta.clone(), o.m.clone(), o.v.clone(), o.step.clone()) for o in self._optimizers()]
-                rng = self.feed.get('rng_state') if isinstance(self.feed, dict) else None
-                rng_snap = rng.clone() if torch.is_tensor(rng) else None
+    def _capture_single(self, kinds):
+        """ONE HIP graph for the steps [kinds], each forward + backward + pack (+ exchange) + Adam: a step of its own ([which]), or in ring
+        mode a whole iteration ([generator step, critic step x CRITIC_ITERS]: no graph-launch gap between the steps).  On the capture stream:
+        eager warm-up steps, a dress rehearsal, the capture; the site logs of the last two are kept (site_log, capture_site_log)."""
+        s, cur = F.shared_stream(self.device, 'capture'), torch.cuda.current_stream(self.device)
+        with self._forked():
+            s.wait_stream(cur)
+            with torch.cuda.stream(s), self._restored():          # (allocator, lazy init; the optimizers exist: each kind ran eagerly once)
                 for k in kinds:
                     self._eager(k)
-                for o, th, m, v, st in snap:
-                    o.theta.copy_(th); o.m.copy_(m); o.v.copy_(v); o.step.copy_(st)
-                if rng_snap is not None:
-                    rng.copy_(rng_snap)
-            torch.cuda.current_stream(self.device).wait_stream(s)
+            cur.wait_stream(s)
             torch.cuda.synchronize(self.device)
-            if getattr(self, 'record_site_log', False):
-                F.record_sites(True)
             use_ahead = self._ahead_ok(kinds)
-            F.set_site_plan(self._site_plan(kinds, use_ahead))
-
-            try:
-                # dress rehearsal: the body exactly as it will be captured -- ahead-of-time passes, site plans -- run once eagerly, so that
-                # every plan-time cache (slab tables: a launch that finds none under capture bakes the slower in-kernel descriptors into
-                # the graph), every per-stream workspace and every lazily set function attribute exists before the capture
-                with torch.cuda.stream(s):
-                    snap = [(o, o.theta.clone(), o.m.clone(), o.v.clone(), o.step.clone()) for o in self._optimizers()]
-                    rng_snap = rng.clone() if torch.is_tensor(rng) else None
-                    self._iteration_body(kinds, self._ahead_prepare(kinds) if use_ahead else None)
-                    for o, th, m, v, st in snap:
-                        o.theta.copy_(th); o.m.copy_(m); o.v.copy_(v); o.step.copy_(st)
-                    if rng_snap is not None:
-                        rng.copy_(rng_snap)
-                torch.cuda.current_stream(self.device).wait_stream(s)
-                torch.cuda.synchronize(self.device)
-                self.site_log = F.site_log()
-                F.record_sites(False)
-                ahead = self._ahead_prepare(kinds) if use_ahead else None
-                lib.drop_taps(set(kinds))                  # (tests: only the captured graph's activations are of interest)
-                dot = os.environ.get('GGAN_GRAPH_DOT')
-                g = torch.cuda.CUDAGraph(keep_graph=True) if dot else torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, stream=s, capture_error_mode=_CAPTURE_MODE):
-                    costs, keeps = self._iteration_body(kinds, ahead)
-                if dot:
-                    _dump_graph_dot(g, dot)
-                self.site_mismatches = F.site_mismatches()
-            finally:
-                F.set_site_plan(None)
-                F.record_sites(False)
-            return dict(g=g, costs=costs, keep=keeps, kinds=tuple(kinds))
-        finally:
-            if forkable:
-                self.model.fork_now = False
+            table = self._site_plan(kinds, use_ahead)
+            # dress rehearsal: the body exactly as it will be captured -- ahead-of-time passes, site plans -- run once eagerly, so that
+            # every plan-time cache (slab tables: a launch that finds none under capture bakes the slower in-kernel descriptors into
+            # the graph), every per-stream workspace and every lazily set function attribute exists before the capture
+            with torch.cuda.stream(s), self._restored(), F.site_plan(table, record=True) as rehearsal:
+                self._iteration_body(kinds, self._ahead_prepare(kinds) if use_ahead else None)
+            cur.wait_stream(s)
+            torch.cuda.synchronize(self.device)
+            ahead = self._ahead_prepare(kinds) if use_ahead else None
+            lib.drop_taps(set(kinds))                  # (tests: only the captured graph's activations are of interest)
+            dot = os.environ.get('GGAN_GRAPH_DOT')
+            g = torch.cuda.CUDAGraph(keep_graph=True) if dot else torch.cuda.CUDAGraph()
+            with F.site_plan(table, record=True) as capture, torch.cuda.graph(g, stream=s, capture_error_mode=_CAPTURE_MODE):
+                costs, keeps = self._iteration_body(kinds, ahead)
+            if dot:
+                _dump_graph_dot(g, dot)
+        # (the launches the rehearsal prepared for are those the capture made when the two logs are equal; site_mismatches: the table's
+        #  entries the captured graph ignored because their site held another geometry)
+        self.site_log, self.capture_site_log, self.site_mismatches = rehearsal.log, capture.log, capture.mismatches
+        return dict(g=g, costs=costs, keep=keeps, kinds=tuple(kinds))
 
     def iteration(self, it, batches):
         """batches: iterator of device minibatches (or feed dicts when inject_noise); ignored in ring mode (use_ring)."""
@@ -844,23 +780,16 @@ class Trainer(object):
 
     def _iteration_ring(self, it, kinds):
         """ring mode: the steps of an iteration with nothing issued between them -- as ONE graph replay where that is possible"""
-        one_graph = (self.graph_enabled and it > 0 and (self.world == 1 or self.dp_graph) and not self.split_graph
-                     and all(self._calls[k] >= 1 for k in set(kinds)))
-        if not one_graph and getattr(self, '_as_captured', False) and it > 0 and (self.world == 1 or self.dp_graph) and not self.split_graph \
-                and all(self._calls[k] >= 1 for k in set(kinds)):
-            for k in kinds:
-                self._calls[k] += 1
-            return self._iteration_as_captured(kinds)       # (the iteration graph's launches, issued eagerly: site plans, ahead-of-time passes)
-        if not one_graph:
+        if not (it > 0 and (self.graph_enabled or getattr(self, '_as_captured', False)) and (self.world == 1 or self.dp_graph)
+                and not self.split_graph and all(self._calls[k] >= 1 for k in set(kinds))):
             return {k + '_cost': self.step(k) for k in kinds}
-        for k in kinds:
-            self._calls[k] += 1
-        if all(self._calls[k] >= 2 for k in set(kinds)):
-            lib.end_build_phase()        # (as step(): every kind has been built once)
-        rec = getattr(self, '_iter_graph', None)
+        self._count(kinds)
+        if not self.graph_enabled:
+            return self._launch_as_captured(kinds)          # (the iteration graph's launches, issued eagerly: site plans, ahead-of-time passes)
+        rec = self._iter_graph
         if rec is None or rec['kinds'] != tuple(kinds):
             self.flush()
-            rec = self._iter_graph = self._capture_iteration(kinds)
+            rec = self._iter_graph = self._capture_single(kinds)
         rec['g'].replay()
         return dict(rec['costs'])
 

@@ -105,16 +105,12 @@ class Evaluator(object):
     @contextlib.contextmanager
     def _guard(self):
         """a pass: no tape, the current stream only, the model's step-building state and numpy's RNG state as they were"""
-        m = self.model
-        saved = (m._pending_join, getattr(m, '_noise_event', None), m._early, m.fork_now, getattr(m, 'head_hint', False))
         np_state = np.random.get_state()
-        m.fork_now, m._early, m._pending_join, m.head_hint = False, False, None, False
         t0 = time.time()
         try:
-            with torch.no_grad():
+            with torch.no_grad(), self.model.single_stream():
                 yield
         finally:
-            m._pending_join, m._noise_event, m._early, m.fork_now, m.head_hint = saved
             np.random.set_state(np_state)
             self.last_seconds = time.time() - t0
 

@@ -296,8 +296,8 @@ def conv_geom(N, Ci, H, W, Co, k, stride, padding='SAME'):
 # recording thread, backward launches on autograd's worker thread for the device; the two never run at the same time and autograd's
 # order is a function of the recorded graph, so the numbering is the same in the eager rehearsal, in the capture and in the next process.
 # A site plan maps site -> (plan_wgs, plan_wgs_filter) and overrides whatever the pass-level settings say (-1 = leave that field);
-# entries carry the geometry they were made for and are ignored (counted in site_mismatches) when the site holds another one.
-_SITE = dict(scope=None, n=0, table={}, log=None, mismatches=0)
+# entries carry the geometry they were made for and are ignored (counted in site_plan.mismatches) when the site holds another one.
+_SITE = dict(scope=None, n=0, plan=None)
 
 
 class site_scope(object):
@@ -312,23 +312,22 @@ class site_scope(object):
         _SITE['scope'], _SITE['n'] = self.prev
 
 
-def set_site_plan(table):
-    """table: {'disc2:17': dict(geom=[N, Ci, H, W, Co], wgs=0, wgs_filter=-1), ...} or None"""
-    _SITE['table'] = dict(table or {})
-    _SITE['mismatches'] = 0
+class site_plan(object):
+    """with site_plan(table, record=False) as rec: the sites passed inside take the table's plans.  table: {'disc2:17': dict(geom=[N, Ci,
+    H, W, Co], wgs=0, wgs_filter=-1), ...} or None.  rec.mismatches counts the entries ignored for another geometry; rec.log (record=True)
+    lists every site passed: [(site, (N, Ci, H, W, Co, Ho, Wo), plan_wgs, plan_wgs_filter)]"""
 
+    def __init__(self, table, record=False):
+        self.table = dict(table or {})
+        self.log = [] if record else None
+        self.mismatches = 0
 
-def record_sites(on=True):
-    """start (or stop) logging every site passed: site_log() -> [(site, (N, Ci, H, W, Co, Ho, Wo), plan_wgs, plan_wgs_filter)]"""
-    _SITE['log'] = [] if on else None
+    def __enter__(self):
+        self.prev, _SITE['plan'] = _SITE['plan'], self
+        return self
 
-
-def site_log():
-    return list(_SITE['log'] or [])
-
-
-def site_mismatches():
-    return _SITE['mismatches']
+    def __exit__(self, *a):
+        _SITE['plan'] = self.prev
 
 
 def _geom(t):
@@ -336,19 +335,19 @@ def _geom(t):
     # (the hint plans the filter gradient too since round 5: with the four-wave kernel 128 workgroups x 4 chunks beat 256 x 2 beside a
     #  second chain -- headline 4.29 -> 4.17 ms)
     wgs = wgs_f = both or hint
-    scope = _SITE['scope']
-    if scope is not None:
+    scope, plan = _SITE['scope'], _SITE['plan']
+    if scope is not None and plan is not None:
         site = '%s:%d' % (scope, _SITE['n'])
         _SITE['n'] += 1
-        ov = _SITE['table'].get(site)
+        ov = plan.table.get(site)
         if ov is not None:
             if list(ov.get('geom', t[:5])) != [int(v) for v in t[:5]]:
-                _SITE['mismatches'] += 1
+                plan.mismatches += 1
             else:
                 wgs = ov['wgs'] if ov.get('wgs', -1) >= 0 else wgs
                 wgs_f = ov['wgs_filter'] if ov.get('wgs_filter', -1) >= 0 else wgs_f
-        if _SITE['log'] is not None:
-            _SITE['log'].append((site, tuple(int(v) for v in t[:7]), int(wgs), int(wgs_f)))
+        if plan.log is not None:
+            plan.log.append((site, tuple(int(v) for v in t[:7]), int(wgs), int(wgs_f)))
     return ConvGeom(*(tuple(t[:11]) + (wgs, wgs_f, _lib.PLAN_PLAIN if _PLAIN[0] else 0)))
 
 

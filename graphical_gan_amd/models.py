@@ -88,6 +88,7 @@ class GraphicalGAN(object):
         self._side = None                                     # second stream of forward_nets
         self._early = False                                   # begin_nets() forked it before the noise launch
         self._pending_join = None                             # [stream, event after real_x, event at the branch's end]
+        self._noise_event = None                              # recorded behind the noise launch of an early fork
         self._gp_stream = None                                # the stream the gradient-penalty pass of a wali-gp critic step was issued on
         # two-stream Extractor / Generator passes: measured +3 % (ali, face, mnist), -5..7 % with the gradient penalty (more
         # cross-stream edges than overlap), so the joint-critic modes without a penalty ask for it; the Trainer
@@ -96,6 +97,19 @@ class GraphicalGAN(object):
         #  launch and an immediate join, +1.3 % once the Extractor branch is a root of the graph and carries the critic's z path)
         self.fork_nets = cfg.mode in ('ali', 'alice', 'alice-z', 'alice-x', 'wali', 'wali-gp', 'local_ep', 'local_epce')
         self.fork_now = False
+        self.head_hint = False                                # (engine.Trainer._forward)
+
+    @contextlib.contextmanager
+    def single_stream(self):
+        """a pass built on the current stream alone in the middle of a step that may be building its two-stream passes (engine.Trainer's
+        nets passes ahead of time, evaluate.Evaluator): no fork, no early fork, no pending join, no critic-head hint -- the step's
+        two-stream state is set aside and put back afterwards"""
+        saved = (self._pending_join, self._noise_event, self._early, self.fork_now, self.head_hint)
+        self.fork_now, self._early, self._pending_join, self.head_hint = False, False, None, False
+        try:
+            yield
+        finally:
+            self._pending_join, self._noise_event, self._early, self.fork_now, self.head_hint = saved
 
     # ---- engine hooks: the static inputs of one session.run (what the reference feeds / samples) -----------------
     @property
@@ -106,7 +120,7 @@ class GraphicalGAN(object):
         return bool(self.cfg.batch_critic) and self.cfg.mode in ('ali', 'local_ep', 'wali', 'wali-gp')
 
     def launch_hint(self, which):
-        """workgroups per conv launch the step should plan for (engine.Trainer._step_body -> functional.launch_hint -> ggan_conv_geom.plan_wgs), 0 = default:
+        """workgroups per conv launch the step should plan for (engine.Trainer._iteration_body -> functional.launch_hint -> ggan_conv_geom.plan_wgs), 0 = default:
         128 in wali-gp critic steps while a step graph is built -- there the penalty pass runs beside the [fake; real] pass, and launches
         of ~128 workgroups let the two chains run on different CUs (measured -1 % of the iteration even with the generator step, which
         wants the default, planned the same way)"""

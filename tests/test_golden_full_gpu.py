@@ -223,7 +223,7 @@ def test_full_size_timed_configuration_vs_fixture(gpu, name):
     tr.load_params(P0)
     tr.set_feed(feed)
     tr.flush()
-    tr._graphs, tr._iter_graph = {}, None    # (the critic step's second call captured its graph with the learning rate it had then)
+    tr.drop_graphs()                         # (the critic step's second call captured its graph with the learning rate it had then)
     ring = dataset != 'mnist'
     if ring:
         x = torch.as_tensor(np.ascontiguousarray(feed['real_x_int'])).to(gpu)
@@ -240,8 +240,12 @@ def test_full_size_timed_configuration_vs_fixture(gpu, name):
     if ring:
         assert getattr(tr, '_iter_graph', None) is not None and tr._iter_graph['kinds'] == ('gen',) + ('disc',) * cfg.critic_iters
         assert tr.model.fork_nets            # (the two-stream nets pass and its 128-workgroup plans were on while the graph was built)
+        assert tr.site_log
     else:
         assert set(tr._graphs) == {'gen', 'disc'}        # (one captured graph per step kind, replayed by the last iterations)
+    # the dress rehearsal in front of the last capture passed the launch sites that capture passed, with the same geometries and plans: the
+    # plan-time caches it made are those of the captured launches
+    assert tr.site_log == tr.capture_site_log
     torch.cuda.synchronize()
     for which in ('gen', 'disc'):
         ref = float(z[which + '/cost'])
@@ -322,7 +326,7 @@ def test_full_size_ssgan_first_step_vs_fixture(gpu, timed):
             o.lr = 0.0
         tr.load_params(P0)
         tr.flush()
-        tr._graphs, tr._iter_graph = {}, None
+        tr.drop_graphs()
         res = None
         lib.TAPS[0] = []
         for it in (2, 3, 4):

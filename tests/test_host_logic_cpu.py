@@ -107,6 +107,23 @@ def test_same_padding_table():
     assert g == (64, 3, 32, 32, 64, 16, 16, 5, 2, 1, 1)
 
 
+def test_site_plan_scope():
+    """functional.site_plan: a table entry plans its site's launch when the geometry matches and is counted as a mismatch when it does
+    not; the log lists every site passed; outside the scope (or outside a site_scope) the pass-level plan stands"""
+    from graphical_gan_amd import functional as F
+    g1, g2 = F.conv_geom(8, 3, 32, 32, 64, 5, 2), F.conv_geom(8, 64, 16, 16, 128, 5, 2)
+    table = {'disc0:0': dict(geom=list(g1[:5]), wgs=96, wgs_filter=-1), 'disc0:1': dict(geom=list(g1[:5]), wgs=0, wgs_filter=0)}
+    with F.launch_hint(128):
+        with F.site_plan(table, record=True) as rec, F.site_scope('disc0'):
+            a, b = F._geom(g1), F._geom(g2)
+        assert (a.plan_wgs, a.plan_wgs_filter, b.plan_wgs, b.plan_wgs_filter) == (96, 128, 128, 128)
+        assert rec.mismatches == 1 and rec.log == [('disc0:0', tuple(g1[:7]), 96, 128), ('disc0:1', tuple(g2[:7]), 128, 128)]
+        with F.site_scope('disc0'):
+            assert F._geom(g1).plan_wgs == 128
+        with F.site_plan(table) as rec:
+            assert F._geom(g1).plan_wgs == 128 and rec.log is None
+
+
 def test_flat_layout_is_aligned():
     from graphical_gan_amd.optim import layout_slots
     slots, total = layout_slots([5, 64, 100, 1])

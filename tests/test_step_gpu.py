@@ -663,6 +663,25 @@ def test_cross_replica_batchnorm_inside_the_step_graph_one_rank_rehearsal(gpu):
     assert sums[0] == sums[1], sums
 
 
+def test_plain_trainer_after_a_cross_replica_batchnorm_one(gpu):
+    """A Trainer built without sync_bn after one built with it, in one process (one rank over RCCL): its BatchNorm layers take per-replica
+    statistics again -- the statistics mode used to outlive the sync_bn Trainer, and the plain Trainer's captured steps then gathered
+    statistics with host-issued collectives.  Same weights, bit for bit, as the plain Trainer in a process of its own."""
+    import os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sums = []
+    for i, extra in enumerate((dict(), dict(CHECK_AFTER_SYNC_BN='1'))):
+        env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0', GGAN_FORCE_ALLREDUCE='1', **extra)
+        r = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr',
+                            '127.0.0.1', '--master-port', str(29500 + (os.getpid() % 100) + i), os.path.join(root, 'tools', 'dp_one_rank_check.py'),
+                            'ali', '0'], capture_output=True, text=True, timeout=600, env=env, cwd=root)
+        line = [l for l in r.stdout.splitlines() if l.startswith('CHECK')]
+        assert r.returncode == 0 and line, (r.stdout[-500:], r.stderr[-2000:])
+        assert 'dp_graph=True one_graph=True sync_bn=False' in line[0], line[0]
+        sums.append(line[0].split()[-1])
+    assert sums[0] == sums[1], sums
+
+
 @pytest.mark.parametrize('mode,K', [('ali', 0), ('local_ep', 30)])
 def test_full_size_training_is_bitwise_reproducible(gpu, mode, K):
     """BASELINE-size step (batch 64, HIP-graph replay, two-stream nets pass for ali, on-device noise): two runs from the same

@@ -54,14 +54,12 @@ def main():
     for _ in range(2):
         tr.iteration(it, bi); it += 1
     tr.use_ring(ring)
-    tr.record_site_log = True
     tr.site_plan_override = {}
 
     def timed(table, iters=args.iters):
         nonlocal it
         tr.site_plan_override = dict(table)
-        tr._iter_graph = None
-        tr._graphs = {}
+        tr.drop_graphs()
         gc.collect()
         for _ in range(3):
             tr.iteration(it, bi); it += 1
