@@ -78,6 +78,7 @@ SIGNATURES = {
     'ggan_gmm_latent_st_bwd': (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _I, _P]),
     'ggan_gmm_posterior_assign': (_I, [_P, _P, _F, _I, _I, _I, _I, _P, _P, _P, _P]),
     'ggan_cluster_accuracy': (_I, [_P, _P, _P, _I, _I, _P, _P]),
+    'ggan_video_sheet_u8': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _F, _F, _P]),
     'ggan_gemm_split': (_I, [_I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _I, _P, _I, _F, _P, _Z, _P]),
     'ggan_gemm_colsum': (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
     'ggan_dyn_scan_fwd': (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P]),

@@ -15,7 +15,19 @@ are never written -- and with numpy's global RNG state restored afterwards (the 
 consume it; the training data order must not depend on whether evaluation is on).  BatchNorm uses the statistics of each evaluation
 minibatch, as the reference's graph does (tflib/ops/batchnorm.py: the scripts pass no is_training).
 
-`python -m graphical_gan_amd.evaluate CKPT --script gmgan_inference_mnist [--data-dir DIR]` scores a saved checkpoint."""
+The state-space scripts have no dev cost; their passes are pictures (ssgan_inference_moving_mnist.py:568-618, ssgan_inference_chairs.py:560-606),
+run by SequenceEvaluator on a models_ssgan.StateSpaceGAN under the same rules:
+
+  samples            generate_video: Generator(fixed_noise_g, DynamicGenerator(pre_fixed_noise), fixed_y), N_VIS = BATCH_SIZE sequences, a
+                     fresh epsilon per call; written beside the last training minibatch (samples_<it>, train_data_<it>);
+  reconstructions    reconstruct_video: rec_x = Generator(q_z_g, q_z_l, real_y) on a fixed dev minibatch (reconstruction_<it>);
+  disentangle        dis_x = Generator(dis_g, q_z_l, dis_y): ONE global code for every sequence (and class 1 for moving-MNIST) with the
+                     per-frame codes extracted from a fixed dev minibatch (disentangle_<it>).
+
+Each is written as a .png sheet (one sequence per row) and a looping .gif; the bytes of both come from one ggan_video_sheet_u8 launch.
+
+`python -m graphical_gan_amd.evaluate CKPT --script gmgan_inference_mnist [--data-dir DIR]` scores a saved checkpoint;
+`... CKPT --script ssgan_inference_moving_mnist|ssgan_inference_chairs [--data-dir DIR] --out-dir DIR` writes the four pairs of files."""
 import argparse
 import contextlib
 import os
@@ -79,7 +91,24 @@ def _split(b):
     return b, None
 
 
-class Evaluator(object):
+class _Passes(object):
+    """what the image and the sequence evaluator share: the guard every pass runs under"""
+    last_seconds = 0.0            # wall time of the last pass (device work included)
+
+    @contextlib.contextmanager
+    def _guard(self):
+        """a pass: no tape, the current stream only, the model's step-building state and numpy's RNG state as they were"""
+        np_state = np.random.get_state()
+        t0 = time.time()
+        try:
+            with torch.no_grad(), self.model.single_stream():
+                yield
+        finally:
+            np.random.set_state(np_state)
+            self.last_seconds = time.time() - t0
+
+
+class Evaluator(_Passes):
     def __init__(self, trainer, settings, keep_noise=False):
         """trainer: an engine.Trainer of an image script (models.GraphicalGAN); settings: the script's UPPERCASE block (BATCH_SIZE, MODE,
         N_VIS, N_COMS, SEED).  keep_noise (tests): dev_costs keeps the noise it drew per batch in self.kept."""
@@ -102,18 +131,6 @@ class Evaluator(object):
         self.last_seconds = 0.0           # wall time of the last pass (device work included)
 
     # ---- plumbing ------------------------------------------------------------------------------------------------------------------
-    @contextlib.contextmanager
-    def _guard(self):
-        """a pass: no tape, the current stream only, the model's step-building state and numpy's RNG state as they were"""
-        np_state = np.random.get_state()
-        t0 = time.time()
-        try:
-            with torch.no_grad(), self.model.single_stream():
-                yield
-        finally:
-            np.random.set_state(np_state)
-            self.last_seconds = time.time() - t0
-
     def _stage(self, batches, want_labels=False):
         """minibatches (host arrays or device tensors, optionally (images, labels) tuples) -> (device [n, B, D] in the placeholder's
         dtype, device int32 labels [n*B] or None).  One upload per pass; a trailing partial minibatch is dropped, as the loaders do."""
@@ -252,6 +269,166 @@ class Evaluator(object):
         return paths
 
 
+# ---- the state-space scripts' video passes ---------------------------------------------------------------------------------------------
+VIDEO_NAMES = ('samples', 'train_data', 'reconstruction', 'disentangle')
+
+
+def pixel_maps(dataset):
+    """(a, b, d) of ggan_video_sheet_u8: generated frames q = trunc(((x + 1) * a) * b), data q = trunc(x * d).
+    chairs: int((x + 1) * (255.99 / 2)) (ssgan_inference_chairs.py:577), data the loader's 0..255 values.
+    moving-MNIST: u = (x + 1) / 2 then save_images' uint8(255.99 * u) (:595), data in [0, 1] through the same uint8(255.99 * u); the
+    script's (x + 1) * 2. of generate_video / disentangle (:586,:612) is NOT reproduced."""
+    if dataset == 'chairs':
+        return 255.99 / 2, 1.0, 1.0
+    return 0.5, 255.99, 255.99
+
+
+def host_sheet(gen, data, shape, maps, interleave=False):
+    """the bytes ggan_video_sheet_u8 produces, on the host in numpy float32 in the written order (the old way: floats downloaded,
+    large_image's tiling loop) -> (sheet [rows*H, LEN*W, C], index planes [LEN, nh*H, nw*W])"""
+    a, b, d = (np.float32(v) for v in maps)
+    q = lambda v: np.clip(np.trunc(v), 0, 255).astype(np.uint8)
+    parts = []
+    if data is not None:
+        parts.append(q(np.asarray(data, np.float32) * d))
+    if gen is not None:
+        parts.append(q(((np.asarray(gen, np.float32) + np.float32(1)) * a) * b))
+    n, LEN = parts[0].shape[:2]
+    if interleave:
+        x = np.empty((2 * n, LEN) + tuple(shape), np.uint8)
+        x[0::2], x[1::2] = parts[0].reshape((n, LEN) + tuple(shape)), parts[1].reshape((n, LEN) + tuple(shape))
+    else:
+        assert len(parts) == 1
+        x = parts[0].reshape((n, LEN) + tuple(shape))
+    rows = x.shape[0]
+    sheet = lib.save_images.large_image(x.reshape((-1,) + tuple(shape)), size=(rows, LEN))
+    planes, _ = lib.save_images.gif_planes(x)
+    return sheet, planes
+
+
+class SequenceEvaluator(_Passes):
+    def __init__(self, trainer, settings):
+        """trainer: an engine.Trainer of a state-space script (models_ssgan.StateSpaceGAN); settings: the script's UPPERCASE block
+        (BATCH_SIZE, N_VIS, SEED).  The fixed inputs are drawn once, in the reference's order, from a generator of the evaluator's own."""
+        self.tr, self.S = trainer, settings
+        self.model, self.cfg, self.device = trainer.model, trainer.cfg, trainer.device
+        c = self.cfg
+        seed = int(settings.get('SEED', 0)) + EVAL_SEED
+        n_vis = int(settings.get('N_VIS', c.B))
+        # (the nets are built for BATCH_SIZE sequences: N_VIS = BATCH_SIZE, ssgan_inference_moving_mnist.py:55)
+        assert n_vis == c.B, 'N_VIS must be BATCH_SIZE'
+        assert not c.n_c or n_vis % c.n_c == 0, 'N_VIS must be a multiple of N_C (ssgan_inference_moving_mnist.py:56)'
+        self.feed = self.model.feed_buffers(self.device)
+        self.feed['rng_state'] = F.noise_state(self.device, seed)
+        rng = np.random.RandomState(seed)
+        up = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).to(self.device)
+        self.pre_fixed_noise = up(rng.normal(size=(n_vis, c.dim_l)))                                    # :579
+        self.fixed_y = up(np.tile(np.eye(c.n_c), (n_vis // c.n_c, 1)) if c.n_c else np.zeros((n_vis, 0)))        # :580
+        self.fixed_noise_g = up(rng.normal(size=(n_vis, c.dim_g)))                                      # :581
+        dis_y = np.zeros((c.B, c.n_c))
+        if c.n_c:
+            dis_y[:, 1] = 1                                                                               # :607 class 1 for every row
+        self.dis_y = up(dis_y)
+        self.dis_g = up(np.tile(rng.normal(size=(1, c.dim_g)), (c.B, 1)))                               # :608
+        self.rec_data = self.dis_data = None          # the fixed dev minibatches (device: (x [B, LEN, D], one-hot y [B, N_C]))
+        self.timing = {}                              # seconds of the last save_videos: device / download / encode
+
+    # ---- plumbing ------------------------------------------------------------------------------------------------------------------
+    def _batch(self, batch):
+        """a loader minibatch (x, or (x, labels), labels as class numbers or one-hot rows; host or device) -> device (x, one-hot y)"""
+        c = self.cfg
+        x, y = _split(batch)
+        x = (x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x, dtype=np.float32))).to(self.device, torch.float32)
+        x = x.reshape(c.B, c.LEN, c.output_dim).clone()
+        oh = torch.zeros((c.B, c.n_c), dtype=torch.float32, device=self.device)
+        if c.n_c:
+            if y is None:
+                raise ValueError('the moving-MNIST passes need labelled minibatches')
+            y = y if torch.is_tensor(y) else torch.as_tensor(np.asarray(y))
+            if y.dim() == 2:
+                oh.copy_(y.to(self.device, torch.float32))
+            else:
+                oh[torch.arange(c.B, device=self.device), y.to(self.device, torch.int64)] = 1
+        return x, oh
+
+    def set_fixed_data(self, rec_batch, dis_batch=None):
+        """the reconstruction minibatch and the disentangling one (each the first minibatch of a fresh dev generator, :591,:605)"""
+        self.rec_data = self._batch(rec_batch)
+        self.dis_data = self._batch(dis_batch) if dis_batch is not None else self.rec_data
+
+    def _extract(self, data):
+        """(real_y, q_z_g, q_z_l) of a fixed minibatch (:514-518), through the evaluator's own feed"""
+        m = self.model
+        m.set_batch(self.feed, data)
+        u = self.feed['real_x_unit']
+        real_x = F.Axpby.apply(u, u, 2.0 / self.cfg.x_div, 0.0, -1.0)                                  # 2*(x/div-.5)
+        real_y = self.feed['real_y']
+        return real_y, m.G_Extractor(real_x, real_y), m.DynamicExtractor(m.Extractor(real_x, real_y))
+
+    # ---- the passes: device tensors [B, LEN, OUTPUT_DIM] in the generator's range -----------------------------------------------------
+    def samples(self):
+        """fixed_noise_samples (:582-583); epsilon is drawn anew on every call (:137) and stays in self.feed['epsilon']"""
+        with self._guard():
+            F.noise_fill_(self.feed['rng_state'], [(self.feed['epsilon'], F.NOISE_NORMAL, 0., 1.)])
+            z_l = self.model.DynamicGenerator(self.pre_fixed_noise, self.feed['epsilon'])
+            return self.model.Generator(self.fixed_noise_g, z_l, self.fixed_y)
+
+    def reconstructions(self, batch=None):
+        """rec_x = Generator(q_z_g, q_z_l, real_y) on the fixed minibatch (:519,:594)"""
+        data = self._batch(batch) if batch is not None else self.rec_data
+        assert data is not None, 'no reconstruction minibatch: pass one or call set_fixed_data'
+        with self._guard():
+            real_y, q_z_g, q_z_l = self._extract(data)
+            return self.model.Generator(q_z_g, q_z_l, real_y)
+
+    def disentangle(self, batch=None):
+        """dis_x = Generator(dis_g, q_z_l, dis_y) (:609): one global code, the fixed minibatch's per-frame codes"""
+        data = self._batch(batch) if batch is not None else self.dis_data
+        assert data is not None, 'no disentangling minibatch: pass one or call set_fixed_data'
+        with self._guard():
+            _, _, q_z_l = self._extract(data)
+            return self.model.Generator(self.dis_g, q_z_l, self.dis_y)
+
+    # ---- files ---------------------------------------------------------------------------------------------------------------------
+    def sheets(self, train_data=None):
+        """{name: (sheet bytes, index planes)} on the device for the passes' files: one ggan_video_sheet_u8 launch each"""
+        c = self.cfg
+        shape, (a, b, d) = (c.C, c.S, c.S), pixel_maps(c.dataset)
+        out = {}
+        out['samples'] = F.video_sheet_u8(self.samples(), None, shape, a, b, d)
+        if train_data is not None:
+            x = _split(train_data)[0]
+            out['train_data'] = F.video_sheet_u8(None, x.to(self.device, torch.float32).reshape(c.B, c.LEN, c.output_dim), shape, a, b, d)
+        if self.rec_data is not None:
+            out['reconstruction'] = F.video_sheet_u8(self.reconstructions(), self.rec_data[0], shape, a, b, d, interleave=True)
+            out['disentangle'] = F.video_sheet_u8(self.disentangle(), self.dis_data[0], shape, a, b, d, interleave=True)
+        return out
+
+    def save_videos(self, out_dir, frame, train_data=None):
+        """writes <name>_<frame>.png / .gif for samples, train_data (the minibatch handed in), reconstruction and disentangle; returns
+        the paths.  Only the byte tensors are downloaded; self.timing splits the wall time into device / download / encode seconds."""
+        S = lib.save_images
+        t0 = time.time()
+        dev = self.sheets(train_data)
+        if self.device.type == 'cuda':
+            torch.cuda.synchronize(self.device)
+        t1 = time.time()
+        host = {k: (s.cpu().numpy(), g.cpu().numpy()) for k, (s, g) in dev.items()}
+        t2 = time.time()
+        palette = S.grey_palette() if self.cfg.C == 1 else S.cube_palette()
+        paths = []
+        for name in VIDEO_NAMES:
+            if name not in host:
+                continue
+            sheet, planes = host[name]
+            stem = os.path.join(out_dir, '%s_%s' % (name, frame))
+            S.write_png(stem + '.png', sheet)
+            S.write_gif(stem + '.gif', planes, palette)
+            paths += [stem + '.png', stem + '.gif']
+        self.timing = dict(device=t1 - t0, download=t2 - t1, encode=time.time() - t2)
+        return paths
+
+
 # ---- command line: score a saved checkpoint ----------------------------------------------------------------------------------------
 def main(argv=None):
     """builds the script's model, restores the checkpoint's weights, runs the evaluation passes once and prints them"""
@@ -259,10 +436,10 @@ def main(argv=None):
     from .engine import Trainer
     ap = argparse.ArgumentParser(prog='python -m graphical_gan_amd.evaluate', description=main.__doc__)
     ap.add_argument('ckpt', help='a params_<it>.npz written by run.train / checkpoint.save')
-    ap.add_argument('--script', required=True, help='the image script the checkpoint was trained with, e.g. gmgan_inference_mnist')
+    ap.add_argument('--script', required=True, help='the script the checkpoint was trained with, e.g. gmgan_inference_mnist or ssgan_inference_chairs')
     ap.add_argument('--data-dir', default=os.environ.get('GGAN_DATA_DIR', ''))
     ap.add_argument('--mode', default=None, help="the script's MODE (default: the script's own)")
-    ap.add_argument('--out-dir', default=None, help='also write the sample grid and the reconstructions here')
+    ap.add_argument('--out-dir', default=None, help='also write the sample grid and the reconstructions here (the state-space scripts: the video files, required)')
     ap.add_argument('--set', action='append', default=[], metavar='KEY=VALUE', help='override an UPPERCASE setting (int / float / str)')
     a = ap.parse_args(argv)
     over = {}
@@ -279,7 +456,13 @@ def main(argv=None):
         over['MODE'] = a.mode
     S = run.reference_block(a.script, **over)
     S.update(DATA_DIR=a.data_dir, SCRIPT=a.script)
-    tr = Trainer(run.config(S), device=lib.get_device(), graph=False)
+    cfg, model = run.config(S), None
+    if S['DATASET'] in run.SEQUENCE_DATASETS:
+        from .models_ssgan import StateSpaceGAN
+        if not a.out_dir:
+            ap.error('--out-dir is required for %s: its passes are files' % a.script)
+        model = StateSpaceGAN(cfg)
+    tr = Trainer(cfg, device=lib.get_device(), graph=False, model=model)
     checkpoint.restore(a.ckpt, tr)
     res = evaluate_once(tr, S, out_dir=a.out_dir)
     for k in sorted(res):
@@ -290,6 +473,12 @@ def main(argv=None):
 def evaluate_once(tr, S, out_dir=None, frame='eval'):
     """every pass the script's data allow, once -> {name: value}"""
     from . import run
+    if S['DATASET'] in run.SEQUENCE_DATASETS:       # the video passes: files only (train_data: the first dev minibatch)
+        ev = SequenceEvaluator(tr, S)
+        dev, _ = run.eval_sets(S, tr.model, tr.device)
+        ev.set_fixed_data(dev[0])
+        os.makedirs(out_dir, exist_ok=True)
+        return {'files': ' '.join(os.path.basename(p) for p in ev.save_videos(out_dir, frame, train_data=dev[0]))}
     ev = Evaluator(tr, S)
     dev, test = run.eval_sets(S, tr.model, tr.device)
     res = dict(ev.dev_costs(dev))

@@ -392,3 +392,37 @@ def cluster_accuracy_(assign, labels, colbest, correct):
     assert correct.dtype == torch.int32 and correct.numel() >= 1 and K <= POSTERIOR_MAX_K
     check(_L().ggan_cluster_accuracy(_p(assign), _p(labels), _p(colbest), N, K, _p(correct), _stream()), 'ggan_cluster_accuracy')
     return correct
+
+
+def sheet_grid(rows):
+    """(nh, nw) of tflib.save_images.large_image's size=None rule: nh the largest divisor of the sample count not above its square root"""
+    nh = int(rows ** 0.5)
+    while (nh + 1) * (nh + 1) <= rows:
+        nh += 1
+    while nh * nh > rows:
+        nh -= 1
+    while rows % nh:
+        nh -= 1
+    return nh, rows // nh
+
+
+def video_sheet_u8(gen, data, shape, a=0.5, b=255.99, d=255.99, interleave=False):
+    """The two byte tensors of one video sheet in ONE launch (ggan_video_sheet_u8; ssgan_inference_moving_mnist.py:568-576 vis):
+    gen [n, LEN, C*H*W] generated frames in [-1, 1] or None, data [n, LEN, C*H*W] as the feed holds it or None, shape = (C, H, W);
+    interleave: rows alternate data / generated.  q = trunc(((x + 1) * a) * b) for generated, trunc(x * d) for data values, clamped to
+    0..255.  -> (sheet uint8 [rows*H, LEN*W, C], index planes uint8 [LEN, nh*H, nw*W]) on the device."""
+    C_, H, W = (int(v) for v in shape)
+    src = gen if gen is not None else data
+    if src is None:
+        raise _lib.GganError('video_sheet_u8 needs generated frames or data')
+    gen, data = (_c(gen) if gen is not None else None), (_c(data) if data is not None else None)
+    n, LEN = int(src.shape[0]), int(src.shape[1])
+    for t in (gen, data):
+        assert t is None or (t.numel() == n * LEN * C_ * H * W and t.shape[0] == n and t.shape[1] == LEN), (t.shape, n, LEN, shape)
+    rows = 2 * n if interleave else n
+    nh, nw = sheet_grid(rows)
+    sheet = torch.empty((rows * H, LEN * W, C_), dtype=torch.uint8, device=src.device)
+    gif = torch.empty((LEN, nh * H, nw * W), dtype=torch.uint8, device=src.device)
+    check(_L().ggan_video_sheet_u8(_p(gen), _p(data), _p(sheet), _p(gif), n, rows, LEN, C_, H, W, nh, nw, 1 if interleave else 0,
+                                   float(a), float(b), float(d), _stream()), 'ggan_video_sheet_u8')
+    return sheet, gif

@@ -18,6 +18,8 @@ What is done differently from a literal transcription (same arithmetic):
     activation is the BatchNorm's epilogue.
 """
 
+import contextlib
+
 import numpy as np
 import torch
 
@@ -80,6 +82,16 @@ class StateSpaceGAN(object):
         self._side = None
         self.fork_nets = True
         self.fork_now = False
+
+    @contextlib.contextmanager
+    def single_stream(self):
+        """a pass built on the current stream alone in the middle of a step that may be building its two-stream passes
+        (evaluate.SequenceEvaluator): no fork onto the second stream -- the step's state is set aside and put back afterwards"""
+        saved, self.fork_now = self.fork_now, False
+        try:
+            yield
+        finally:
+            self.fork_now = saved
 
     # ---- engine hooks: static inputs of one session.run ---------------------------------------------------------------
     def feed_buffers(self, device):

@@ -63,6 +63,7 @@ def _batches(S, model, device):
 
 # ---- the evaluation passes of the reference's driver loops (evaluate.py) ------------------------------------------------------------
 EVAL_KEYS = ('DEV_EVERY', 'ACCURACY_EVERY', 'SAMPLE_EVERY')
+SEQUENCE_DATASETS = ('moving_mnist', 'chairs')         # the state-space scripts: evaluate.SequenceEvaluator
 
 
 def eval_plan(S):
@@ -78,12 +79,15 @@ def eval_due(plan, it):
 
 def eval_settings(script):
     """the cadence the reference's image script runs its passes at (dev costs every 100 iterations; samples / reconstructions every
-    5000; the testing accuracy every 5000, gmgan_inference_mnist only), each overridable by $GGAN_<KEY> (e.g. GGAN_DEV_EVERY=10)"""
+    5000; the testing accuracy every 5000, gmgan_inference_mnist only), each overridable by $GGAN_<KEY> (e.g. GGAN_DEV_EVERY=10).
+    The state-space scripts have only the video passes, every 5000 iterations (ssgan_inference_moving_mnist.py:673-677): SAMPLE_EVERY
+    / $GGAN_SAMPLE_EVERY alone."""
     name = os.path.splitext(os.path.basename(script))[0]
-    S = dict(DEV_EVERY=100, SAMPLE_EVERY=5000, SCRIPT=name)
+    sequences = name in _SEQUENCE_SCRIPTS
+    S = dict(SAMPLE_EVERY=5000, SCRIPT=name) if sequences else dict(DEV_EVERY=100, SAMPLE_EVERY=5000, SCRIPT=name)
     if name == 'gmgan_inference_mnist':
         S['ACCURACY_EVERY'] = 5000
-    for k in EVAL_KEYS:
+    for k in (('SAMPLE_EVERY',) if sequences else EVAL_KEYS):
         if os.environ.get('GGAN_' + k):
             S[k] = int(os.environ['GGAN_' + k])
     return S
@@ -91,7 +95,8 @@ def eval_settings(script):
 
 def eval_sets(S, model, device):
     """(dev minibatches, labelled test minibatches or None) for the evaluation passes: tflib.mnist.load's dev and test generators, the
-    test split of the CIFAR-10 / SVHN loaders, celebA's dev split -- or, without the dataset, a synthetic dev set of the training ring's
+    test split of the CIFAR-10 / SVHN loaders, celebA's dev split, the dev split of the moving-MNIST / chairs loaders (the FIRST
+    minibatch only: the video passes use nothing else) -- or, without the dataset, a synthetic dev set of the training ring's
     shapes and no test set.  Host lists of one epoch each; numpy's global RNG state (which the loaders' shuffles consume) is restored."""
     ds, B = S['DATASET'], S['BATCH_SIZE']
     state = np.random.get_state()
@@ -108,6 +113,12 @@ def eval_sets(S, model, device):
         if ds == 'face':
             _, dev = lib.celebA.load(B, S.get('DATA_DIR', ''))
             return list(dev()), None
+        if ds == 'moving_mnist':
+            _, dev = lib.simple_moving_mnist.load_video(S['LEN'], B)
+            return [next(iter(dev()))], None
+        if ds == 'chairs':
+            _, dev = lib.chairs.load(S['LEN'], B, 64, S.get('DATA_DIR', ''))
+            return [next(iter(dev()))], None
         raise ValueError('no evaluation passes for dataset %r' % ds)
     except FileNotFoundError:
         return [t for t in model.synthetic_ring(device, n=8, seed=4321)], None
@@ -248,8 +259,14 @@ def train(S, cfg, model=None, out_dir=None):
     plan = eval_plan(S)
     evaluator = None
     if plan and (tr.world == 1 or torch.distributed.get_rank() == 0):     # (replicas: rank 0 evaluates and logs)
-        from .evaluate import Evaluator
-        evaluator = Evaluator(tr, S)
+        from .evaluate import Evaluator, SequenceEvaluator
+        from .models_ssgan import StateSpaceGAN
+        sequences = isinstance(tr.model, StateSpaceGAN)
+        if sequences and not out_dir:
+            print('[run] video passes skipped: no OUT_DIR to write them to')
+            plan = None
+    if plan and (tr.world == 1 or torch.distributed.get_rank() == 0):
+        evaluator = (SequenceEvaluator if sequences else Evaluator)(tr, S)
         ev_dev, ev_test = eval_sets(S, tr.model, device)
         evaluator.set_fixed_data(ev_dev[0])
         if 'ACCURACY_EVERY' in plan and (ev_test is None or not tr.cfg.K):
@@ -276,7 +293,7 @@ def train(S, cfg, model=None, out_dir=None):
             lib.plot.flush(out_dir, os.path.join(out_dir, 'logfile.txt') if out_dir else None)
         due = eval_due(plan, it) if evaluator is not None else ()
         if due:
-            eval_ms += _evaluate(evaluator, due, ev_dev, ev_test, it, out_dir, device)
+            eval_ms += _evaluate(evaluator, due, ev_dev, ev_test, it, out_dir, device, tr)
             lib.plot.flush(out_dir, os.path.join(out_dir, 'logfile.txt') if out_dir else None)
         lib.plot.tick()
         if out_dir and S.get('SAVE_EVERY') and (it + 1) % S['SAVE_EVERY'] == 0:
@@ -295,8 +312,9 @@ def train(S, cfg, model=None, out_dir=None):
     return tr
 
 
-def _evaluate(ev, due, dev, test, it, out_dir, device):
+def _evaluate(ev, due, dev, test, it, out_dir, device, tr=None):
     """the passes due after iteration `it`, logged through lib.plot under the reference's names -> milliseconds they took"""
+    from .evaluate import SequenceEvaluator
     if device.type == 'cuda':
         torch.cuda.synchronize(device)          # (the training work queued so far is not the passes' time)
     t0 = time.time()
@@ -306,7 +324,11 @@ def _evaluate(ev, due, dev, test, it, out_dir, device):
     if 'ACCURACY_EVERY' in due:
         lib.plot.plot('testing accuracy', ev.cluster_accuracy(test))
     if 'SAMPLE_EVERY' in due and out_dir:
-        ev.save_images(out_dir, it)
+        if isinstance(ev, SequenceEvaluator):
+            # generate_video(iteration, _data): the minibatch of the last critic step, still in the Trainer's feed buffer (read only)
+            ev.save_videos(out_dir, it, train_data=tr.feed['real_x_unit'])
+        else:
+            ev.save_images(out_dir, it)
     if device.type == 'cuda':
         torch.cuda.synchronize(device)
     return (time.time() - t0) * 1e3

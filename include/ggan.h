@@ -469,6 +469,19 @@ int ggan_gmm_posterior_assign(const float* z, const float* mu, float log_pi, int
                               int32_t* assign, uint64_t* colbest, ggan_stream_t stream);
 int ggan_cluster_accuracy(const int32_t* assign, const int32_t* labels, const uint64_t* colbest, int N, int K, int32_t* correct,
                           ggan_stream_t stream);
+/* The frame sheets of the state-space scripts' video passes (ssgan_inference_moving_mnist.py:568-618 vis / generate_video /
+ * reconstruct_video / disentangle), one launch per sheet, each pixel read once:
+ *   gen  [n, LEN, C, H, W] generated frames in [-1, 1]: q = trunc(((x + 1) * a) * b), each product rounded to float32 on its own;
+ *   data [n, LEN, C*H*W] sequences as the feed holds them (real_x_unit): q = trunc(x * d); q clamped to 0..255.
+ *   Sources: gen alone, data alone, or both with interleave != 0 (sheet row 2i = data i, row 2i + 1 = generated i);
+ *   rows = n, or 2n when interleaved.
+ *   sheet [rows*H, LEN*W, C] bytes: save_images(x, size=(rows, LEN)), row r the LEN frames of sequence r;
+ *   gif   [LEN, nh*H, nw*W] palette indices: frame t tiles sequence r at cell (r / nw, r % nw), nh * nw = rows; the index is the grey byte
+ *   (C = 1) or 36 r6 + 6 g6 + b6 of the 6x6x6 colour cube, r6 = (5 r + 127) / 255 in integers (C = 3).
+ * C is 1 or 3, W a multiple of 4, gen / data 16-byte aligned, sheet / gif 4-byte aligned.  Added without a version change: no existing
+ * entry point or struct is touched. */
+int ggan_video_sheet_u8(const float* gen, const float* data, uint8_t* sheet, uint8_t* gif, int n, int rows, int LEN, int C, int H, int W,
+                        int nh, int nw, int interleave, float a, float b, float d, ggan_stream_t stream);
 
 /* reconstruction distances of tflib/utils/distance.py:3-17 (`distance(x, y, 'l1'|'l2')` = reduce_mean(|x-y|^p)), used by the
  * alice / local_epce / vegan objectives as rec_penalty: out[0] (+)= weight * mean(|x-y|^p), p = 1 | 2; the backward writes

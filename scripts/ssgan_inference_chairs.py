@@ -11,6 +11,7 @@ MODE = 'local_ep'  # local_ep, local_epce-z, ali, alice-z (ALI_MODE concat_x | c
 BN_FLAG = False  # BatchNorm in the frame generator, extractors and critics (BN_FLAG_G / _E / _D follow it; see the block)
 SETTINGS = run.reference_block(__file__, MODE=MODE, BN_FLAG=BN_FLAG)
 # edit the block here, e.g. SETTINGS['N_COMS'] = 10 -- or pass it to reference_block, which then derives N_VIS etc. from it
+SETTINGS.update(run.eval_settings(__file__))  # the video passes every 5000 iterations: samples / train_data / reconstruction / disentangle
 SETTINGS.update(DATA_DIR=os.environ.get('GGAN_DATA_DIR', ''), OUT_DIR=os.environ.get('GGAN_OUT_DIR', ''), SAVE_EVERY=10000, LOG_EVERY=100)
 if len(sys.argv) > 1:
     SETTINGS['ITERS'] = int(sys.argv[1])
