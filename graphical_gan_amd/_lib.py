@@ -16,6 +16,8 @@ PACK_ARRIVE_INTS = 33 * 1024          # include/ggan.h: GGAN_PACK_ARRIVE_INTS (a
 POSTERIOR_MAX_K = 8192               # include/ggan.h: GGAN_POSTERIOR_MAX_K
 MODE_K = {'CONCRETE': 0, 'STRAIGHT_THROUGHT_CONCRETE': 1, 'STRAIGHT_THROUGHT': 2}   # include/ggan.h: GGAN_MODE_K_*
 BCE_MAX = 16
+TSNE_MAX_K = 128                     # include/ggan.h: GGAN_TSNE_MAX_K
+TSNE_MAX_SPLITS = 64                 # include/ggan.h: GGAN_TSNE_MAX_SPLITS
 ABI_VERSION = 800                    # include/ggan.h: GGAN_ABI_VERSION (struct layouts and entry points this module binds)
 
 
@@ -79,6 +81,13 @@ SIGNATURES = {
     'ggan_gmm_posterior_assign': (_I, [_P, _P, _F, _I, _I, _I, _I, _P, _P, _P, _P]),
     'ggan_cluster_accuracy': (_I, [_P, _P, _P, _I, _I, _P, _P]),
     'ggan_video_sheet_u8': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _F, _F, _P]),
+    'ggan_tsne_sqnorms': (_I, [_P, _I, _I, _P, _P]),
+    'ggan_tsne_neighbours': (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _Z, _P]),
+    'ggan_tsne_affinities': (_I, [_P, _I, _I, _F, _I, _F, _P, _P, _P]),
+    'ggan_tsne_symmetrise': (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P]),
+    'ggan_tsne_gradient': (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
+    'ggan_tsne_kl': (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
+    'ggan_tsne_iterate': (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _I, _I, _I, _F, _F, _F, _F, _F, _P]),
     'ggan_gemm_split': (_I, [_I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _I, _P, _I, _F, _P, _Z, _P]),
     'ggan_gemm_colsum': (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
     'ggan_dyn_scan_fwd': (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P]),

@@ -7,7 +7,10 @@
   sample_grid        generate_image: Generator(HyperGenerator(tile(eye(N_COMS)), fixed noise)) with one column per component
                      (gmgan_inference_mnist.py:406-419), or Generator(fixed noise) with N_VIS = 2*BATCH_SIZE rows
                      (gan_inference_cifar10.py:370-378);
-  reconstructions    reconstruct_image: real / Generator(Extractor(x)) pairs on a fixed dev minibatch (gmgan_inference_mnist.py:429-443).
+  reconstructions    reconstruct_image: real / Generator(Extractor(x)) pairs on a fixed dev minibatch (gmgan_inference_mnist.py:429-443);
+  manifold           the latent-space pictures of the MNIST scripts (gan_inference_mnist.py:472-480, gmgan_inference_mnist.py:533-551):
+                     q_z (and p_z, and the images) of the labelled dev set embedded by functional.tsne on the device, scattered by
+                     tflib.visualization coloured by digit / mixture component / inferred component.
 
 The passes are safe in the middle of training: they run under torch.no_grad() on the current stream only (no second stream, no
 collective), with a feed dict and a noise generator state of their own -- the Trainer's static feed buffers, ring slots and noise state
@@ -26,7 +29,8 @@ run by SequenceEvaluator on a models_ssgan.StateSpaceGAN under the same rules:
 
 Each is written as a .png sheet (one sequence per row) and a looping .gif; the bytes of both come from one ggan_video_sheet_u8 launch.
 
-`python -m graphical_gan_amd.evaluate CKPT --script gmgan_inference_mnist [--data-dir DIR]` scores a saved checkpoint;
+`python -m graphical_gan_amd.evaluate CKPT --script gmgan_inference_mnist [--data-dir DIR]` scores a saved checkpoint
+(`--out-dir DIR --manifold` also writes the latent-space pictures of the two MNIST scripts);
 `... CKPT --script ssgan_inference_moving_mnist|ssgan_inference_chairs [--data-dir DIR] --out-dir DIR` writes the four pairs of files."""
 import argparse
 import contextlib
@@ -49,6 +53,12 @@ _NAMES = {
     'gmgan_inference_mnist': ('{frame}_samples_{mode}.png', '{frame}_reconstruction_{mode}.png'),
     'gmgan_inference_face': ('{frame}_samples_{mode}.png', '{frame}_reconstruction_{mode}.png'),
 }
+# the t-SNE scatters: (file name, point set, label set) -- gan_inference_mnist.py:480; gmgan_inference_mnist.py:546-551, whose `cluster` and
+# `dev_data_vis` pictures are ONE embedding of the images
+MANIFOLD_SCRIPTS = ('gan_inference_mnist', 'gmgan_inference_mnist')      # the two scripts of the reference that call TSNE()
+_MANIFOLD = (('{mode}_mnist_manifold_{frame}.png', 'z', 'y'),)
+_MANIFOLD_K = (('{frame}_manifold_{mode}.png', 'z', 'y'), ('{frame}_prior_{mode}.png', 'pz', 'pk'),
+               ('{frame}_cluster_{mode}.png', 'x', 'qk'), ('{frame}_dev_data_vis_{mode}.png', 'x', 'y'))
 _DEFAULT_NAMES = ('{mode}_samples_{frame}.png', '{mode}_reconstruction_{frame}.png')       # gan_inference_cifar10 / svhn / face
 _DEFAULT_NAMES_K = _NAMES['gmgan_inference_cifar10']                                         # a mixture model of no named script
 
@@ -215,6 +225,62 @@ class Evaluator(_Passes):
                 self.last_assign, self.last_colbest, self.last_labels = assign.cpu().numpy(), colbest.cpu().numpy(), Y.cpu().numpy()
                 return acc, probs.cpu().numpy()
         return acc
+
+    def latent_sets(self, batches):
+        """the point sets of the latent-space pictures over the labelled minibatches, as device arrays: z = q_z [N, DIM_LATENT] and
+        y = the labels (gan_inference_mnist.py:474-478); with a mixture prior also x = the images, pz = p_z of a fresh hyper_p_k /
+        hyper_p_z per minibatch, pk = argmax hyper_p_k, qk = argmax q_k, q_k the sampled assignment of the configured MODE_K
+        (gmgan_inference_mnist.py:535-543)"""
+        c = self.cfg
+        with self._guard():
+            X, Y = self._stage(batches, want_labels=True)
+            n, B = X.shape[0], c.B
+            new = lambda w, dt=torch.float32: torch.empty((n * B, w) if w else (n * B,), dtype=dt, device=self.device)
+            out = dict(z=new(c.dim_latent), y=Y)
+            if c.K:
+                out.update(x=new(c.output_dim), pz=new(c.dim_latent), pk=new(0, torch.int64), qk=new(0, torch.int64))
+            self.kept = []
+            for i in range(n):
+                rows = slice(i * B, (i + 1) * B)
+                self._load(X[i])
+                real_x = self.model.real_x(self.feed)
+                q = self.model.Extractor(real_x, eps=self.feed['q_eps']) if c.agg else self.model.Extractor(real_x)
+                q_z = q[0] if isinstance(q, tuple) else q
+                out['z'][rows].copy_(q_z)
+                if c.K:
+                    out['x'][rows].copy_(real_x.float())
+                    out['pz'][rows].copy_(self.model.HyperGenerator(self.feed['k_onehot'], self.feed['p_z_noise']))
+                    out['pk'][rows].copy_(torch.argmax(self.feed['k_onehot'], dim=1))
+                    _, q_k = self.model.HyperExtractor(q_z, self.feed.get('gumbel_u'))
+                    out['qk'][rows].copy_(torch.argmax(q_k, dim=1))
+        return out
+
+    def manifold(self, batches, out_dir, frame):
+        """embeds the point sets of latent_sets with functional.tsne and writes the scatters under the reference's file names; returns
+        the paths: the four pictures of gmgan_inference_mnist with a mixture prior, the one of gan_inference_mnist without.  MNIST models
+        only (the reference draws them in no other script).  self.manifold_log: (point set, KL, seconds) of each embedding, also printed.  MANIFOLD_PERPLEXITY (30) and
+        MANIFOLD_ITERS (1000) of the settings reach the embedder; its initial positions are seeded from the settings seed."""
+        c = self.cfg
+        if c.dataset != 'mnist':
+            raise ValueError('the latent-space pictures are a pass of the MNIST scripts (%s); dataset %r has none' % (', '.join(MANIFOLD_SCRIPTS), c.dataset))
+        sets = self.latent_sets(batches)
+        t_sets = self.last_seconds
+        mode = self.S.get('MODE', c.mode)
+        perplexity, n_iter = float(self.S.get('MANIFOLD_PERPLEXITY', 30.)), int(self.S.get('MANIFOLD_ITERS', 1000))
+        seed = int(self.S.get('SEED', 0)) + EVAL_SEED
+        paths, embedded, self.manifold_log = [], {}, []
+        with self._guard():
+            for fname, points, labels in (_MANIFOLD_K if c.K else _MANIFOLD):
+                if points not in embedded:
+                    t0 = time.time()
+                    Y, kl = F.tsne(sets[points], perplexity=perplexity, n_iter=n_iter, seed=seed, return_kl=True)
+                    embedded[points] = Y.cpu().numpy()
+                    self.manifold_log.append((points, kl, time.time() - t0))
+                    print('[eval] t-SNE of %s %s: KL %.4f, %.2f s' % (points, tuple(sets[points].shape), kl, time.time() - t0))
+                lib.visualization.scatter(embedded[points], sets[labels].cpu().numpy(), out_dir, fname.format(frame=frame, mode=mode))
+                paths.append(os.path.join(out_dir, fname.format(frame=frame, mode=mode)))
+        self.last_seconds += t_sets
+        return paths
 
     def _to_unit(self, x):
         """generator output -> [0, 1] images for save_images"""
@@ -440,6 +506,7 @@ def main(argv=None):
     ap.add_argument('--data-dir', default=os.environ.get('GGAN_DATA_DIR', ''))
     ap.add_argument('--mode', default=None, help="the script's MODE (default: the script's own)")
     ap.add_argument('--out-dir', default=None, help='also write the sample grid and the reconstructions here (the state-space scripts: the video files, required)')
+    ap.add_argument('--manifold', action='store_true', help='also write the latent-space t-SNE pictures of the MNIST scripts to --out-dir')
     ap.add_argument('--set', action='append', default=[], metavar='KEY=VALUE', help='override an UPPERCASE setting (int / float / str)')
     a = ap.parse_args(argv)
     over = {}
@@ -454,6 +521,12 @@ def main(argv=None):
         over[k] = v
     if a.mode:
         over['MODE'] = a.mode
+    if a.manifold:          # (checked before anything is built)
+        name = os.path.splitext(os.path.basename(a.script))[0]
+        if name not in MANIFOLD_SCRIPTS:
+            ap.error('--manifold: the latent-space pictures exist for %s only, not for %s' % (' and '.join(MANIFOLD_SCRIPTS), name))
+        if not a.out_dir:
+            ap.error('--manifold writes pictures: it needs --out-dir')
     S = run.reference_block(a.script, **over)
     S.update(DATA_DIR=a.data_dir, SCRIPT=a.script)
     cfg, model = run.config(S), None
@@ -464,14 +537,14 @@ def main(argv=None):
         model = StateSpaceGAN(cfg)
     tr = Trainer(cfg, device=lib.get_device(), graph=False, model=model)
     checkpoint.restore(a.ckpt, tr)
-    res = evaluate_once(tr, S, out_dir=a.out_dir)
+    res = evaluate_once(tr, S, out_dir=a.out_dir, manifold=a.manifold)
     for k in sorted(res):
         print('%s\t%s' % (k, res[k]))
     return res
 
 
-def evaluate_once(tr, S, out_dir=None, frame='eval'):
-    """every pass the script's data allow, once -> {name: value}"""
+def evaluate_once(tr, S, out_dir=None, frame='eval', manifold=False):
+    """every pass the script's data allow, once -> {name: value}; manifold: the latent-space pictures too (labelled dev data only)"""
     from . import run
     if S['DATASET'] in run.SEQUENCE_DATASETS:       # the video passes: files only (train_data: the first dev minibatch)
         ev = SequenceEvaluator(tr, S)
@@ -488,6 +561,11 @@ def evaluate_once(tr, S, out_dir=None, frame='eval'):
         os.makedirs(out_dir, exist_ok=True)
         ev.set_fixed_data(dev[0])
         ev.save_images(out_dir, frame)
+    if manifold:
+        if not run.labelled(dev):
+            print('[evaluate] latent-space t-SNE skipped: no labelled dev set')
+        else:
+            res['manifold files'] = ' '.join(os.path.basename(p) for p in ev.manifold(dev, out_dir, frame))
     return res
 
 

@@ -93,6 +93,42 @@ def eval_settings(script):
     return S
 
 
+# the latent-space t-SNE pictures (evaluate.Evaluator.manifold) have a cadence of their own, outside EVAL_KEYS: every 50000 iterations in
+# gan_inference_mnist.py:472, once after the last iteration in gmgan_inference_mnist.py:534, in no other script
+MANIFOLD_KEYS = ('MANIFOLD_EVERY', 'MANIFOLD_AT_END')
+
+
+def manifold_settings(script):
+    """{'MANIFOLD_EVERY': 50000} for gan_inference_mnist, {'MANIFOLD_AT_END': True} for gmgan_inference_mnist, {} for every other script;
+    $GGAN_MANIFOLD_EVERY sets (lowers) MANIFOLD_EVERY for those two"""
+    name = os.path.splitext(os.path.basename(script))[0]
+    S = {'gan_inference_mnist': {'MANIFOLD_EVERY': 50000}, 'gmgan_inference_mnist': {'MANIFOLD_AT_END': True}}.get(name, {})
+    S = dict(S)
+    k = 'MANIFOLD_EVERY'
+    if S and os.environ.get('GGAN_' + k):
+        S[k] = int(os.environ['GGAN_' + k])
+    return S
+
+
+def manifold_plan(S):
+    """the MANIFOLD_* keys a settings block switches on, or None"""
+    plan = {k: S[k] for k in MANIFOLD_KEYS if S.get(k)}
+    return plan or None
+
+
+def manifold_due(plan, it, iters):
+    """does the pass fire after iteration `it` of `iters`: it % N == N - 1 (gan_inference_mnist.py:472), it == ITERS - 1 (gmgan :534)"""
+    if not plan:
+        return False
+    n = int(plan.get('MANIFOLD_EVERY') or 0)
+    return bool((n and it % n == n - 1) or (plan.get('MANIFOLD_AT_END') and it == iters - 1))
+
+
+def labelled(batches):
+    """are these minibatches (images, labels) pairs"""
+    return bool(batches) and all(isinstance(b, (tuple, list)) and len(b) > 1 and b[1] is not None for b in batches)
+
+
 def eval_sets(S, model, device):
     """(dev minibatches, labelled test minibatches or None) for the evaluation passes: tflib.mnist.load's dev and test generators, the
     test split of the CIFAR-10 / SVHN loaders, celebA's dev split, the dev split of the moving-MNIST / chairs loaders (the FIRST
@@ -272,6 +308,23 @@ def train(S, cfg, model=None, out_dir=None):
         if 'ACCURACY_EVERY' in plan and (ev_test is None or not tr.cfg.K):
             print('[run] testing accuracy skipped: %s' % ('no mixture prior (N_COMS)' if not tr.cfg.K else 'no labelled test set (%s data)' % source))
             plan.pop('ACCURACY_EVERY')
+    manifold = manifold_plan(S) if (tr.world == 1 or torch.distributed.get_rank() == 0) else None
+    if manifold:
+        from .evaluate import Evaluator
+        from .models_ssgan import StateSpaceGAN
+        m_dev = None
+        if isinstance(tr.model, StateSpaceGAN) or tr.cfg.dataset != 'mnist':
+            why = 'a pass of the MNIST scripts only'
+        elif not out_dir:
+            why = 'no OUT_DIR to write the pictures to'
+        else:
+            m_dev = ev_dev if evaluator is not None else eval_sets(S, tr.model, device)[0]
+            why = None if labelled(m_dev) else 'no labelled dev set (%s data)' % source
+        if why:
+            print('[run] latent-space t-SNE skipped: %s' % why)
+            manifold = None
+        else:
+            m_eval = evaluator if evaluator is not None else Evaluator(tr, S)
     eval_ms = 0.0            # wall time of the evaluation passes (kept out of `time`)
     for it in range(S['ITERS']):
         if (it == 2 and isinstance(batches, DevicePrefetcher) and S.get('RING_FEED', True) and tr.graph_enabled
@@ -295,6 +348,8 @@ def train(S, cfg, model=None, out_dir=None):
         if due:
             eval_ms += _evaluate(evaluator, due, ev_dev, ev_test, it, out_dir, device, tr)
             lib.plot.flush(out_dir, os.path.join(out_dir, 'logfile.txt') if out_dir else None)
+        if manifold_due(manifold, it, S['ITERS']):
+            eval_ms += _manifold(m_eval, m_dev, it, out_dir, device)
         lib.plot.tick()
         if out_dir and S.get('SAVE_EVERY') and (it + 1) % S['SAVE_EVERY'] == 0:
             checkpoint.save(os.path.join(out_dir, 'params_%d.npz' % (it + 1)), tr, data_source=source)
@@ -329,6 +384,17 @@ def _evaluate(ev, due, dev, test, it, out_dir, device, tr=None):
             ev.save_videos(out_dir, it, train_data=tr.feed['real_x_unit'])
         else:
             ev.save_images(out_dir, it)
+    if device.type == 'cuda':
+        torch.cuda.synchronize(device)
+    return (time.time() - t0) * 1e3
+
+
+def _manifold(ev, dev, it, out_dir, device):
+    """the latent-space pictures after iteration `it` -> milliseconds they took"""
+    if device.type == 'cuda':
+        torch.cuda.synchronize(device)
+    t0 = time.time()
+    ev.manifold(dev, out_dir, it)
     if device.type == 'cuda':
         torch.cuda.synchronize(device)
     return (time.time() - t0) * 1e3

@@ -483,6 +483,46 @@ int ggan_cluster_accuracy(const int32_t* assign, const int32_t* labels, const ui
 int ggan_video_sheet_u8(const float* gen, const float* data, uint8_t* sheet, uint8_t* gif, int n, int rows, int LEN, int C, int H, int W,
                         int nh, int nw, int interleave, float a, float b, float d, ggan_stream_t stream);
 
+/* ---- t-SNE: the latent-space pictures of the MNIST scripts (gan_inference_mnist.py:472-480, gmgan_inference_mnist.py:533-551:
+ * TSNE().fit_transform on the host).  van der Maaten's algorithm with the schedule of that TSNE(); the repulsive term is summed exactly
+ * over all pairs (no Barnes-Hut tree) and there is no early stop.  No float atomics: the same input gives the same bits on every run.
+ * Added without a version change: no existing entry point or struct is touched.
+ *   ggan_tsne_sqnorms     norms[i] = |x_i|^2, x [N, D].
+ *   ggan_tsne_neighbours  rows row0 .. row0+rows-1: dots [rows, N] (scratch) = X_blk X^T through ggan_gemm (ws as there), turned in place
+ *                         into d_ij = max(|x_i|^2 + |x_j|^2 - 2 x_i.x_j, 0); idx / dist [N, K]: the K nearest j != i of each row of the
+ *                         block, ascending in (distance, index): a tie in distance goes to the lower index.  2 <= K + 1 <= N, K <= 128.
+ *   ggan_tsne_affinities  sklearn's _binary_search_perplexity, one row each: at most `steps` bisection steps on beta from 1, until the
+ *                         entropy of p_j|i = exp(-beta d_ij) / sum is log(perplexity) within tol.  Each row of dist is ascending (as ggan_tsne_neighbours writes it): the distances are taken relative to
+ *                         dist[i][0], which changes neither p nor the entropy and needs no floor on the sum; p_cond [N, K], beta [N]: the value
+ *                         p_cond was formed with.  0 < perplexity < N.
+ *   ggan_tsne_symmetrise  P = (P + P^T) / 2N as a CSR: ptr [N + 1], col / val [2 N K].  Row i: its K neighbours in their order, then
+ *                         every j whose list holds i, ascending; a j in both relations carries its whole value in the first group and
+ *                         0 in the second.  ptr[N] = 2 N K.  scratch: 2 N + N K ints.
+ *   ggan_tsne_gradient    at the embedding y [N, 2]: attr[i] = sum_j P_ij q_ij (y_i - y_j), rep[i] = sum_j q_ij^2 (y_i - y_j),
+ *                         z[0] = sum_{i != j} q_ij, q_ij = 1 / (1 + |y_i - y_j|^2).  The j range is cut into `splits` (1 .. 64)
+ *                         parts, one per workgroup; part: 2 N splits floats, zblk: splits * ceil(N / 256) floats, added in a fixed order.
+ *   ggan_tsne_kl          kl[0] = sum_ij P_ij log(P_ij Z / q_ij) (klrow: N floats of scratch).
+ *   ggan_tsne_iterate     iterations it0 .. it1-1: grad = 4 (e attr - rep / Z); gains + 0.2 where grad and velocity disagree in sign,
+ *                         x 0.8 otherwise, floored at min_gain; vel = m vel - learning_rate gain grad; y += vel.  e = early_exaggeration
+ *                         and m = momentum0 while it < exploration_iters, then 1 and momentum1.  Positions alternate between ya (read
+ *                         first) and yb: the result is in ya after an even number of iterations, in yb after an odd one. */
+#define GGAN_TSNE_MAX_K 128
+#define GGAN_TSNE_MAX_SPLITS 64
+int ggan_tsne_sqnorms(const float* x, int N, int D, float* norms, ggan_stream_t stream);
+int ggan_tsne_neighbours(const float* x, const float* norms, int N, int D, int row0, int rows, int K, float* dots, int32_t* idx, float* dist,
+                         void* ws, size_t ws_bytes, ggan_stream_t stream);
+int ggan_tsne_affinities(const float* dist, int N, int K, float perplexity, int steps, float tol, float* p_cond, float* beta,
+                         ggan_stream_t stream);
+int ggan_tsne_symmetrise(const int32_t* idx, const float* p_cond, int N, int K, int* ptr, int32_t* col, float* val, int* scratch,
+                         ggan_stream_t stream);
+int ggan_tsne_gradient(const int* ptr, const int32_t* col, const float* val, const float* y, int N, int splits, float* part, float* zblk,
+                       float* attr, float* rep, float* z, ggan_stream_t stream);
+int ggan_tsne_kl(const int* ptr, const int32_t* col, const float* val, const float* y, int N, int splits, float* part, float* zblk,
+                 float* klrow, float* kl, ggan_stream_t stream);
+int ggan_tsne_iterate(const int* ptr, const int32_t* col, const float* val, float* ya, float* yb, float* vel, float* gains, int N, int splits,
+                      float* part, float* zblk, int it0, int it1, int exploration_iters, float early_exaggeration, float momentum0,
+                      float momentum1, float learning_rate, float min_gain, ggan_stream_t stream);
+
 /* reconstruction distances of tflib/utils/distance.py:3-17 (`distance(x, y, 'l1'|'l2')` = reduce_mean(|x-y|^p)), used by the
  * alice / local_epce / vegan objectives as rec_penalty: out[0] (+)= weight * mean(|x-y|^p), p = 1 | 2; the backward writes
  * gx and/or gy (either may be NULL). */
