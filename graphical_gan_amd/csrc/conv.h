@@ -21,8 +21,17 @@ int conv_wgrad_naive(const ggan_conv_geom& g, const float* x, const float* gy, G
 // 0 on success, <0 on error.
 // Workgroups the forward / data-gradient launches are planned for when ggan_conv_geom.plan_wgs is 0 (~one per CU)
 constexpr int kTargetWgs = 200;
+// Output mask of a forward launch (epilogues of conv_corr.hip and conv_thin.hip): the launch stores act_grad(value, ref[i]) instead of the
+// value.  conv_fwd_mfma sets `applied` when its launch does -- and returns 1 before launching anything when the planned launch cannot
+// (split-K: the epilogue does not see final values).
+struct OutMask {
+    const float* ref;
+    int act;
+    float alpha;
+    bool applied;
+};
 int conv_fwd_mfma(const ggan_conv_geom& g, const float* x, const float* w, const float* bias, float* y, int act,
-                  float alpha, void* ws, size_t ws_bytes, hipStream_t s);
+                  float alpha, void* ws, size_t ws_bytes, hipStream_t s, OutMask* mask = nullptr);
 int conv_dgrad_mfma(const ggan_conv_geom& g, const float* gy, GyMask m, const float* w, const float* bias, float* gx,
                     int act, float alpha, void* ws, size_t ws_bytes, hipStream_t s);
 // all-class data gradient on 64-pixel x 16 / 32-channel tiles (conv_dg16.hip, round 4): same contract; target_wgs = ggan_conv_geom.plan_wgs
@@ -53,15 +62,6 @@ struct ThinCastSrc {
     int nslots, offset;
     float div, mul;
 };
-// Output mask of a forward launch (conv_corr.hip epilogue): while *g_out_mask is set, conv_fwd_mfma stores act_grad(value, ref[i]) instead of
-// the value -- or returns 1 before launching anything when the planned launch cannot (split-K: the epilogue does not see final values).
-struct OutMask {
-    const float* ref;
-    int act;
-    float alpha;
-    bool applied;
-};
-extern thread_local OutMask* g_out_mask;
 // mask (optional): the thin-channel forward stores act_grad(value, mask->ref[i]) (the masked forward of a first layer)
 int conv_fwd_thin(const ggan_conv_geom& g, const float* x, const float* w, const float* bias, float* y, int act, float alpha,
                   hipStream_t s, const ThinCastSrc* cast = nullptr, const OutMask* mask = nullptr);

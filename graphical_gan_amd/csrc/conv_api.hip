@@ -210,9 +210,7 @@ int ggan_conv2d_fwd_masked(const ggan_conv_geom* g, const float* x, const float*
         const int r = conv_fwd_thin(*g, x, w, nullptr, y, GGAN_ACT_NONE, 0.f, (hipStream_t)stream, nullptr, &M);
         if (r <= 0) return r;
     }
-    g_out_mask = &M;
-    const int rc = conv_fwd_mfma(*g, x, w, nullptr, y, GGAN_ACT_NONE, 0.f, ws, ws ? ws_bytes : 0, (hipStream_t)stream);
-    g_out_mask = nullptr;
+    const int rc = conv_fwd_mfma(*g, x, w, nullptr, y, GGAN_ACT_NONE, 0.f, ws, ws ? ws_bytes : 0, (hipStream_t)stream, &M);
     if (rc == 0 && !M.applied) { set_error("conv2d_fwd_masked: launch without the mask"); return -3; }
     return rc;
 }

@@ -1096,7 +1096,7 @@ const unsigned* fwd_slab_table(const CorrParams& P, int CK, int nthr, int su, hi
 template <int MODE>
 int plan_and_launch(CorrParams& P, int Hu, int Wv, int su, int ext_r, int ext_c, int ntaps, int groups, float* dst,
                     const float* bias, int act, float alpha, void* ws, size_t ws_bytes, hipStream_t s, const char* name,
-                    double fl, const char* sk_env) {
+                    double fl, const char* sk_env, OutMask* mask = nullptr) {
     const int target = P.plan_wgs > 0 ? P.plan_wgs : kTargetWgs;
     const WaveCfg* kCfgs = MODE == 1 ? kCfgsDgrad : kCfgsFwd;
     // 8 waves per workgroup (two per SIMD: one wave's LDS / barrier stalls hide under the other's MFMAs; measured
@@ -1196,11 +1196,11 @@ int plan_and_launch(CorrParams& P, int Hu, int Wv, int su, int ext_r, int ext_c,
     }
     P.out = P.SK > 1 ? (float*)ws : dst;
     P.bias = bias; P.act = act; P.alpha = alpha;
-    if (g_out_mask) {
+    if (mask) {
         // the stored values masked by a reference tensor (conv.h: OutMask): only where the epilogue writes the final values
         if (MODE != 0 || P.SK != 1) return 1;
-        P.out_ref = g_out_mask->ref; P.out_act = g_out_mask->act; P.out_alpha = g_out_mask->alpha;
-        g_out_mask->applied = true;
+        P.out_ref = mask->ref; P.out_act = mask->act; P.out_alpha = mask->alpha;
+        mask->applied = true;
     }
     if ((P.dbg & 4) && ws && ws_bytes > (64u << 20)) P.stamps = (unsigned long long*)((char*)ws + ws_bytes - (32u << 20));
     size_t stage = MODE == 0 ? 2 * ((size_t)fwd_region(CK * P.CS, CK * P.CS / P.xq, P.xq) + (size_t)fwd_region(ntaps * CK * RS, ntaps * CK * (TNW / 4), 4))
@@ -1234,8 +1234,6 @@ int plan_and_launch(CorrParams& P, int Hu, int Wv, int su, int ext_r, int ext_c,
 
 namespace ggan {
 
-thread_local OutMask* g_out_mask = nullptr;
-
 int launch_splitk_reduce(const float* partial, int SK, size_t elems, float* out, const float* bias, int C, int HW, int act,
                          float alpha, hipStream_t s, size_t slab_stride, float* tail_out, size_t tail) {
     if (slab_stride == 0) slab_stride = elems;
@@ -1266,7 +1264,7 @@ static bool hot_geometry(const ggan_conv_geom& g) { return g.k == 5 && g.stride 
 static bool fits32(size_t bytes) { return bytes < 0x7FFFFFF0ull; }
 
 int conv_fwd_mfma(const ggan_conv_geom& g, const float* x, const float* w, const float* bias, float* y, int act,
-                  float alpha, void* ws, size_t ws_bytes, hipStream_t s) {
+                  float alpha, void* ws, size_t ws_bytes, hipStream_t s, OutMask* mask) {
     if (!hot_geometry(g) || (g.Co & 3)) return 1;
     ws = ws_scratch(ws, ws_bytes);
     const size_t in_bytes = (size_t)g.N * g.Ci * g.H * g.W * 4, w_bytes = (size_t)25 * g.Ci * g.Co * 4;
@@ -1287,7 +1285,7 @@ int conv_fwd_mfma(const ggan_conv_geom& g, const float* x, const float* w, const
     P.out_elems = (size_t)g.N * g.Co * g.Ho * g.Wo;
     const double fl = 2.0 * P.out_elems * g.Ci * 25.0;
     return plan_and_launch<0>(P, g.Ho, g.Wo, 2, 5, 5, 25, 1, y, bias, act, alpha, ws, ws_bytes, s, "conv_fwd_mfma", fl,
-                              "GGAN_FWD_SK");
+                              "GGAN_FWD_SK", mask);
 }
 
 int conv_dgrad_mfma(const ggan_conv_geom& g, const float* gy, GyMask m, const float* w, const float* bias, float* gx,

@@ -12,9 +12,9 @@ There is no CPU path: tensors must live on a HIP device and libggan.so must load
 # included, so that `from graphical_gan_amd import functional as F` reads as before
 from ._core import (  # noqa: F401
     C, os, weakref, torch, Function, once_differentiable, _lib, ACT_NONE, ACT_LRELU, ACT_RELU, ACT_TANH, ACT_SIGMOID, ConvGeom,
-    check, _WS, _WS_BYTES, _L, _p, _stream, _dev, _c, _os, _DEFER, _DATA_ONLY, _is_param, data_grad_only,
-    _skip_undefined, defer_wgrad_reduce, _wgrad_parts, _STREAMS, shared_stream, workspace, _TARGET, _SERIAL_BWD, serial_backward,
-    _bwd_target, target_workgroups, _threading, _PLAN, _PLAIN, force_plain, launch_hint, _carries_hint, _planned_for,
+    check, _WS, _WS_BYTES, _L, _p, _stream, _dev, _c, _DEFER, _DATA_ONLY, _is_param, data_grad_only,
+    _skip_undefined, defer_wgrad_reduce, _wgrad_parts, _STREAMS, shared_stream, workspace, _PLAN, _PLAIN, _SERIAL_BWD, target_workgroups,
+    launch_hint, serial_backward, _remembers_plan, force_plain,
     same_geometry, conv_geom, _geom, _SITE, site_scope, site_plan, RowSlot, _new_out, _adjacent, HEAD_LOGITS, _PENDING_COSTS, _tail_value, settle_cost,
     pending_costs, drop_pending_costs, UNIT_SEEDS, unit_seed, is_unit_seed, LATE_EXT, _LATE_TERMS, mark_ready, wait_ready, add_late_terms,
     drop_late_terms)

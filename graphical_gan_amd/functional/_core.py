@@ -1,6 +1,7 @@
 """state shared by every op family: library handle and pointer helpers, workspaces and side streams, launch plans (target_workgroups / launch_hint), conv geometry, row slots, and the registries the loss heads and optimizers share (HEAD_LOGITS, pending costs, unit seeds)."""
 import ctypes as C
 import os
+import threading
 import weakref
 
 import torch
@@ -38,9 +39,6 @@ def _c(t):
     if t.dtype != torch.float32:
         raise _lib.GganError('fp32 expected, got %s' % t.dtype)
     return t if t.is_contiguous() else t.contiguous()
-
-
-import os as _os
 
 
 # Filter gradients as split-K partial slabs: inside `defer_wgrad_reduce` the filter-gradient kernels leave their slabs in a
@@ -178,14 +176,51 @@ def workspace(device):
 # ---------------------------------------------------------------------------------------------------
 # geometry (TF padding arithmetic)
 # ---------------------------------------------------------------------------------------------------
-_TARGET = [0]
-_SERIAL_BWD = [False]
+# The launch plan of a conv call (ggan_conv_geom.plan_wgs / plan_wgs_filter / plan_flags) is per CALL: it is filled into the geometry
+# struct from this thread's current setting -- autograd runs backward nodes on worker threads, each with its own -- and the library keeps
+# no process-wide plan (round 3 review: set / launch / restore sequences on C globals interleaved between threads).
+class _Plan(threading.local):
+    target = 0         # target_workgroups
+    hint = 0           # launch_hint
+
+
+_PLAN = _Plan()
+_PLAIN = [False]       # force_plain(): debug cross-check on the plain kernels (process-wide on purpose: a test switch)
+_SERIAL_BWD = [False]  # serial_backward(): process-wide on purpose too (see there)
+
+
+class _plan_field(object):
+    """sets one field of this thread's plan inside the block and restores it behind it"""
+    field = None
+
+    def __init__(self, n):
+        self.n = int(n or 0)
+
+    def __enter__(self):
+        self.prev = getattr(_PLAN, self.field)
+        setattr(_PLAN, self.field, self.n)
+
+    def __exit__(self, *a):
+        setattr(_PLAN, self.field, self.prev)
+
+
+class target_workgroups(_plan_field):
+    """with target_workgroups(n): the conv ops recorded inside plan their launches -- forward AND, later, backward -- for n workgroups
+    (ggan_conv_geom.plan_wgs / plan_wgs_filter of their calls) instead of about one per CU: for layers of two chains that run side by side on two streams"""
+    field = 'target'
+
+
+class launch_hint(_plan_field):
+    """with launch_hint(n): the launches of conv calls made inside (and not under target_workgroups) plan for n workgroups
+    (engine.Trainer._launch_hint: the wali-gp critic step, whose penalty pass runs beside the main pass)"""
+    field = 'hint'
 
 
 class serial_backward(object):
     """with serial_backward(): the backward launches of layers recorded under target_workgroups take the DEFAULT plan -- for a backward
     pass whose two chains are NOT going to run side by side (the data-parallel generator step differentiates the Generator's and the
-    Extractor's halves one after the other, so that the first gradient bucket can go on the wire early: engine._bwd_phase1 / 2)"""
+    Extractor's halves one after the other, so that the first gradient bucket can go on the wire early: engine._bwd_phase1 / 2).
+    A process-wide flag, unlike the plan: it is set on the thread that calls backward and read on autograd's worker thread."""
 
     def __enter__(self):
         self.prev, _SERIAL_BWD[0] = _SERIAL_BWD[0], True
@@ -194,81 +229,28 @@ class serial_backward(object):
         _SERIAL_BWD[0] = self.prev
 
 
-def _bwd_target(ctx):
-    return 0 if _SERIAL_BWD[0] else getattr(ctx, 'target', 0)
-
-
-class target_workgroups(object):
-    """with target_workgroups(n): the conv ops recorded inside plan their launches -- forward AND, later, backward -- for n workgroups
-    (ggan_conv_geom.plan_wgs / plan_wgs_filter of their calls) instead of about one per CU: for layers of two chains that run side by side on two streams"""
-
-    def __init__(self, n):
-        self.n = int(n or 0)
-
-    def __enter__(self):
-        self.prev, _TARGET[0] = _TARGET[0], self.n
-
-    def __exit__(self, *a):
-        _TARGET[0] = self.prev
-
-
-# The launch plan of a conv call (ggan_conv_geom.plan_wgs / plan_wgs_filter / plan_flags) is per CALL: it is filled into the geometry
-# struct from this thread's current setting -- autograd runs backward nodes on worker threads, each with its own -- and the library keeps
-# no process-wide plan (round 3 review: set / launch / restore sequences on C globals interleaved between threads).
-import threading as _threading
-_PLAN = _threading.local()
-_PLAIN = [False]       # force_plain(): debug cross-check on the plain kernels (process-wide on purpose: a test switch)
-
-
-def force_plain(on):
-    """every conv call from now on asks for the plain one-thread-per-output kernels (GGAN_PLAN_PLAIN); returns the old setting"""
-    old, _PLAIN[0] = _PLAIN[0], bool(on)
-    return old
-
-
-class launch_hint(object):
-    """with launch_hint(n): the launches of conv calls made inside (and not under target_workgroups) plan for n workgroups
-    (engine.Trainer._launch_hint: the wali-gp critic step, whose penalty pass runs beside the main pass)"""
-
-    def __init__(self, n):
-        self.n = int(n or 0)
-
-    def __enter__(self):
-        self.prev = getattr(_PLAN, 'hint', 0)
-        _PLAN.hint = self.n
-
-    def __exit__(self, *a):
-        _PLAN.hint = self.prev
-
-
-def _carries_hint(cls):
-    """conv Functions: the launch hint in force when the layer was recorded also plans its backward launches -- autograd runs backward
-    nodes on its own worker threads, where this thread's setting is not visible"""
+def _remembers_plan(cls):
+    """conv Functions: the (target, hint) in force when the layer was recorded plans its whole backward too -- every launch and every
+    Function applied in it.  autograd runs backward nodes on its own worker threads, where the recording thread's setting is not visible."""
     fwd, bwd = cls.forward, cls.backward
 
     def forward(ctx, *args):
-        ctx._hint = getattr(_PLAN, 'hint', 0)
+        ctx._plan = (_PLAN.target, _PLAN.hint)
         return fwd(ctx, *args)
 
     def backward(ctx, *gs):
-        with launch_hint(ctx._hint):
+        target, hint = ctx._plan
+        with target_workgroups(0 if _SERIAL_BWD[0] else target), launch_hint(hint):
             return bwd(ctx, *gs)
     cls.forward = staticmethod(forward)
     cls.backward = staticmethod(backward)
     return cls
 
 
-class _planned_for(object):
-    def __init__(self, n):
-        self.n = int(n or 0)
-
-    def __enter__(self):
-        self.prev = getattr(_PLAN, 'both', 0)
-        if self.n:
-            _PLAN.both = self.n
-
-    def __exit__(self, *a):
-        _PLAN.both = self.prev
+def force_plain(on):
+    """every conv call from now on asks for the plain one-thread-per-output kernels (GGAN_PLAN_PLAIN); returns the old setting"""
+    old, _PLAIN[0] = _PLAIN[0], bool(on)
+    return old
 
 
 def same_geometry(size, k, stride, padding='SAME'):
@@ -331,10 +313,9 @@ class site_plan(object):
 
 
 def _geom(t):
-    both, hint = getattr(_PLAN, 'both', 0), getattr(_PLAN, 'hint', 0)
     # (the hint plans the filter gradient too since round 5: with the four-wave kernel 128 workgroups x 4 chunks beat 256 x 2 beside a
     #  second chain -- headline 4.29 -> 4.17 ms)
-    wgs = wgs_f = both or hint
+    wgs = wgs_f = _PLAN.target or _PLAN.hint
     scope, plan = _SITE['scope'], _SITE['plan']
     if scope is not None and plan is not None:
         site = '%s:%d' % (scope, _SITE['n'])

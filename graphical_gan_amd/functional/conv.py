@@ -5,8 +5,7 @@ import torch
 from torch.autograd import Function
 from .._lib import ACT_NONE, ACT_LRELU, ACT_RELU, check  # noqa: F401
 from ._core import (  # noqa: F401
-    _L, _p, _stream, _c, _DEFER, _DATA_ONLY, _is_param, _skip_undefined, _wgrad_parts, workspace, _TARGET,
-    _bwd_target, target_workgroups, _PLAN, _carries_hint, _planned_for, _geom, _new_out)
+    _L, _p, _stream, _c, _DEFER, _DATA_ONLY, _is_param, _skip_undefined, _wgrad_parts, workspace, _remembers_plan, _geom, _new_out)
 from .pointwise import ActBwd  # noqa: F401
 
 
@@ -48,7 +47,7 @@ class PendingCast(object):
         return self.out
 
 
-@_carries_hint
+@_remembers_plan
 @_skip_undefined
 class ConvFwd(Function):
     """y = conv(x[N,Ci,H,W], w[k,k,Ci,Co]) + bias  (tf.nn.conv2d + bias_add; also the Deconv2D data-gradient)."""
@@ -69,25 +68,23 @@ class ConvFwd(Function):
         x, w = _c(x), _c(w)
         assert tuple(x.shape) == (N, Ci, H, W) and tuple(w.shape) == (geom[7], geom[7], Ci, Co), (x.shape, w.shape, geom)
         ctx.grad_rows = int(grad_rows) if grad_rows else None
-        ctx.target = _TARGET[0]
         y = torch.empty((N, Co, Ho, Wo), dtype=torch.float32, device=x.device)
         ws = workspace(x.device)
-        with _planned_for(ctx.target):
-            g = _geom(geom)
-            bp = _p(_c(bias)) if bias is not None else _p(None)
-            if pend is not None:
-                rt, ca, cb, off = pend.ring
-                nz = _p(_c(pend.noise)) if pend.noise is not None else _p(None)
-                rc = _L().ggan_conv2d_fwd_cast_ring(C.byref(g), _p(rt), rt.shape[0], _p(ca), _p(cb), int(off), nz, pend.div, pend.mul,
-                                                    _p(x), _p(w), bp, _p(y), act, alpha, _stream())
-                if rc == 1:
-                    pend.materialize()          # (geometry outside the thin-channel kernel: the two launches)
-                    pend = None
-                else:
-                    check(rc, 'ggan_conv2d_fwd_cast_ring')
-                    pend.done = True
-            if pend is None:
-                check(_L().ggan_conv2d_fwd(C.byref(g), _p(x), _p(w), bp, _p(y), act, alpha, _p(ws), ws.numel(), _stream()), 'ggan_conv2d_fwd')
+        g = _geom(geom)
+        bp = _p(_c(bias)) if bias is not None else _p(None)
+        if pend is not None:
+            rt, ca, cb, off = pend.ring
+            nz = _p(_c(pend.noise)) if pend.noise is not None else _p(None)
+            rc = _L().ggan_conv2d_fwd_cast_ring(C.byref(g), _p(rt), rt.shape[0], _p(ca), _p(cb), int(off), nz, pend.div, pend.mul,
+                                                _p(x), _p(w), bp, _p(y), act, alpha, _stream())
+            if rc == 1:
+                pend.materialize()          # (geometry outside the thin-channel kernel: the two launches)
+                pend = None
+            else:
+                check(rc, 'ggan_conv2d_fwd_cast_ring')
+                pend.done = True
+        if pend is None:
+            check(_L().ggan_conv2d_fwd(C.byref(g), _p(x), _p(w), bp, _p(y), act, alpha, _p(ws), ws.numel(), _stream()), 'ggan_conv2d_fwd')
         ctx.geom, ctx.act, ctx.alpha, ctx.has_bias = geom, act, alpha, bias is not None
         ctx.w_param, ctx.b_param = _is_param(w), _is_param(bias)
         ctx.save_for_backward(x, w, y if act != ACT_NONE else None)
@@ -99,8 +96,7 @@ class ConvFwd(Function):
         if not torch.is_grad_enabled():
             # plain backward: two launches -- the activation derivative is applied while gy is staged and the bias
             # gradient comes out of the filter-gradient kernel (no act_bwd / chansum passes, no intermediate tensor)
-            with _planned_for(_bwd_target(ctx)):
-                r = _fused_conv_backward(ctx, gy, x, w, y)
+            r = _fused_conv_backward(ctx, gy, x, w, y)
             if r is not None:
                 return r + (None,)
         want_w = ctx.needs_input_grad[1] and not (_DATA_ONLY[0] and ctx.w_param)
@@ -109,8 +105,7 @@ class ConvFwd(Function):
                 and not ctx.grad_rows):
             # a double backward is being recorded and only the data gradient is asked for (the gradient-penalty pass): the activation
             # derivative rides in the data-gradient launch, and in its backward's launches (ConvDgradMasked)
-            with _planned_for(_bwd_target(ctx)):        # (the plan remembered for this layer's backward launches)
-                return ConvDgradMasked.apply(gy, y, w, ctx.geom, ctx.act, ctx.alpha), None, None, None, None, None, None
+            return ConvDgradMasked.apply(gy, y, w, ctx.geom, ctx.act, ctx.alpha), None, None, None, None, None, None
         if ctx.act != ACT_NONE:
             gy = ActBwd.apply(gy, y, ctx.act, ctx.alpha)       # lrelu/relu: sign(y) == sign(pre-activation)
         gx = gw = gb = None
@@ -159,7 +154,7 @@ def _fused_conv_backward(ctx, gy, x, w, y):
     return gx, gw, gb, None, None, None
 
 
-@_carries_hint
+@_remembers_plan
 @_skip_undefined
 class ConvDgrad(Function):
     """gx[N,Ci,H,W] = conv^T(gy[N,Co,Ho,Wo], w) + bias[Ci]  (Conv2DBackpropInput; also the Deconv2D forward)."""
@@ -169,13 +164,11 @@ class ConvDgrad(Function):
         gy, w = _c(gy), _c(w)
         N, Ci, H, W, Co, Ho, Wo = geom[:7]
         assert tuple(gy.shape) == (N, Co, Ho, Wo) and tuple(w.shape) == (geom[7], geom[7], Ci, Co), (gy.shape, w.shape, geom)
-        ctx.target = _TARGET[0]
         gx = _new_out(slot, (N, Ci, H, W), gy.device)
         ws = workspace(gy.device)
-        with _planned_for(ctx.target):
-            g = _geom(geom)
-            check(_L().ggan_conv2d_bwd_data(C.byref(g), _p(gy), _p(w), _p(_c(bias)) if bias is not None else _p(None),
-                                            _p(gx), act, alpha, _p(ws), ws.numel(), _stream()), 'ggan_conv2d_bwd_data')
+        g = _geom(geom)
+        check(_L().ggan_conv2d_bwd_data(C.byref(g), _p(gy), _p(w), _p(_c(bias)) if bias is not None else _p(None),
+                                        _p(gx), act, alpha, _p(ws), ws.numel(), _stream()), 'ggan_conv2d_bwd_data')
         ctx.geom, ctx.act, ctx.alpha, ctx.has_bias = geom, act, alpha, bias is not None
         ctx.save_for_backward(gy, w, gx if act != ACT_NONE else None)
         return gx
@@ -202,21 +195,18 @@ class ConvDgrad(Function):
                 reg[d_b.data_ptr()] = (n.value, Cc, part)
         elif ctx.act != ACT_NONE:
             h = ActBwd.apply(h, out, ctx.act, ctx.alpha)
-        tgt = _bwd_target(ctx)
         if ctx.needs_input_grad[1]:
-            with _planned_for(tgt):
-                parts = _wgrad_parts(_c(h), gy, None, ACT_NONE, 0.0, ctx.geom, False) if not torch.is_grad_enabled() else None
-                d_w = parts[0] if parts is not None else ConvWgrad.apply(h, gy, ctx.geom)
+            parts = _wgrad_parts(_c(h), gy, None, ACT_NONE, 0.0, ctx.geom, False) if not torch.is_grad_enabled() else None
+            d_w = parts[0] if parts is not None else ConvWgrad.apply(h, gy, ctx.geom)
         if ctx.has_bias and ctx.needs_input_grad[2] and d_b is None:
             pre = getattr(h, '_ggan_chansum', None) if not torch.is_grad_enabled() else None
             d_b = pre if (pre is not None and pre.numel() == h.shape[1]) else ChanSum.apply(h)
         if ctx.needs_input_grad[0]:
-            with target_workgroups(tgt):
-                d_gy = ConvFwd.apply(h, w, None, ctx.geom, ACT_NONE, 0.0)
+            d_gy = ConvFwd.apply(h, w, None, ctx.geom, ACT_NONE, 0.0)
         return (d_gy, d_w, d_b) + (None,) * (len(ctx.needs_input_grad) - 3)
 
 
-@_carries_hint
+@_remembers_plan
 @_skip_undefined
 class ConvDgradMasked(Function):
     """gx = conv^T(gy * act'(yref), w): ActBwd + ConvDgrad as one differentiable op (ggan_conv2d_bwd_data_act stages gy through the
@@ -231,7 +221,6 @@ class ConvDgradMasked(Function):
         assert tuple(gy.shape) == (N, Co, Ho, Wo) == tuple(yref.shape), (gy.shape, yref.shape, geom)
         gx = torch.empty((N, Ci, H, W), dtype=torch.float32, device=gy.device)
         ws = workspace(gy.device)
-        ctx.target = getattr(_PLAN, 'both', 0)            # (set by the layer whose backward this op is; its own backward launches follow it)
         g = _geom(geom)
         check(_L().ggan_conv2d_bwd_data_act(C.byref(g), _p(gy), _p(yref), act, alpha, _p(w), _p(gx), _p(ws), ws.numel(), _stream()),
               'ggan_conv2d_bwd_data_act')
@@ -254,8 +243,7 @@ class ConvDgradMasked(Function):
             return d_gy, None, d_w, None, None, None
         h = _c(h)
         N, Ci, H, W, Co, Ho, Wo, k = geom[:8]
-        with _planned_for(ctx.target):
-            g = _geom(geom)
+        g = _geom(geom)
         L, ws = _L(), workspace(h.device)
         if ctx.needs_input_grad[0]:
             d_gy = torch.empty((N, Co, Ho, Wo), dtype=torch.float32, device=h.device)
@@ -281,7 +269,7 @@ class ConvDgradMasked(Function):
         return d_gy, None, d_w, None, None, None
 
 
-@_carries_hint
+@_remembers_plan
 @_skip_undefined
 class ConvWgrad(Function):
     """gw[k,k,Ci,Co] = sum_n,oh,ow x (*) gy  (Conv2DBackpropFilter)."""

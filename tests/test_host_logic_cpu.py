@@ -124,6 +124,69 @@ def test_site_plan_scope():
             assert F._geom(g1).plan_wgs == 128 and rec.log is None
 
 
+def test_layer_plan_carries_from_forward_to_backward():
+    """functional._remembers_plan: a layer's backward -- its launches and the Functions applied in it -- plans with the (target, hint) in
+    force when the layer was recorded, on whichever thread it runs (here a fresh one, as autograd's device worker is), and with the
+    default target under serial_backward(), which the thread that calls backward sets for the worker to read"""
+    import contextlib
+    import threading
+    import torch
+    from graphical_gan_amd import functional as F
+    t = F.conv_geom(4, 8, 16, 16, 16, 5, 2)
+    seen = []
+
+    def note(tag):
+        g = F._geom(t)
+        seen.append((tag, g.plan_wgs, g.plan_wgs_filter))
+
+    @F._remembers_plan
+    class Inner(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x):
+            note('inner')
+            return x.clone()
+
+        @staticmethod
+        def backward(ctx, g):
+            return g
+
+    @F._remembers_plan
+    class Layer(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x):
+            note('fwd')
+            return x.clone()
+
+        @staticmethod
+        def backward(ctx, g):
+            note('bwd')
+            return Inner.apply(g)
+
+    def run(record, serial):
+        del seen[:]
+        x = torch.zeros(2, requires_grad=True)
+        with contextlib.ExitStack() as st:
+            for c in record:
+                st.enter_context(c)
+            y = Layer.apply(x).sum()
+        with (F.serial_backward() if serial else contextlib.nullcontext()):
+            th = threading.Thread(target=y.backward)
+            th.start(); th.join()
+        assert x.grad is not None and [s[0] for s in seen] == ['fwd', 'bwd', 'inner'], seen
+        assert seen[1][1:] == seen[2][1:]              # a Function applied inside the backward records the backward's plan
+        assert all(s[1] == s[2] for s in seen)         # (plan_wgs_filter follows plan_wgs)
+        note('after')
+        assert seen[3] == ('after', 0, 0)              # nothing left set on this thread
+        return seen[0][1], seen[1][1]
+
+    assert run([], False) == (0, 0)
+    assert run([F.launch_hint(128)], False) == (128, 128)
+    assert run([F.launch_hint(128), F.target_workgroups(96)], False) == (96, 96)
+    assert run([F.launch_hint(128), F.target_workgroups(96)], True) == (96, 128)
+    assert run([F.target_workgroups(96)], True) == (96, 0)
+    assert not F._SERIAL_BWD[0]
+
+
 def test_flat_layout_is_aligned():
     from graphical_gan_amd.optim import layout_slots
     slots, total = layout_slots([5, 64, 100, 1])
