@@ -986,9 +986,9 @@ int launch_cfg(int cfg, const CorrParams& P, dim3 grid, size_t shmem, hipStream_
         allow_big_lds(corr_kernel<0, 2, 1, 4, 1>); allow_big_lds(corr_kernel<0, 1, 1, 8, 1>);
         allow_big_lds(corr_kernel<1, 2, 1, 4, 2>); allow_big_lds(corr_kernel<1, 1, 1, 8, 1>);
         allow_big_lds(corr_kernel<0, 2, 2, 2, 1>); allow_big_lds(corr_kernel<1, 2, 2, 2, 2>);
-        allow_big_lds(corr_kernel<2, 2, 1, 2, 2>); allow_big_lds(corr_kernel<2, 2, 1, 4, 1>); allow_big_lds(corr_kernel<2, 1, 1, 8, 1>);
-        allow_big_lds(corr_kernel<2, 2, 2, 2, 1>); allow_big_lds(corr_kernel<0, 2, 1, 4, 2>); allow_big_lds(corr_kernel<2, 2, 1, 4, 2>);
-        allow_big_lds(corr_kernel<0, 4, 1, 2, 2>); allow_big_lds(corr_kernel<2, 4, 1, 2, 2>);
+        allow_big_lds(corr_kernel<2, 2, 1, 2, 2>); allow_big_lds(corr_kernel<2, 1, 1, 8, 1>);
+        allow_big_lds(corr_kernel<2, 2, 2, 2, 1>); allow_big_lds(corr_kernel<2, 2, 1, 4, 2>);
+        allow_big_lds(corr_kernel<0, 4, 1, 2, 2>);
         allow_big_lds(corr_kernel<0, 2, 1, 4, 1, true>); allow_big_lds(corr_kernel<0, 1, 1, 8, 1, true>); allow_big_lds(corr_kernel<0, 2, 2, 2, 1, true>);
         allow_big_lds(corr_kernel<0, 4, 1, 2, 2, true>);
         allow_big_lds(corr_kernel<1, 2, 1, 4, 2, true>); allow_big_lds(corr_kernel<1, 1, 1, 8, 1, true>);
@@ -1030,11 +1030,18 @@ int launch_cfg(int cfg, const CorrParams& P, dim3 grid, size_t shmem, hipStream_
     if constexpr (MODE == 0 || MODE == 2) {
         switch (cfg) {
             case 1: GGAN_LAUNCH((MODE == 0 ? "corr_kernel<0, 2, 1, 2, 2, false>" : "corr_kernel<2, 2, 1, 2, 2, false>"), fl, ab, (corr_kernel<MODE, 2, 1, 2, 2>), grid, dim3(256), shmem, s, P); break;
-            case 4: GGAN_LAUNCH((MODE == 0 ? "corr_kernel<0, 2, 1, 4, 1, false>" : "corr_kernel<2, 2, 1, 4, 1, false>"), fl, ab, (corr_kernel<MODE, 2, 1, 4, 1>), grid, dim3(512), shmem, s, P); break;
+            // (plan_and_launch offers layouts 4 and 8 to the forward kind only and layout 7 to the all-class data gradient only)
+            case 4:
+                if constexpr (MODE == 0) { GGAN_LAUNCH("corr_kernel<0, 2, 1, 4, 1, false>", fl, ab, (corr_kernel<0, 2, 1, 4, 1>), grid, dim3(512), shmem, s, P); break; }
+                set_error("%s: no variant of wave layout %d", name, cfg); return -3;
             case 5: GGAN_LAUNCH((MODE == 0 ? "corr_kernel<0, 1, 1, 8, 1, false>" : "corr_kernel<2, 1, 1, 8, 1, false>"), fl, ab, (corr_kernel<MODE, 1, 1, 8, 1>), grid, dim3(512), shmem, s, P); break;
             case 6: GGAN_LAUNCH((MODE == 0 ? "corr_kernel<0, 2, 2, 2, 1, false>" : "corr_kernel<2, 2, 2, 2, 1, false>"), fl, ab, (corr_kernel<MODE, 2, 2, 2, 1>), grid, dim3(512), shmem, s, P); break;
-            case 7: GGAN_LAUNCH((MODE == 0 ? "corr_kernel<0, 2, 1, 4, 2, false>" : "corr_kernel<2, 2, 1, 4, 2, false>"), fl, ab, (corr_kernel<MODE, 2, 1, 4, 2>), grid, dim3(512), shmem, s, P); break;
-            case 8: GGAN_LAUNCH((MODE == 0 ? "corr_kernel<0, 4, 1, 2, 2, false>" : "corr_kernel<2, 4, 1, 2, 2, false>"), fl, ab, (corr_kernel<MODE, 4, 1, 2, 2>), grid, dim3(512), shmem, s, P); break;
+            case 7:
+                if constexpr (MODE == 2) { GGAN_LAUNCH("corr_kernel<2, 2, 1, 4, 2, false>", fl, ab, (corr_kernel<2, 2, 1, 4, 2>), grid, dim3(512), shmem, s, P); break; }
+                set_error("%s: no variant of wave layout %d", name, cfg); return -3;
+            case 8:
+                if constexpr (MODE == 0) { GGAN_LAUNCH("corr_kernel<0, 4, 1, 2, 2, false>", fl, ab, (corr_kernel<0, 4, 1, 2, 2>), grid, dim3(512), shmem, s, P); break; }
+                set_error("%s: no variant of wave layout %d", name, cfg); return -3;
             default: set_error("%s: no variant of wave layout %d", name, cfg); return -3;
         }
     } else {
@@ -1223,6 +1230,9 @@ int plan_and_launch(CorrParams& P, int Hu, int Wv, int su, int ext_r, int ext_c,
             }
         }
     }
+    if (getenv("GGAN_TRACE_CONV"))      // what a kernel name cannot show (tests/test_conv_dispatch_gpu.py reads this line)
+        fprintf(stderr, "[ggan] plan %s mode=%d cfg=%d tile=(%d,%d,%d) xq=%d SK=%d xcd_p=%d grid=(%d,%d,%d) %s\n", name, MODE, cfg, P.TI, P.TR,
+                P.TC, P.xq, P.SK, P.xcd_p, gx, gy, groups * P.SK, P.xtab ? "table" : "no-table");
     int rc = launch_cfg<MODE>(cfg, P, dim3(gx, gy, groups * P.SK), shmem, s, name, fl);
     if (rc) return rc;
     if (P.SK > 1)

@@ -1642,7 +1642,9 @@ def test_dg16_data_gradient(gpu, case, kq, variant, monkeypatch):
     L.ggan_prof_enable(0)
     names = [r['name'] for r in _lib.prof_report()]
     L.ggan_prof_reset()
-    assert any(n.startswith('dg16_kernel<') for n in names), names
+    # the exact instance: tile columns min(Wo, 16) + 8 slab columns, the forced KQ, masked staging or not
+    expect = 'dg16_kernel<%d, %d, %s>' % (min(Ho, 16) + 8, kq, 'true' if variant == 'masked' else 'false')
+    assert [n for n in names if n.startswith('dg16_kernel<')] == [expect], (names, expect)
     assert _rel(gx.cpu().numpy(), ref) < TOL
 
 

@@ -214,7 +214,11 @@ def test_conv_layer_second_order_dg16(gpu, registry, case, route, monkeypatch):
     monkeypatch.setenv('GGAN_DG16_FORCE', '1')
     L = _lib.load()
     _, names = _prof_names(L, lambda: _conv_case(gpu, registry, case, route, 3 + sum(case[1:5])))
-    assert any(n.startswith('dg16_kernel<') for n in names), names
+    # the exact instances: tile columns min(Wo, 16) + 8 slab columns; 16-channel tiles (KQ 4: these grids are below the default plan)
+    Wo = -(-case[3] // 2)
+    expect = ['dg16_kernel<%d, 4, %s>' % (min(Wo, 16) + 8, m) for m in ('false', 'true')]
+    dg16 = [n for n in names if n.startswith('dg16_kernel<')]
+    assert dg16 and all(n in expect for n in dg16), (names, expect)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
