@@ -937,8 +937,47 @@ __global__ void splitk_reduce_small_k(const float* __restrict__ partial, int SK,
 struct WaveCfg { int WM, WN, KS, PW; };
 // fwd: 25 taps per chunk-channel-pair; dgrad class pairs carry only 12-13 taps, so they stage twice as many channels per
 // chunk (PW doubled) to keep ~25+ MFMAs per wave between barriers
-const WaveCfg kCfgsFwd[9] = {{2, 2, 1, 2}, {2, 1, 2, 2}, {1, 1, 4, 1}, {1, 1, 4, 2}, {2, 1, 4, 1}, {1, 1, 8, 1}, {2, 2, 2, 1}, {2, 1, 4, 2}, {4, 1, 2, 2}};
-const WaveCfg kCfgsDgrad[9] = {{2, 2, 1, 4}, {2, 1, 2, 4}, {1, 1, 4, 2}, {1, 1, 4, 4}, {2, 1, 4, 2}, {1, 1, 8, 1}, {2, 2, 2, 2}, {1, 1, 8, 2}, {1, 1, 8, 2}};
+constexpr int kNumCfgs = 9;
+constexpr WaveCfg kCfgsFwd[kNumCfgs] = {{2, 2, 1, 2}, {2, 1, 2, 2}, {1, 1, 4, 1}, {1, 1, 4, 2}, {2, 1, 4, 1}, {1, 1, 8, 1}, {2, 2, 2, 1}, {2, 1, 4, 2}, {4, 1, 2, 2}};
+constexpr WaveCfg kCfgsDgrad[kNumCfgs] = {{2, 2, 1, 4}, {2, 1, 2, 4}, {1, 1, 4, 2}, {1, 1, 4, 4}, {2, 1, 4, 2}, {1, 1, 8, 1}, {2, 2, 2, 2}, {1, 1, 8, 2}, {1, 1, 8, 2}};
+constexpr const WaveCfg* cfgs_of(int mode) { return mode == 1 ? kCfgsDgrad : kCfgsFwd; }
+
+// Every corr_kernel instance, once: X(MODE, WM, WN, KS, PW, X4).  The table below is all the host knows of them -- the launch, the
+// LDS opt-in, the profiler name (as rocprofv3 prints the instantiation) and which layouts have a 16-byte-unit variant all read it.
+#define CORR_EACH(X)                                                                                                        \
+    X(0, 2, 1, 2, 2, false) X(0, 2, 1, 4, 1, false) X(0, 1, 1, 8, 1, false) X(0, 2, 2, 2, 1, false) X(0, 4, 1, 2, 2, false) \
+    X(0, 2, 1, 4, 1, true) X(0, 1, 1, 8, 1, true) X(0, 2, 2, 2, 1, true) X(0, 4, 1, 2, 2, true)                             \
+    X(1, 2, 1, 2, 4, false) X(1, 2, 1, 4, 2, false) X(1, 1, 1, 8, 1, false) X(1, 2, 2, 2, 2, false)                         \
+    X(1, 2, 1, 4, 2, true) X(1, 1, 1, 8, 1, true)                                                                           \
+    X(2, 2, 1, 2, 2, false) X(2, 1, 1, 8, 1, false) X(2, 2, 2, 2, 1, false) X(2, 2, 1, 4, 2, false)                         \
+    X(2, 1, 1, 8, 1, true) X(2, 2, 2, 2, 1, true) X(2, 2, 1, 4, 2, true)
+struct CorrInst { int mode; WaveCfg wc; bool x4; const char* name; void (*kernel)(const CorrParams); };
+#define CORR_INST(MODE, WM, WN, KS, PW, X4) \
+    {MODE, {WM, WN, KS, PW}, X4, "corr_kernel<" #MODE ", " #WM ", " #WN ", " #KS ", " #PW ", " #X4 ">", corr_kernel<MODE, WM, WN, KS, PW, X4>},
+constexpr CorrInst kCorrInsts[] = {CORR_EACH(CORR_INST)};
+#undef CORR_INST
+#undef CORR_EACH
+
+constexpr const CorrInst* find_inst(int mode, const WaveCfg& wc, bool x4) {
+    for (const CorrInst& k : kCorrInsts)
+        if (k.mode == mode && k.wc.WM == wc.WM && k.wc.WN == wc.WN && k.wc.KS == wc.KS && k.wc.PW == wc.PW && k.x4 == x4) return &k;
+    return nullptr;
+}
+// x4: the variant that stages its slab in 16-byte units (plan_and_launch offers it only where it exists)
+constexpr bool has_inst(int mode, int cfg, bool x4) { return find_inst(mode, cfgs_of(mode)[cfg], x4) != nullptr; }
+
+// The wave layouts plan_and_launch chooses among, largest tile first: the forward kind all of kOrderFwd, the class pairs the same from
+// its second entry, the all-class data gradient kOrderAll from its second entry; fewer than 8 reduction channels override to 1 or 6.
+constexpr int kOrderFwd[4] = {8, 6, 4, 5}, kOrderAll[4] = {8, 6, 7, 5};
+constexpr const int* order_of(int mode) { return mode == 2 ? kOrderAll : kOrderFwd; }
+constexpr int order_begin(int mode) { return mode == 0 ? 0 : 1; }
+constexpr bool planner_covered(int mode) {
+    for (int oi = order_begin(mode); oi < 4; ++oi)
+        if (!has_inst(mode, order_of(mode)[oi], false)) return false;
+    return has_inst(mode, 1, false) && has_inst(mode, 6, false);
+}
+static_assert(planner_covered(0) && planner_covered(1) && planner_covered(2),
+              "plan_and_launch offers a wave layout that has no entry in CORR_EACH");
 
 // pixel tile TI x TR x TC <= TM whose CK-channel slab fits the per-thread staging budget
 bool pick_tile(CorrParams& P, int Hu, int Wv, int TM, int CK, int su, int ext_r, int ext_c) {
@@ -968,91 +1007,18 @@ bool finish_tile(CorrParams& P, int Hu, int Wv) {
     return true;
 }
 
-template <typename K>
-void allow_big_lds(K kernel) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-}
-
-// wave layouts of the data-gradient kinds that have a 16-byte-unit variant (launch_cfg)
-bool dgrad_x4_cfg(int mode, int cfg) { return mode == 1 ? (cfg == 4 || cfg == 5) : (cfg == 5 || cfg == 6 || cfg == 7); }
-
 template <int MODE>
 int launch_cfg(int cfg, const CorrParams& P, dim3 grid, size_t shmem, hipStream_t s, const char* name, double fl) {
     // algorithmic bytes of the launch: input + filter + output, one pass each (SURVEY.md App. B "bytes")
     const double ab = (double)P.in_bytes + (double)P.w_bytes + 4.0 * (double)P.out_elems;
     static std::atomic<unsigned long long> once{0};
-    if (first_on_device(once)) {   // double-buffered staging can exceed the 64 KiB default dynamic-LDS limit
-        allow_big_lds(corr_kernel<0, 2, 1, 2, 2>); allow_big_lds(corr_kernel<1, 2, 1, 2, 4>);
-        allow_big_lds(corr_kernel<0, 2, 1, 4, 1>); allow_big_lds(corr_kernel<0, 1, 1, 8, 1>);
-        allow_big_lds(corr_kernel<1, 2, 1, 4, 2>); allow_big_lds(corr_kernel<1, 1, 1, 8, 1>);
-        allow_big_lds(corr_kernel<0, 2, 2, 2, 1>); allow_big_lds(corr_kernel<1, 2, 2, 2, 2>);
-        allow_big_lds(corr_kernel<2, 2, 1, 2, 2>); allow_big_lds(corr_kernel<2, 1, 1, 8, 1>);
-        allow_big_lds(corr_kernel<2, 2, 2, 2, 1>); allow_big_lds(corr_kernel<2, 2, 1, 4, 2>);
-        allow_big_lds(corr_kernel<0, 4, 1, 2, 2>);
-        allow_big_lds(corr_kernel<0, 2, 1, 4, 1, true>); allow_big_lds(corr_kernel<0, 1, 1, 8, 1, true>); allow_big_lds(corr_kernel<0, 2, 2, 2, 1, true>);
-        allow_big_lds(corr_kernel<0, 4, 1, 2, 2, true>);
-        allow_big_lds(corr_kernel<1, 2, 1, 4, 2, true>); allow_big_lds(corr_kernel<1, 1, 1, 8, 1, true>);
-        allow_big_lds(corr_kernel<2, 1, 1, 8, 1, true>); allow_big_lds(corr_kernel<2, 2, 1, 4, 2, true>); allow_big_lds(corr_kernel<2, 2, 2, 2, 1, true>);
-    }
+    if (first_on_device(once))     // double-buffered staging can exceed the 64 KiB default dynamic-LDS limit
+        for (const CorrInst& k : kCorrInsts)
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k.kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (shmem > 160 * 1024) { set_error("%s: LDS request %zu too large", name, shmem); return -3; }
-    if constexpr (MODE == 0) {
-        if (P.xq == 4) {       // slab staged in 16-byte units (the 8-wave layouts only: plan_and_launch)
-            switch (cfg) {
-                case 4: GGAN_LAUNCH("corr_kernel<0, 2, 1, 4, 1, true>", fl, ab, (corr_kernel<0, 2, 1, 4, 1, true>), grid, dim3(512), shmem, s, P); break;
-                case 5: GGAN_LAUNCH("corr_kernel<0, 1, 1, 8, 1, true>", fl, ab, (corr_kernel<0, 1, 1, 8, 1, true>), grid, dim3(512), shmem, s, P); break;
-                case 6: GGAN_LAUNCH("corr_kernel<0, 2, 2, 2, 1, true>", fl, ab, (corr_kernel<0, 2, 2, 2, 1, true>), grid, dim3(512), shmem, s, P); break;
-                case 8: GGAN_LAUNCH("corr_kernel<0, 4, 1, 2, 2, true>", fl, ab, (corr_kernel<0, 4, 1, 2, 2, true>), grid, dim3(512), shmem, s, P); break;
-                default: set_error("%s: no 16-byte-unit variant of wave layout %d", name, cfg); return -3;
-            }
-            return 0;
-        }
-    }
-    if constexpr (MODE == 2) {
-        if (P.xq == 4) {
-            switch (cfg) {
-                case 5: GGAN_LAUNCH("corr_kernel<2, 1, 1, 8, 1, true>", fl, ab, (corr_kernel<2, 1, 1, 8, 1, true>), grid, dim3(512), shmem, s, P); break;
-                case 6: GGAN_LAUNCH("corr_kernel<2, 2, 2, 2, 1, true>", fl, ab, (corr_kernel<2, 2, 2, 2, 1, true>), grid, dim3(512), shmem, s, P); break;
-                default: GGAN_LAUNCH("corr_kernel<2, 2, 1, 4, 2, true>", fl, ab, (corr_kernel<2, 2, 1, 4, 2, true>), grid, dim3(512), shmem, s, P); break;
-            }
-            return 0;
-        }
-    }
-    if constexpr (MODE == 1) {
-        if (P.xq == 4) {
-            switch (cfg) {
-                case 4: GGAN_LAUNCH("corr_kernel<1, 2, 1, 4, 2, true>", fl, ab, (corr_kernel<1, 2, 1, 4, 2, true>), grid, dim3(512), shmem, s, P); break;
-                case 5: GGAN_LAUNCH("corr_kernel<1, 1, 1, 8, 1, true>", fl, ab, (corr_kernel<1, 1, 1, 8, 1, true>), grid, dim3(512), shmem, s, P); break;
-                default: set_error("%s: no 16-byte-unit variant of wave layout %d", name, cfg); return -3;
-            }
-            return 0;
-        }
-    }
-    if constexpr (MODE == 0 || MODE == 2) {
-        switch (cfg) {
-            case 1: GGAN_LAUNCH((MODE == 0 ? "corr_kernel<0, 2, 1, 2, 2, false>" : "corr_kernel<2, 2, 1, 2, 2, false>"), fl, ab, (corr_kernel<MODE, 2, 1, 2, 2>), grid, dim3(256), shmem, s, P); break;
-            // (plan_and_launch offers layouts 4 and 8 to the forward kind only and layout 7 to the all-class data gradient only)
-            case 4:
-                if constexpr (MODE == 0) { GGAN_LAUNCH("corr_kernel<0, 2, 1, 4, 1, false>", fl, ab, (corr_kernel<0, 2, 1, 4, 1>), grid, dim3(512), shmem, s, P); break; }
-                set_error("%s: no variant of wave layout %d", name, cfg); return -3;
-            case 5: GGAN_LAUNCH((MODE == 0 ? "corr_kernel<0, 1, 1, 8, 1, false>" : "corr_kernel<2, 1, 1, 8, 1, false>"), fl, ab, (corr_kernel<MODE, 1, 1, 8, 1>), grid, dim3(512), shmem, s, P); break;
-            case 6: GGAN_LAUNCH((MODE == 0 ? "corr_kernel<0, 2, 2, 2, 1, false>" : "corr_kernel<2, 2, 2, 2, 1, false>"), fl, ab, (corr_kernel<MODE, 2, 2, 2, 1>), grid, dim3(512), shmem, s, P); break;
-            case 7:
-                if constexpr (MODE == 2) { GGAN_LAUNCH("corr_kernel<2, 2, 1, 4, 2, false>", fl, ab, (corr_kernel<2, 2, 1, 4, 2>), grid, dim3(512), shmem, s, P); break; }
-                set_error("%s: no variant of wave layout %d", name, cfg); return -3;
-            case 8:
-                if constexpr (MODE == 0) { GGAN_LAUNCH("corr_kernel<0, 4, 1, 2, 2, false>", fl, ab, (corr_kernel<0, 4, 1, 2, 2>), grid, dim3(512), shmem, s, P); break; }
-                set_error("%s: no variant of wave layout %d", name, cfg); return -3;
-            default: set_error("%s: no variant of wave layout %d", name, cfg); return -3;
-        }
-    } else {
-        switch (cfg) {
-            case 1: GGAN_LAUNCH("corr_kernel<1, 2, 1, 2, 4, false>", fl, ab, (corr_kernel<1, 2, 1, 2, 4>), grid, dim3(256), shmem, s, P); break;
-            case 4: GGAN_LAUNCH("corr_kernel<1, 2, 1, 4, 2, false>", fl, ab, (corr_kernel<1, 2, 1, 4, 2>), grid, dim3(512), shmem, s, P); break;
-            case 5: GGAN_LAUNCH("corr_kernel<1, 1, 1, 8, 1, false>", fl, ab, (corr_kernel<1, 1, 1, 8, 1>), grid, dim3(512), shmem, s, P); break;
-            case 6: GGAN_LAUNCH("corr_kernel<1, 2, 2, 2, 2, false>", fl, ab, (corr_kernel<1, 2, 2, 2, 2>), grid, dim3(512), shmem, s, P); break;
-            default: set_error("%s: no data-gradient variant of wave layout %d", name, cfg); return -3;
-        }
-    }
+    const CorrInst* k = cfg >= 0 && cfg < kNumCfgs ? find_inst(MODE, cfgs_of(MODE)[cfg], P.xq == 4) : nullptr;
+    if (!k) { set_error("%s: no %d-byte-unit variant of wave layout %d", name, P.xq == 4 ? 16 : 4, cfg); return -3; }
+    GGAN_LAUNCH(k->name, fl, ab, k->kernel, grid, dim3(64 * k->wc.WM * k->wc.WN * k->wc.KS), shmem, s, P);
     return 0;
 }
 
@@ -1105,7 +1071,7 @@ int plan_and_launch(CorrParams& P, int Hu, int Wv, int su, int ext_r, int ext_c,
                     const float* bias, int act, float alpha, void* ws, size_t ws_bytes, hipStream_t s, const char* name,
                     double fl, const char* sk_env, OutMask* mask = nullptr) {
     const int target = P.plan_wgs > 0 ? P.plan_wgs : kTargetWgs;
-    const WaveCfg* kCfgs = MODE == 1 ? kCfgsDgrad : kCfgsFwd;
+    const WaveCfg* kCfgs = cfgs_of(MODE);
     // 8 waves per workgroup (two per SIMD: one wave's LDS / barrier stalls hide under the other's MFMAs; measured
     // 12-19 % faster than the 4-wave layouts).  Largest tile that still yields ~one workgroup per CU.
     // 128x32, 64x64, 64x32, 32x32 (pixels x channels).  The filter slice is 2/3 of what a 64x32 workgroup stages per chunk and
@@ -1115,10 +1081,9 @@ int plan_and_launch(CorrParams& P, int Hu, int Wv, int su, int ext_r, int ext_c,
     //  goes by LDS-DMA with 8-byte fragment reads: 47.4 vs 53.9 us on the 64->128 layer at 128 images)
     // (class pairs on 32x32 tiles with 32-channel chunks measured equal to the 16-channel chunks, 33.6 vs 33.9 us on the 128->256
     //  layer: the time per chunk follows the staged bytes, not the barriers)
-    static const int order_fwd[4] = {8, 6, 4, 5}, order_all[4] = {8, 6, 7, 5};
-    const int* order = MODE == 2 ? order_all : order_fwd;
+    const int* order = order_of(MODE);
     int cfg = 5;
-    for (int oi = MODE == 0 ? 0 : 1; oi < 4; ++oi) {
+    for (int oi = order_begin(MODE); oi < 4; ++oi) {
         const int c = order[oi];
         const WaveCfg& wc = kCfgs[c];
         const int CK = 2 * wc.KS * wc.PW, TM = 32 * wc.WM, TNW = 32 * wc.WN;
@@ -1140,7 +1105,7 @@ int plan_and_launch(CorrParams& P, int Hu, int Wv, int su, int ext_r, int ext_c,
     P.dma = (MODE == 0 || (CK % 16 == 0 && wc.PW <= 2)) && (P.dbg & 3) == 0;
     const int RS = TNW + (MODE != 0 ? 2 : 0);     // filter row stride in LDS (corr_body: padded for the k-contiguous staging)
     P.xq = 1;
-    if (MODE == 0 && cfg >= 4 && P.dma && (P.Win & 3) == 0 && (((uintptr_t)P.in) & 15) == 0 && ((su * P.TC) & 3) == 0) {
+    if (MODE == 0 && has_inst(MODE, cfg, true) && P.dma && (P.Win & 3) == 0 && (((uintptr_t)P.in) & 15) == 0 && ((su * P.TC) & 3) == 0) {
         // Slab rows in 16-byte units of the image rows: a dword-gather DMA instruction costs the texture path ~64 cycles (a lane
         // per cycle) and the slab took 6 of them per wave and chunk -- as much texture-path time as the chunk has MFMA time.  With
         // the slab columns shifted so that LDS column c holds image column (unit-aligned start) + c, a lane moves 4 floats, and
@@ -1162,7 +1127,7 @@ int plan_and_launch(CorrParams& P, int Hu, int Wv, int su, int ext_r, int ext_c,
             P.CS = (int)cs4;
         }
     }
-    if (MODE != 0 && dgrad_x4_cfg(MODE, cfg) && (P.Win & 3) == 0 && (((uintptr_t)P.in) & 15) == 0 &&
+    if (MODE != 0 && has_inst(MODE, cfg, true) && (P.Win & 3) == 0 && (((uintptr_t)P.in) & 15) == 0 &&
         (((uintptr_t)P.in_ref) & 15) == 0 && ((su * P.TC) & 3) == 0) {
         // The same units for the register-staged slab of the data-gradient kinds: a thread fetches and commits 4 floats of an image
         // row per instruction (the 8-wave layouts staged 3 dwords per thread and chunk, twice that with the activation mask).

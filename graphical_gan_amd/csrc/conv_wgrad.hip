@@ -423,6 +423,11 @@ template <int W_> struct W4Geom {
 
 template <int W> struct WaveTag { static constexpr int value = W; };
 
+// The image widths wgrad4_kernel is compiled for, once: the LDS opt-ins, the launches (profiler names as rocprofv3 prints the
+// instantiations) and the geometry selection of both translation units expand this list.
+#define WGRAD4_EACH(X) X(8) X(16) X(32) X(64)
+#define WGRAD_BIG_LDS(K) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+
 // SPLIT (round 5, experiment GGAN_WGRAD_SPLIT=1): eight waves with the roles split -- waves 0-3 (one per SIMD) only read fragments and
 // multiply, waves 4-7 (their SIMD partners) only stage the next chunk -- so that no staging instruction sits in an MFMA stream.
 template <int GW, bool SPLIT = false>
@@ -835,18 +840,16 @@ int wgrad4_split_launch(int W, unsigned grid, size_t shmem, hipStream_t s, const
     WgradParams P;
     memcpy(&P, params, sizeof(P));
     static std::atomic<unsigned long long> attr_set{0};
-    if (first_on_device(attr_set)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad4_kernel<16, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad4_kernel<8, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad4_kernel<32, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad4_kernel<64, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    }
+#define W4_ATTR(GW) WGRAD_BIG_LDS((wgrad4_kernel<GW, true>))
+    if (first_on_device(attr_set)) { WGRAD4_EACH(W4_ATTR) }
+#undef W4_ATTR
     const dim3 grid4(grid);
-    if (W == 16) { GGAN_LAUNCH("wgrad4_kernel<16, true>", fl, ab, (wgrad4_kernel<16, true>), grid4, dim3(2 * W4_NTHR), shmem, s, P); }
-    else if (W == 8) { GGAN_LAUNCH("wgrad4_kernel<8, true>", fl, ab, (wgrad4_kernel<8, true>), grid4, dim3(2 * W4_NTHR), shmem, s, P); }
-    else if (W == 32) { GGAN_LAUNCH("wgrad4_kernel<32, true>", fl, ab, (wgrad4_kernel<32, true>), grid4, dim3(2 * W4_NTHR), shmem, s, P); }
-    else { GGAN_LAUNCH("wgrad4_kernel<64, true>", fl, ab, (wgrad4_kernel<64, true>), grid4, dim3(2 * W4_NTHR), shmem, s, P); }
-    return 0;
+#define W4_CASE(GW) \
+    if (W == GW) { GGAN_LAUNCH("wgrad4_kernel<" #GW ", true>", fl, ab, (wgrad4_kernel<GW, true>), grid4, dim3(2 * W4_NTHR), shmem, s, P); return 0; }
+    WGRAD4_EACH(W4_CASE)
+#undef W4_CASE
+    set_error("conv_wgrad: no role-split kernel for image width %d", W);
+    return -3;
 }
 }  // namespace ggan
 #else
@@ -913,10 +916,9 @@ int conv_wgrad_mfma(const ggan_conv_geom& g, const float* x, const float* gy, Gy
     };
     int four = 0;
     if (env_int("GGAN_WGRAD_W4", 1) != 0) {
-        if (geom_is(W4Geom<16>{})) four = 16;
-        else if (geom_is(W4Geom<8>{})) four = 8;
-        else if (geom_is(W4Geom<32>{})) four = 32;
-        else if (geom_is(W4Geom<64>{})) four = 64;
+#define W4_PICK(GW) if (!four && geom_is(W4Geom<GW>{})) four = GW;
+        WGRAD4_EACH(W4_PICK)
+#undef W4_PICK
     }
     if (!four && !plan_chunk(128, TCO, NTHR) && !plan_chunk(64, TCO, NTHR)) return 1;
     const int tco = four ? W4_TCO : TCO;
@@ -945,15 +947,9 @@ int conv_wgrad_mfma(const ggan_conv_geom& g, const float* x, const float* gy, Gy
     const size_t shmem = (stage > red ? stage : red) * sizeof(float);
     if (shmem > 160 * 1024) return 1;
     static std::atomic<unsigned long long> attr_set{0};
-    if (first_on_device(attr_set)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad4_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad4_kernel<16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad4_kernel<32>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad4_kernel<64>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    }
+#define W4_ATTR(GW) WGRAD_BIG_LDS(wgrad4_kernel<GW>)
+    if (first_on_device(attr_set)) { WGRAD_BIG_LDS(wgrad_kernel<0>) WGRAD_BIG_LDS(wgrad_kernel<1>) WGRAD_BIG_LDS(wgrad_kernel<2>) WGRAD4_EACH(W4_ATTR) }
+#undef W4_ATTR
     const int nit = P.PC == 128 ? 2 : (P.PC == 64 ? 1 : 0);
     const double fl = 2.0 * g.N * g.Co * g.Ho * g.Wo * (double)g.Ci * 25.0;
     const double ab = 4.0 * ((double)g.N * g.Ci * g.H * g.W + (double)g.N * g.Co * g.Ho * g.Wo + 25.0 * g.Ci * g.Co);
@@ -962,10 +958,9 @@ int conv_wgrad_mfma(const ggan_conv_geom& g, const float* x, const float* gy, Gy
     const dim3 grid4(gx * gy_ * P.SK);       // split-fastest workgroup numbering (decoded in the kernel)
     const bool split_roles = env_int("GGAN_WGRAD_SPLIT", 1) != 0;          // (read per call, like GGAN_WGRAD_W4 / _SK)
     if (split_roles && four > 0) { const int rc = wgrad4_split_launch(four, grid4.x, shmem, s, &P, fl, ab); if (rc) return rc; }
-    else if (four == 16) { GGAN_LAUNCH("wgrad4_kernel<16>", fl, ab, wgrad4_kernel<16>, grid4, dim3(W4_NTHR), shmem, s, P); }
-    else if (four == 8) { GGAN_LAUNCH("wgrad4_kernel<8>", fl, ab, wgrad4_kernel<8>, grid4, dim3(W4_NTHR), shmem, s, P); }
-    else if (four == 32) { GGAN_LAUNCH("wgrad4_kernel<32>", fl, ab, wgrad4_kernel<32>, grid4, dim3(W4_NTHR), shmem, s, P); }
-    else if (four == 64) { GGAN_LAUNCH("wgrad4_kernel<64>", fl, ab, wgrad4_kernel<64>, grid4, dim3(W4_NTHR), shmem, s, P); }
+#define W4_CASE(GW) else if (four == GW) { GGAN_LAUNCH("wgrad4_kernel<" #GW ">", fl, ab, wgrad4_kernel<GW>, grid4, dim3(W4_NTHR), shmem, s, P); }
+    WGRAD4_EACH(W4_CASE)
+#undef W4_CASE
     else if (nit == 2) { GGAN_LAUNCH("wgrad_kernel<2>", fl, ab, wgrad_kernel<2>, dim3(gx, gy_, P.SK), dim3(NTHR), shmem, s, P); }
     else if (nit == 1) { GGAN_LAUNCH("wgrad_kernel<1>", fl, ab, wgrad_kernel<1>, dim3(gx, gy_, P.SK), dim3(NTHR), shmem, s, P); }
     else { GGAN_LAUNCH("wgrad_kernel<0>", fl, ab, wgrad_kernel<0>, dim3(gx, gy_, P.SK), dim3(NTHR), shmem, s, P); }

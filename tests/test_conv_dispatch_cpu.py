@@ -1,7 +1,8 @@
-"""The coverage table tests/_conv_dispatch.py against the sources: every kernel name the conv2d family launches (the literal first
-arguments of GGAN_LAUNCH in csrc/conv_corr.hip, conv_wgrad.hip, conv_thin.hip, conv_naive.hip, both arms of the `MODE == 0 ? .. : ..`
-pairs, and the dg16_kernel<SCP, KQ, masked> names conv_dg16.hip's macros spell) has a row, no row names a kernel the sources no
-longer launch, and the table keeps the cases it was written for.  Reads the project's own sources for kernel names only."""
+"""The coverage table tests/_conv_dispatch.py against the sources: every kernel name the conv2d family launches (the names the
+instance lists CORR_EACH of csrc/conv_corr.hip, WGRAD4_EACH of conv_wgrad.hip and DG16_EACH of conv_dg16.hip spell through their
+stringising forms, and the literal first arguments of GGAN_LAUNCH in those files, conv_thin.hip and conv_naive.hip) has a row, no
+row names a kernel the sources no longer launch, and the table keeps the cases it was written for.  Reads the project's own sources
+for kernel names only."""
 import os
 import re
 
@@ -23,12 +24,26 @@ def launched_names(text):
     return out
 
 
-def dg16_names(text):
-    each = re.search(r'#define DG16_EACH\(X\)(.*)', text).group(1)
-    pairs = re.findall(r'X\((\d+), (\d+)\)', each)
-    forms = re.findall(r'GGAN_LAUNCH\("dg16_kernel<" #SCP ", " #KQ ", (true|false)>"', text)
-    assert pairs and sorted(forms) == ['false', 'true'], (pairs, forms)
-    return set('dg16_kernel<%s, %s, %s>' % (scp, kq, f) for scp, kq in pairs for f in forms)
+_FORM = re.compile(r'"([^"\n]*)"((?:\s*#\w+\s*"[^"\n]*")+)')
+EACH = (('conv_corr.hip', 'CORR_EACH', 'corr_kernel<', 1), ('conv_wgrad.hip', 'WGRAD4_EACH', 'wgrad4_kernel<', 2),
+        ('conv_dg16.hip', 'DG16_EACH', 'dg16_kernel<', 2))          # (file, instance list, name prefix, stringising forms)
+
+
+def each_names(text, each, prefix, nforms):
+    """the names an instance list spells: every `X(..)` entry of `#define <each>(X) X(..) X(..)` (continuation lines included) put
+    through every stringising form `"<prefix>" #A ", " #B ">"` of the text; #A, #B are parameters of the `#define` the form stands in"""
+    body = re.search(r'#define %s\(X\)((?:.*\\\n)*.*)' % each, text).group(1)
+    entries = [[a.strip() for a in e.split(',')] for e in re.findall(r'X\(([^()]*)\)', body)]
+    forms = [f for f in _FORM.finditer(text) if f.group(1).startswith(prefix)]
+    assert entries and len(forms) == nforms, (each, entries, [f.group(0) for f in forms])
+    names = set()
+    for f in forms:
+        params = [p.strip() for p in re.findall(r'#define \w+\(([^)]*)\)', text[:f.start()])[-1].split(',')]
+        for e in entries:
+            assert len(e) == len(params), (each, e, params)
+            value = dict(zip(params, e))
+            names.add(f.group(1) + ''.join(value[p] + lit for p, lit in re.findall(r'#(\w+)\s*"([^"\n]*)"', f.group(2))))
+    return names
 
 
 def _read(name, csrc=CSRC):
@@ -40,7 +55,9 @@ def family_names(csrc=CSRC):
     names = set()
     for f in FAMILY:
         names |= launched_names(_read(f, csrc))
-    return names | dg16_names(_read('conv_dg16.hip', csrc))
+    for f, each, prefix, nforms in EACH:
+        names |= each_names(_read(f, csrc), each, prefix, nforms)
+    return names
 
 
 def uncovered(csrc=CSRC):
@@ -56,6 +73,18 @@ def test_parser_reads_both_arms_and_plain_literals():
             'GGAN_LAUNCH("other_k", 0, 0, other_k, dim3(1), dim3(256), 0, s, P);\n'
             '    if (P.MT == 8) { GGAN_LAUNCH("thin", fl, 0, (thin<NT_, true, 8>), grid, dim3(512), shmem, s, P); } \\\n')
     assert launched_names(text) == {'k<0, 1, false>', 'k<2, 1, false>', 'other_k', 'thin'}
+
+
+def test_list_reader_follows_continuation_lines_and_every_form():
+    text = ('#define K_EACH(X)   \\\n    X(0, 2, false) X(1, 4, true) \\\n    X(2, 8, true)\n'
+            '#define K_ATTR(A, B, C) opt_in(k<A, B, C>);\n'
+            '#define K_INST(MODE, PW, X4) {MODE, PW, X4, "k<" #MODE ", " #PW ", " #X4 ">", k<MODE, PW, X4>},\n'
+            '#define W_EACH(X) X(8) X(16)\n'
+            '#define W_CASE(GW) if (w == GW) { GGAN_LAUNCH("w4<" #GW ">", fl, ab, w4<GW>, grid, dim3(256), shmem, s, P); } \\\n'
+            '    else { GGAN_LAUNCH("w4<" #GW ", true>", fl, ab, (w4<GW, true>), grid, dim3(512), shmem, s, P); }\n')
+    assert each_names(text, 'K_EACH', 'k<', 1) == {'k<0, 2, false>', 'k<1, 4, true>', 'k<2, 8, true>'}
+    assert each_names(text, 'W_EACH', 'w4<', 2) == {'w4<8>', 'w4<16>', 'w4<8, true>', 'w4<16, true>'}
+    assert not launched_names(text)
 
 
 def test_every_launched_kernel_has_a_row_and_every_row_a_launch():
@@ -86,6 +115,25 @@ def test_a_scratch_copy_with_one_more_instance_is_caught(tmp_path):
         (tmp_path / f).write_text(text)
     missing, stale = uncovered(str(tmp_path))
     assert missing == ['conv_wgrad_plain', 'corr_kernel<1, 1, 1, 4, 4, false>'] and stale == ['conv_wgrad_naive'], (missing, stale)
+
+
+def test_a_scratch_copy_with_one_more_list_entry_is_caught(tmp_path):
+    """a copy of the sources with one more X(..) entry in the corr and the wgrad4 instance lists and one entry fewer in the dg16 list"""
+    for f in FAMILY + ('conv_dg16.hip',):
+        text = _read(f)
+        if f == 'conv_corr.hip':
+            assert text.count('X(1, 2, 1, 2, 4, false)') == 1
+            text = text.replace('X(1, 2, 1, 2, 4, false)', 'X(1, 2, 1, 2, 4, false) X(1, 1, 1, 4, 4, false)')
+        if f == 'conv_wgrad.hip':
+            assert text.count('X(32) X(64)') == 1
+            text = text.replace('X(32) X(64)', 'X(32) X(64) X(128)')
+        if f == 'conv_dg16.hip':
+            assert text.count(' X(24, 2)') == 1
+            text = text.replace(' X(24, 2)', '')
+        (tmp_path / f).write_text(text)
+    missing, stale = uncovered(str(tmp_path))
+    assert missing == ['corr_kernel<1, 1, 1, 4, 4, false>', 'wgrad4_kernel<128, true>', 'wgrad4_kernel<128>'], missing
+    assert stale == ['dg16_kernel<24, 2, false>', 'dg16_kernel<24, 2, true>'], stale
 
 
 def test_rows_are_well_formed():
