@@ -1,0 +1,292 @@
+// Set-level mixture-of-RBF kernel sums between two row sets (tflib/objs/mmd.py:20-67 at dev-set sizes): for X[m,d], Y[n,d]
+//   S_xx = sum_{i != j} k(x_i, x_j),  S_yy likewise,  S_xy = sum_{i,j} k(x_i, y_j),  k(a,b) = sum_s wt_s exp(-||a-b||^2 / (2 sigma_s^2))
+// from which both MMD^2 estimators follow (include/ggan.h).  ggan_mix_rbf_mmd2_fwd (pointwise.hip) forms direct differences on one
+// scalar workgroup per row and stops at m + n = 512; here the Gram product runs on v_mfma_f32_32x32x2_f32 and nothing of size
+// (m+n)^2 ever reaches memory.
+//
+// The two sets are ONE row list Z = [X; Y] of T = m + n rows, cut into blocks of 128.  A tile is a pair of blocks (a, b): 128x128
+// dot products g_ij from LDS-staged k-major operand tiles (both operands are k-contiguous in memory, as op(B) of gemm.hip with
+// tb = 1), 2x2 waves of 64x64, four 32x32 accumulators per wave.  The epilogue forms max(n_i + n_j - 2 g_ij, 0) from the row norms
+// of a pre-pass, the mixture of exponentials, and adds the value to the sum its PAIR belongs to -- decided per element from
+// (i < m, j < m), so a tile may straddle the X / Y boundary or hang over the end of Z.
+//
+// Symmetry: k(z_i, z_j) = k(z_j, z_i), so of the nb x nb tiles only one of (a, b) / (b, a) is computed.  Block a visits
+// b = (a + t) mod nb for t = 0 .. nb/2 (the last step, when nb is even, only from the lower half of the blocks): every unordered pair of
+// blocks exactly once, and every block the same number of tiles.  A visited element stands for both orders of its pair: it counts twice
+// in S_xx / S_yy and once in S_xy; on the diagonal tile (t = 0) only i < j is counted, which also drops i == j.
+//
+// Reduction: workgroup (a, s) walks the steps t = s, s + S, ... of block a, accumulates each tile in float per thread (<= 64 values),
+// the tiles in double, and leaves ONE partial triple; the last stage adds the nb * S triples in a fixed order in double.  No atomics: two
+// calls on the same input give the same bits.  S is chosen so that nb * S is about 2048 workgroups, so the workspace (T norms + nb * S
+// triples) is linear in m + n.
+#include "common.h"
+using namespace ggan;
+
+namespace {
+
+constexpr int BT = 128;            // rows of Z per block: a tile is BT x BT
+constexpr int KS = 16;             // k per main-loop step
+constexpr int LD = BT + 4;         // LDS tile row (floats): 4 * LD = 16 (mod 64), the four k-quads of a staging wave hit disjoint banks
+constexpr int kMaxSigmas = 8;
+constexpr int kMaxRows = 131072;
+constexpr int kTargetWgs = 2048;
+
+struct SetParams {
+    const float* X;
+    const float* Y;
+    const float* norms;            // [T] squared row norms of Z
+    double* part;                  // [nb * S][3]
+    int m, T, d, ns;
+    int nb, S;
+    int vec;                       // float4 loads legal on every row (d % 4 == 0 and both bases 16-byte aligned)
+    float g2[kMaxSigmas];          // log2(e) / (2 sigma^2): exp(-gamma D) = exp2(-g2 D)
+    float wt[kMaxSigmas];
+};
+
+__device__ __forceinline__ const float* z_row(const SetParams& P, int r) {
+    return r < P.m ? P.X + (size_t)r * P.d : P.Y + (size_t)(r - P.m) * P.d;
+}
+
+// four consecutive k of row r of Z (zeros beyond T or d), without a branch: the address is clamped into the row list and into the row, the
+// value dropped afterwards -- every load of a step can then be in flight at once (guarded loads compile to "load; wait" chains).
+// VEC (d % 4 == 0 and both bases 16-byte aligned, so every row is): one 16-byte load; k is a multiple of 4, so k < d means k + 3 < d.
+// !VEC (rows of odd d are not 16-byte aligned): four dword loads, each with its own range test.
+template <bool VEC>
+__device__ __forceinline__ float4 load4(const SetParams& P, int r, int k) {
+    const float* row = z_row(P, min(r, P.T - 1));
+    const bool rok = r < P.T;
+    if (VEC) {
+        const float4 t = *reinterpret_cast<const float4*>(row + min(k, P.d - 4));
+        const bool ok = rok && k < P.d;
+        return make_float4(ok ? t.x : 0.f, ok ? t.y : 0.f, ok ? t.z : 0.f, ok ? t.w : 0.f);
+    }
+    float v[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const float t = row[min(k + j, P.d - 1)];
+        v[j] = (rok && k + j < P.d) ? t : 0.f;
+    }
+    return make_float4(v[0], v[1], v[2], v[3]);
+}
+
+// squared norms: one wave per row, lane-strided fma chains combined by the wave's butterfly (a fixed order)
+__global__ __launch_bounds__(256) void set_norms_k(const SetParams P, float* __restrict__ norms) {
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (r >= P.T) return;
+    const float* z = z_row(P, r);
+    float s = 0.f;
+    for (int k = lane; k < P.d; k += 64) s = fmaf(z[k], z[k], s);
+    s = wave_sum(s);
+    if (lane == 0) norms[r] = s;
+}
+
+// is step t of block a a tile to compute (see the head of the file)
+__device__ __forceinline__ bool step_valid(int a, int t, int nb) { return 2 * t < nb || (2 * t == nb && 2 * a < nb) || t == 0; }
+
+// NS: the number of kernel widths (their constants then live in scalar registers for the whole epilogue; a run-time count made every
+// element's loop re-read them from the argument block).  VEC: see load4.
+template <int NS, bool VEC>
+__global__ __launch_bounds__(256) void set_sums_k(const SetParams P) {
+    warm_kernarg(P);
+    __shared__ __attribute__((aligned(16))) float As[2][KS * LD];
+    __shared__ __attribute__((aligned(16))) float Bs[2][KS * LD];
+    __shared__ float nA[BT], nB[BT];
+    __shared__ double red[4][3];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave & 1, wn = wave >> 1, half = lane >> 5, l31 = lane & 31;
+    const int a = blockIdx.x, s = blockIdx.y;
+    double dxx = 0.0, dyy = 0.0, dxy = 0.0;
+    float g2[NS], wt[NS];
+#pragma unroll
+    for (int q = 0; q < NS; ++q) { g2[q] = P.g2[q]; wt[q] = P.wt[q]; }
+
+    // staging: unit u of a thread is 4 consecutive k of one tile row; 4 lanes cover the 16 k of a row (64 contiguous bytes)
+    auto load_step = [&](int r0a, int r0b, int k0, float4 (&xa)[2], float4 (&xb)[2]) {
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int unit = tid + 256 * u, row = unit >> 2, k = k0 + (unit & 3) * 4;
+            xa[u] = load4<VEC>(P, r0a + row, k);
+            xb[u] = load4<VEC>(P, r0b + row, k);
+        }
+    };
+    auto store_step = [&](int buf, const float4 (&xa)[2], const float4 (&xb)[2]) {
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int unit = tid + 256 * u, row = unit >> 2, kq = unit & 3;
+            float* da = &As[buf][(kq * 4) * LD + row];
+            float* db = &Bs[buf][(kq * 4) * LD + row];
+            da[0] = xa[u].x; da[LD] = xa[u].y; da[2 * LD] = xa[u].z; da[3 * LD] = xa[u].w;
+            db[0] = xb[u].x; db[LD] = xb[u].y; db[2 * LD] = xb[u].z; db[3 * LD] = xb[u].w;
+        }
+    };
+
+    // the steps of this workgroup: t = s, s + S, ... as far as they are tiles to compute (uniform over the workgroup)
+    const int nt = P.nb / 2 + 1;
+    auto next_step = [&](int t) {
+        while (t < nt && !step_valid(a, t, P.nb)) t += P.S;
+        return t;
+    };
+    const int r0a = a * BT;
+    float4 ra[2], rb[2];
+    int t = next_step(s);
+    if (t < nt) load_step(r0a, ((a + t) % P.nb) * BT, 0, ra, rb);
+    while (t < nt) {
+        const int b = (a + t) % P.nb;
+        const int r0b = b * BT;
+        if (tid < BT) nA[tid] = r0a + tid < P.T ? P.norms[r0a + tid] : 0.f;
+        else nB[tid - BT] = r0b + tid - BT < P.T ? P.norms[r0b + tid - BT] : 0.f;
+
+        f32x16 acc[2][2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+        store_step(0, ra, rb);                               // (the first step of a tile is loaded ahead: above, or behind the last tile's k loop)
+        __syncthreads();
+        int buf = 0;
+        for (int k0 = 0; k0 < P.d; k0 += KS) {
+            const bool more = k0 + KS < P.d;
+            if (more) load_step(r0a, r0b, k0 + KS, ra, rb);        // in flight while the MFMA block runs
+            const float* Ab = As[buf];
+            const float* Bb = Bs[buf];
+#pragma unroll
+            for (int kk = 0; kk < KS / 2; ++kk) {
+                const int k = 2 * kk + half;
+                const float a0 = Ab[k * LD + wm * 64 + l31], a1 = Ab[k * LD + wm * 64 + 32 + l31];
+                const float b0 = Bb[k * LD + wn * 64 + l31], b1 = Bb[k * LD + wn * 64 + 32 + l31];
+                acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
+                acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
+                acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
+                acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
+            }
+            if (more) store_step(buf ^ 1, ra, rb);
+            __syncthreads();
+            buf ^= 1;
+        }
+
+        const int tn = next_step(t + P.S);
+        if (tn < nt) load_step(r0a, ((a + tn) % P.nb) * BT, 0, ra, rb);       // the next tile's first step, in flight during the epilogue
+
+        // epilogue: accumulator register r of lane l is g[row (r & 3) + 8 (r >> 2) + 4 (l >> 5)][column l & 31] of its 32x32 block
+        float fxx = 0.f, fyy = 0.f, fxy = 0.f;
+        const bool diag = t == 0;
+#pragma unroll
+        for (int bj = 0; bj < 2; ++bj) {
+            const int jl = wn * 64 + bj * 32 + l31, j = r0b + jl;
+            const float nj = nB[jl];
+            const bool jx = j < P.m;
+#pragma unroll
+            for (int bi = 0; bi < 2; ++bi) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int il = wm * 64 + bi * 32 + (r & 3) + 8 * (r >> 2) + 4 * half, i = r0a + il;
+                    const bool on = i < P.T && j < P.T && (!diag || i < j);
+                    const float dist = fmaxf(nA[il] + nj - 2.f * acc[bi][bj][r], 0.f);
+                    float kv = 0.f;
+                    #pragma unroll
+                    for (int q = 0; q < NS; ++q) kv = fmaf(wt[q], __builtin_amdgcn_exp2f(-g2[q] * dist), kv);
+                    kv = on ? kv : 0.f;
+                    const bool ix = i < P.m;
+                    fxx += (ix && jx) ? 2.f * kv : 0.f;
+                    fyy += (!ix && !jx) ? 2.f * kv : 0.f;
+                    fxy += (ix != jx) ? kv : 0.f;
+                }
+            }
+        }
+        dxx += (double)fxx; dyy += (double)fyy; dxy += (double)fxy;
+        __syncthreads();                                   // nA / nB are rewritten by the next tile
+        t = tn;
+    }
+
+    // the workgroup's triple: lanes by the wave's butterfly, the four waves in wave order
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        dxx += __shfl_xor(dxx, o, 64);
+        dyy += __shfl_xor(dyy, o, 64);
+        dxy += __shfl_xor(dxy, o, 64);
+    }
+    if (lane == 0) { red[wave][0] = dxx; red[wave][1] = dyy; red[wave][2] = dxy; }
+    __syncthreads();
+    if (tid < 3) P.part[((size_t)a * P.S + s) * 3 + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+}
+
+// last stage: thread i adds triples i, i + 256, ... in that order, then a fixed tree over the 256 threads
+__global__ __launch_bounds__(256) void set_final_k(const double* __restrict__ part, int count, double* __restrict__ sums3) {
+    __shared__ double sm[256];
+    const int tid = threadIdx.x;
+    for (int c = 0; c < 3; ++c) {
+        double v = 0.0;
+        for (int i = tid; i < count; i += 256) v += part[(size_t)i * 3 + c];
+        sm[tid] = v;
+        __syncthreads();
+        for (int o = 128; o > 0; o >>= 1) {
+            if (tid < o) sm[tid] += sm[tid + o];
+            __syncthreads();
+        }
+        if (tid == 0) sums3[c] = sm[0];
+        __syncthreads();
+    }
+}
+
+inline int blocks_of(int m, int n) { return (int)(((long)m + n + BT - 1) / BT); }
+inline int splits_of(int nb) {
+    const int nt = nb / 2 + 1;
+    int S = (kTargetWgs + nb - 1) / nb;
+    if (S > nt) S = nt;
+    return S < 1 ? 1 : S;
+}
+inline size_t norms_bytes(int m, int n) { return ((size_t)((long)m + n) * sizeof(float) + 15) & ~(size_t)15; }
+
+}  // namespace
+
+extern "C" {
+
+size_t ggan_mix_rbf_sums_workspace(int m, int n) {
+    if (m < 1 || n < 1 || m > kMaxRows || n > kMaxRows) return 0;
+    const int nb = blocks_of(m, n);
+    return norms_bytes(m, n) + (size_t)nb * splits_of(nb) * 3 * sizeof(double);
+}
+
+int ggan_mix_rbf_sums(const float* X, const float* Y, int m, int n, int d, const float* sigmas, const float* wts, int ns,
+                      double* sums3, void* ws, size_t ws_bytes, ggan_stream_t stream) {
+    GGAN_CHECK_ARG(X && Y && sigmas && sums3 && ws, "null pointer");
+    GGAN_CHECK_ARG(m >= 1 && n >= 1 && m <= kMaxRows && n <= kMaxRows, "1 <= m, n <= 131072");
+    GGAN_CHECK_ARG(d >= 1, "d < 1");
+    GGAN_CHECK_ARG(ns >= 1 && ns <= kMaxSigmas, "1 <= ns <= 8");
+    GGAN_CHECK_ARG(ws_bytes >= ggan_mix_rbf_sums_workspace(m, n), "workspace too small (ggan_mix_rbf_sums_workspace)");
+    GGAN_CHECK_ARG(((uintptr_t)ws & 15) == 0 && ((uintptr_t)sums3 & 7) == 0, "workspace must be 16-byte, sums3 8-byte aligned");
+    for (int i = 0; i < ns; ++i) GGAN_CHECK_ARG(sigmas[i] > 0.f, "sigma <= 0");
+    SetParams P;
+    P.X = X; P.Y = Y; P.m = m; P.T = m + n; P.d = d; P.ns = ns;
+    P.nb = blocks_of(m, n);
+    P.S = splits_of(P.nb);
+    P.vec = (d % 4 == 0) && ((uintptr_t)X & 15) == 0 && ((uintptr_t)Y & 15) == 0;
+    for (int i = 0; i < kMaxSigmas; ++i) {
+        P.g2[i] = i < ns ? (float)(1.4426950408889634 / (2.0 * (double)sigmas[i] * (double)sigmas[i])) : 0.f;
+        P.wt[i] = i < ns ? (wts ? wts[i] : 1.f) : 0.f;
+    }
+    float* norms = (float*)ws;
+    P.norms = norms;
+    P.part = (double*)((char*)ws + norms_bytes(m, n));
+    hipStream_t st = (hipStream_t)stream;
+    GGAN_LAUNCH("mmd_set_norms", 2.0 * P.T * d, 4.0 * P.T * d, set_norms_k, dim3(cdiv(P.T, 4)), dim3(256), 0, st, P, norms);
+    // tiles computed: nb diagonal ones and nb (nb - 1) / 2 pairs
+    const double tiles = 0.5 * (double)P.nb * (P.nb + 1);
+    const double flops = tiles * 2.0 * BT * BT * d, bytes = tiles * 2.0 * BT * d * 4.0;
+#define SUMS_CASE(NS)                                                                                                                  \
+    case NS:                                                                                                                           \
+        if (P.vec) { GGAN_LAUNCH("mmd_set_sums", flops, bytes, (set_sums_k<NS, true>), dim3(P.nb, P.S), dim3(256), 0, st, P); }        \
+        else { GGAN_LAUNCH("mmd_set_sums", flops, bytes, (set_sums_k<NS, false>), dim3(P.nb, P.S), dim3(256), 0, st, P); }             \
+        break;
+    switch (ns) {
+        SUMS_CASE(1) SUMS_CASE(2) SUMS_CASE(3) SUMS_CASE(4) SUMS_CASE(5) SUMS_CASE(6) SUMS_CASE(7) SUMS_CASE(8)
+    }
+#undef SUMS_CASE
+    GGAN_LAUNCH("mmd_set_final", 0, 24.0 * P.nb * P.S, set_final_k, dim3(1), dim3(256), 0, st, (const double*)P.part, P.nb * P.S, sums3);
+    return 0;
+}
+
+}  // extern "C"

@@ -1344,6 +1344,7 @@ struct MmdParams {
     const float* Y;
     int m, n, d, ns;
     float gamma[kMmdMaxSigmas], wt[kMmdMaxSigmas];
+    int unbiased;      // mmd.py:53-61: the diagonal of the same-set blocks is left out, the means are over m (m - 1) and n (n - 1) pairs
 };
 
 __device__ __forceinline__ const float* mmd_row(const MmdParams& P, int r) { return r < P.m ? P.X + (size_t)r * P.d : P.Y + (size_t)(r - P.m) * P.d; }
@@ -1352,6 +1353,10 @@ __device__ __forceinline__ const float* mmd_row(const MmdParams& P, int r) { ret
 // pair is visited from both sides, which makes the -2/(mn) of the definition)
 __device__ __forceinline__ float mmd_coef(const MmdParams& P, int r, int j) {
     const bool rx = r < P.m, jx = j < P.m;
+    if (P.unbiased && rx == jx) {
+        if (r == j) return 0.f;
+        return rx ? 1.f / ((float)P.m * (float)(P.m - 1)) : 1.f / ((float)P.n * (float)(P.n - 1));
+    }
     if (rx && jx) return 1.f / ((float)P.m * (float)P.m);
     if (!rx && !jx) return 1.f / ((float)P.n * (float)P.n);
     return -1.f / ((float)P.m * (float)P.n);
@@ -1897,9 +1902,11 @@ int ggan_noise_fill(float* const* dsts, const size_t* sizes, const int* kinds, c
     return 0;
 }
 
-static int mmd_params(MmdParams& P, const float* X, const float* Y, int m, int n, int d, const float* sigmas, const float* wts, int ns) {
+static int mmd_params(MmdParams& P, const float* X, const float* Y, int m, int n, int d, const float* sigmas, const float* wts, int ns,
+                      int unbiased = 0) {
     if (!(X && Y && sigmas) || m <= 0 || n <= 0 || d <= 0 || ns <= 0 || ns > kMmdMaxSigmas || m + n > 512) return -1;
-    P.X = X; P.Y = Y; P.m = m; P.n = n; P.d = d; P.ns = ns;
+    if (unbiased && (m < 2 || n < 2)) return -1;
+    P.X = X; P.Y = Y; P.m = m; P.n = n; P.d = d; P.ns = ns; P.unbiased = unbiased;
     for (int i = 0; i < ns; ++i) {
         P.gamma[i] = 1.f / (2.f * sigmas[i] * sigmas[i]);
         P.wt[i] = wts ? wts[i] : 1.f;
@@ -1921,6 +1928,23 @@ int ggan_mix_rbf_mmd2_bwd(const float* X, const float* Y, int m, int n, int d, c
     MmdParams P;
     GGAN_CHECK_ARG(mmd_params(P, X, Y, m, n, d, sigmas, wts, ns) == 0 && gout && (dX || dY), "bad argument");
     GGAN_LAUNCH("mmd2_bwd", 5.0 * (m + n) * (m + n) * d, 0, mmd2_bwd_k, dim3(m + n), dim3(256), 0, (hipStream_t)stream, P, gout, dX, dY);
+    return 0;
+}
+
+int ggan_mix_rbf_mmd2_unbiased_fwd(const float* X, const float* Y, int m, int n, int d, const float* sigmas, const float* wts, int ns,
+                                   float* out, float* row_scratch, ggan_stream_t stream) {
+    MmdParams P;
+    GGAN_CHECK_ARG(mmd_params(P, X, Y, m, n, d, sigmas, wts, ns, 1) == 0 && out && row_scratch, "bad argument");
+    GGAN_LAUNCH("mmd2u_rows", 3.0 * (m + n) * (m + n) * d, 0, mmd2_rows_k, dim3(m + n), dim3(256), 0, (hipStream_t)stream, P, row_scratch);
+    GGAN_LAUNCH("mmd2_final", 0, 0, mmd2_final_k, dim3(1), dim3(64), 0, (hipStream_t)stream, (const float*)row_scratch, m + n, out);
+    return 0;
+}
+
+int ggan_mix_rbf_mmd2_unbiased_bwd(const float* X, const float* Y, int m, int n, int d, const float* sigmas, const float* wts, int ns,
+                                   const float* gout, float* dX, float* dY, ggan_stream_t stream) {
+    MmdParams P;
+    GGAN_CHECK_ARG(mmd_params(P, X, Y, m, n, d, sigmas, wts, ns, 1) == 0 && gout && (dX || dY), "bad argument");
+    GGAN_LAUNCH("mmd2u_bwd", 5.0 * (m + n) * (m + n) * d, 0, mmd2_bwd_k, dim3(m + n), dim3(256), 0, (hipStream_t)stream, P, gout, dX, dY);
     return 0;
 }
 

@@ -10,7 +10,10 @@
   reconstructions    reconstruct_image: real / Generator(Extractor(x)) pairs on a fixed dev minibatch (gmgan_inference_mnist.py:429-443);
   manifold           the latent-space pictures of the MNIST scripts (gan_inference_mnist.py:472-480, gmgan_inference_mnist.py:533-551):
                      q_z (and p_z, and the images) of the labelled dev set embedded by functional.tsne on the device, scattered by
-                     tflib.visualization coloured by digit / mixture component / inferred component.
+                     tflib.visualization coloured by digit / mixture component / inferred component;
+  mmd_scores         `dev mmd z` / `dev mmd x`: the unbiased mixture-of-RBF MMD^2 (tflib/objs/mmd.py:20-67, sigmas 2..80) between the aggregate
+                     posterior q(z) and the prior p(z), and between the dev images and as many generated ones -- two set-level sums of
+                     ggan_mix_rbf_sums.  Not a pass of the reference's loops: the stand-in for its inception score (README).
 
 The passes are safe in the middle of training: they run under torch.no_grad() on the current stream only (no second stream, no
 collective), with a feed dict and a noise generator state of their own -- the Trainer's static feed buffers, ring slots and noise state
@@ -30,7 +33,7 @@ run by SequenceEvaluator on a models_ssgan.StateSpaceGAN under the same rules:
 Each is written as a .png sheet (one sequence per row) and a looping .gif; the bytes of both come from one ggan_video_sheet_u8 launch.
 
 `python -m graphical_gan_amd.evaluate CKPT --script gmgan_inference_mnist [--data-dir DIR]` scores a saved checkpoint
-(`--out-dir DIR --manifold` also writes the latent-space pictures of the two MNIST scripts);
+(`--out-dir DIR --manifold` also writes the latent-space pictures of the two MNIST scripts, `--mmd` adds the two MMD^2 rows);
 `... CKPT --script ssgan_inference_moving_mnist|ssgan_inference_chairs [--data-dir DIR] --out-dir DIR` writes the four pairs of files."""
 import argparse
 import contextlib
@@ -43,6 +46,7 @@ import torch
 from . import functional as F
 from . import tflib as lib
 
+MMD_MAX_ROWS = 10000      # rows per set of the mmd_scores pass (settings: MMD_MAX_ROWS)
 EVAL_SEED = 7919          # offset of the evaluator's noise seeds from the settings seed (the Trainer's stream of draws is not touched)
 
 # the reference's output file names, per script: (samples, reconstructions), formatted with frame= and mode=
@@ -254,6 +258,36 @@ class Evaluator(_Passes):
                     _, q_k = self.model.HyperExtractor(q_z, self.feed.get('gumbel_u'))
                     out['qk'][rows].copy_(torch.argmax(q_k, dim=1))
         return out
+
+    def mmd_scores(self, batches, return_sets=False):
+        """{'dev mmd z': unbiased MMD^2(q_z, p_z), 'dev mmd x': unbiased MMD^2(real_x, Generator(p_z))} over the full dev minibatches, at
+        most MMD_MAX_ROWS rows per set: z = q_z (the sampled code of the aggregated-posterior MODEs, as latent_sets), pz = as many fresh
+        prior draws (through HyperGenerator with a mixture prior), x = real_x as the nets see it, gx = Generator(pz) minibatch by minibatch.
+        The sets stay on the device; the two values come back in ONE host synchronisation.  return_sets: (values, {z, pz, x, gx})."""
+        c = self.cfg
+        with self._guard():
+            X, _ = self._stage(batches)
+            B = c.B
+            n = min(X.shape[0], max(1, int(self.S.get('MMD_MAX_ROWS', MMD_MAX_ROWS)) // B))
+            if n * B < 2:
+                raise ValueError('the unbiased MMD needs at least 2 rows per set')
+            new = lambda w: torch.empty((n * B, w), dtype=torch.float32, device=self.device)
+            sets = dict(z=new(c.dim_latent), pz=new(c.dim_latent), x=new(c.output_dim), gx=new(c.output_dim))
+            self.kept = []
+            for i in range(n):
+                rows = slice(i * B, (i + 1) * B)
+                self._load(X[i])
+                real_x = self.model.real_x(self.feed)
+                q = self.model.Extractor(real_x, eps=self.feed['q_eps']) if c.agg else self.model.Extractor(real_x)
+                sets['z'][rows].copy_(q[0] if isinstance(q, tuple) else q)
+                sets['x'][rows].copy_(real_x.float())
+                p_z = self.model.HyperGenerator(self.feed['k_onehot'], self.feed['p_z_noise']) if c.K else self.feed['p_z_noise']
+                sets['pz'][rows].copy_(p_z)
+                sets['gx'][rows].copy_(self.model.Generator(sets['pz'][rows]).float())
+            vals = torch.stack([lib.objs.mmd.mix_rbf_mmd2(sets['z'], sets['pz'], biased=False),
+                                lib.objs.mmd.mix_rbf_mmd2(sets['x'], sets['gx'], biased=False)]).cpu().numpy()
+        res = {'dev mmd z': float(vals[0]), 'dev mmd x': float(vals[1])}
+        return (res, sets) if return_sets else res
 
     def manifold(self, batches, out_dir, frame):
         """embeds the point sets of latent_sets with functional.tsne and writes the scatters under the reference's file names; returns
@@ -507,6 +541,7 @@ def main(argv=None):
     ap.add_argument('--mode', default=None, help="the script's MODE (default: the script's own)")
     ap.add_argument('--out-dir', default=None, help='also write the sample grid and the reconstructions here (the state-space scripts: the video files, required)')
     ap.add_argument('--manifold', action='store_true', help='also write the latent-space t-SNE pictures of the MNIST scripts to --out-dir')
+    ap.add_argument('--mmd', action='store_true', help='also score the dev set by the unbiased MMD^2 of codes and of images (dev mmd z / dev mmd x; image scripts)')
     ap.add_argument('--set', action='append', default=[], metavar='KEY=VALUE', help='override an UPPERCASE setting (int / float / str)')
     a = ap.parse_args(argv)
     over = {}
@@ -521,6 +556,8 @@ def main(argv=None):
         over[k] = v
     if a.mode:
         over['MODE'] = a.mode
+    if a.mmd and os.path.splitext(os.path.basename(a.script))[0] in run._SEQUENCE_SCRIPTS:
+        ap.error('--mmd: the state-space scripts have no single code to compare')
     if a.manifold:          # (checked before anything is built)
         name = os.path.splitext(os.path.basename(a.script))[0]
         if name not in MANIFOLD_SCRIPTS:
@@ -537,14 +574,15 @@ def main(argv=None):
         model = StateSpaceGAN(cfg)
     tr = Trainer(cfg, device=lib.get_device(), graph=False, model=model)
     checkpoint.restore(a.ckpt, tr)
-    res = evaluate_once(tr, S, out_dir=a.out_dir, manifold=a.manifold)
+    res = evaluate_once(tr, S, out_dir=a.out_dir, manifold=a.manifold, mmd=a.mmd)
     for k in sorted(res):
         print('%s\t%s' % (k, res[k]))
     return res
 
 
-def evaluate_once(tr, S, out_dir=None, frame='eval', manifold=False):
-    """every pass the script's data allow, once -> {name: value}; manifold: the latent-space pictures too (labelled dev data only)"""
+def evaluate_once(tr, S, out_dir=None, frame='eval', manifold=False, mmd=False):
+    """every pass the script's data allow, once -> {name: value}; manifold: the latent-space pictures too (labelled dev data only);
+    mmd: the two dev-set MMD^2 scores too"""
     from . import run
     if S['DATASET'] in run.SEQUENCE_DATASETS:       # the video passes: files only (train_data: the first dev minibatch)
         ev = SequenceEvaluator(tr, S)
@@ -557,6 +595,8 @@ def evaluate_once(tr, S, out_dir=None, frame='eval', manifold=False):
     res = dict(ev.dev_costs(dev))
     if tr.cfg.K and test is not None:
         res['testing accuracy'] = ev.cluster_accuracy(test)
+    if mmd:
+        res.update(ev.mmd_scores(dev))
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
         ev.set_fixed_data(dev[0])

@@ -248,38 +248,88 @@ class GmmLatentST(Function):
         return (dz, dmu) + (None,) * (n_in - 2)
 
 
+def _mmd2_forward(ctx, name, x, y, sigmas, wts):
+    x, y = _c(x), _c(y)
+    m, d = x.shape
+    n = y.shape[0]
+    assert y.shape[1] == d
+    ns = len(sigmas)
+    sg = (C.c_float * ns)(*[float(v) for v in sigmas])
+    wt = (C.c_float * ns)(*[float(v) for v in wts]) if wts is not None else None
+    out = torch.empty((), dtype=torch.float32, device=x.device)
+    scratch = torch.empty((m + n,), dtype=torch.float32, device=x.device)
+    check(getattr(_L(), name)(_p(x), _p(y), m, n, d, sg, wt, ns, _p(out), _p(scratch), _stream()), name)
+    ctx.sg, ctx.wt, ctx.ns = sg, wt, ns
+    ctx.save_for_backward(x, y)
+    return out
+
+
+def _mmd2_backward(ctx, name, g):
+    x, y = ctx.saved_tensors
+    m, d = x.shape
+    n = y.shape[0]
+    dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+    dy = torch.empty_like(y) if ctx.needs_input_grad[1] else None
+    if dx is None and dy is None:
+        return None, None, None, None
+    check(getattr(_L(), name)(_p(x), _p(y), m, n, d, ctx.sg, ctx.wt, ctx.ns, _p(_c(g)), _p(dx), _p(dy), _stream()), name)
+    return dx, dy, None, None
+
+
 class MixRbfMmd2(Function):
     """biased MMD^2 between two sets of codes under a mixture of RBF kernels (tflib/objs/mmd.py:65-67) -> 0-dim tensor"""
 
     @staticmethod
     def forward(ctx, x, y, sigmas, wts):
-        x, y = _c(x), _c(y)
-        m, d = x.shape
-        n = y.shape[0]
-        assert y.shape[1] == d
-        ns = len(sigmas)
-        sg = (C.c_float * ns)(*[float(v) for v in sigmas])
-        wt = (C.c_float * ns)(*[float(v) for v in wts]) if wts is not None else None
-        out = torch.empty((), dtype=torch.float32, device=x.device)
-        scratch = torch.empty((m + n,), dtype=torch.float32, device=x.device)
-        check(_L().ggan_mix_rbf_mmd2_fwd(_p(x), _p(y), m, n, d, sg, wt, ns, _p(out), _p(scratch), _stream()), 'ggan_mix_rbf_mmd2_fwd')
-        ctx.sg, ctx.wt, ctx.ns = sg, wt, ns
-        ctx.save_for_backward(x, y)
-        return out
+        return _mmd2_forward(ctx, 'ggan_mix_rbf_mmd2_fwd', x, y, sigmas, wts)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
-        x, y = ctx.saved_tensors
-        m, d = x.shape
-        n = y.shape[0]
-        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        dy = torch.empty_like(y) if ctx.needs_input_grad[1] else None
-        if dx is None and dy is None:
-            return None, None, None, None
-        check(_L().ggan_mix_rbf_mmd2_bwd(_p(x), _p(y), m, n, d, ctx.sg, ctx.wt, ctx.ns, _p(_c(g)), _p(dx), _p(dy), _stream()),
-              'ggan_mix_rbf_mmd2_bwd')
-        return dx, dy, None, None
+        return _mmd2_backward(ctx, 'ggan_mix_rbf_mmd2_bwd', g)
+
+
+class MixRbfMmd2Unbiased(Function):
+    """the unbiased estimator (tflib/objs/mmd.py:53-61): same-set diagonals left out, means over m (m - 1) and n (n - 1) pairs; m, n >= 2"""
+
+    @staticmethod
+    def forward(ctx, x, y, sigmas, wts):
+        return _mmd2_forward(ctx, 'ggan_mix_rbf_mmd2_unbiased_fwd', x, y, sigmas, wts)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        return _mmd2_backward(ctx, 'ggan_mix_rbf_mmd2_unbiased_bwd', g)
+
+
+MMD_FUSED_MAX_ROWS = 512      # include/ggan.h: ggan_mix_rbf_mmd2_* take m + n <= 512
+
+
+def mix_rbf_sums(x, y, sigmas, wts=None):
+    """the three pairwise kernel sums of two row sets x [m, d], y [n, d] (ggan_mix_rbf_sums; x and y may be the same tensor) -> float64 device
+    tensor [S_xx, S_yy, S_xy], the same-set sums over ordered pairs i != j.  Forward only: inputs that require grad are refused."""
+    if (torch.is_grad_enabled() and (x.requires_grad or y.requires_grad)):
+        raise _lib.GganError('mix_rbf_sums has no backward: detach the inputs (the differentiable op takes m + n <= %d rows)' % MMD_FUSED_MAX_ROWS)
+    x, y = _c(x), _c(y)
+    if x.dim() != 2 or y.dim() != 2 or x.shape[1] != y.shape[1]:
+        raise ValueError('mix_rbf_sums: two [rows, d] sets of one width expected, got %s and %s' % (tuple(x.shape), tuple(y.shape)))
+    (m, d), n = x.shape, y.shape[0]
+    ns = len(sigmas)
+    sg = (C.c_float * ns)(*[float(v) for v in sigmas])
+    wt = (C.c_float * ns)(*[float(v) for v in wts]) if wts is not None else None
+    nbytes = int(_L().ggan_mix_rbf_sums_workspace(m, n))
+    ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=x.device)
+    out = torch.empty((3,), dtype=torch.float64, device=x.device)
+    check(_L().ggan_mix_rbf_sums(_p(x), _p(y), m, n, d, sg, wt, ns, _p(out), _p(ws), nbytes, _stream()), 'ggan_mix_rbf_sums')
+    return out
+
+
+def mmd2_from_sums(sums3, m, n, wt_sum, biased):
+    """either estimator from [S_xx, S_yy, S_xy] (float64 tensor or array): the reference's diagonal is the constant sum(wts), mmd.py:52-67"""
+    sxx, syy, sxy = sums3[0], sums3[1], sums3[2]
+    if biased:
+        return (sxx + m * wt_sum) / (float(m) * m) + (syy + n * wt_sum) / (float(n) * n) - 2.0 * sxy / (float(m) * n)
+    return sxx / (float(m) * (m - 1)) + syy / (float(n) * (n - 1)) - 2.0 * sxy / (float(m) * n)
 
 
 class Reparam(Function):

@@ -124,6 +124,24 @@ def manifold_due(plan, it, iters):
     return bool((n and it % n == n - 1) or (plan.get('MANIFOLD_AT_END') and it == iters - 1))
 
 
+# the dev-set MMD^2 scores (evaluate.Evaluator.mmd_scores) are no pass of the reference's loops: off unless asked for, a cadence of their
+# own outside EVAL_KEYS
+def mmd_settings(script):
+    """{'MMD_EVERY': N} for the eight image scripts when $GGAN_MMD_EVERY = N is set, {} otherwise -- and always {} for the two state-space
+    scripts, which have no single code to compare"""
+    name = os.path.splitext(os.path.basename(script))[0]
+    every = os.environ.get('GGAN_MMD_EVERY')
+    if name not in _IMAGE_SCRIPTS or not every:
+        return {}
+    return {'MMD_EVERY': int(every)}
+
+
+def mmd_due(S, it):
+    """does the pass fire after iteration `it`: it % N == N - 1, the cadence of the other passes"""
+    n = int(S.get('MMD_EVERY') or 0)
+    return bool(n and it % n == n - 1)
+
+
 def labelled(batches):
     """are these minibatches (images, labels) pairs"""
     return bool(batches) and all(isinstance(b, (tuple, list)) and len(b) > 1 and b[1] is not None for b in batches)
@@ -325,6 +343,15 @@ def train(S, cfg, model=None, out_dir=None):
             manifold = None
         else:
             m_eval = evaluator if evaluator is not None else Evaluator(tr, S)
+    mmd_eval = None
+    if S.get('MMD_EVERY') and (tr.world == 1 or torch.distributed.get_rank() == 0):
+        from .evaluate import Evaluator
+        from .models_ssgan import StateSpaceGAN
+        if isinstance(tr.model, StateSpaceGAN):
+            print('[run] dev mmd skipped: the state-space models have no single code to compare')
+        else:
+            mmd_eval = evaluator if evaluator is not None else (m_eval if manifold else Evaluator(tr, S))
+            mmd_dev = ev_dev if evaluator is not None else (m_dev if manifold else eval_sets(S, tr.model, device)[0])
     eval_ms = 0.0            # wall time of the evaluation passes (kept out of `time`)
     for it in range(S['ITERS']):
         if (it == 2 and isinstance(batches, DevicePrefetcher) and S.get('RING_FEED', True) and tr.graph_enabled
@@ -350,6 +377,9 @@ def train(S, cfg, model=None, out_dir=None):
             lib.plot.flush(out_dir, os.path.join(out_dir, 'logfile.txt') if out_dir else None)
         if manifold_due(manifold, it, S['ITERS']):
             eval_ms += _manifold(m_eval, m_dev, it, out_dir, device)
+        if mmd_eval is not None and mmd_due(S, it):
+            eval_ms += _mmd(mmd_eval, mmd_dev, device)
+            lib.plot.flush(out_dir, os.path.join(out_dir, 'logfile.txt') if out_dir else None)
         lib.plot.tick()
         if out_dir and S.get('SAVE_EVERY') and (it + 1) % S['SAVE_EVERY'] == 0:
             checkpoint.save(os.path.join(out_dir, 'params_%d.npz' % (it + 1)), tr, data_source=source)
@@ -395,6 +425,18 @@ def _manifold(ev, dev, it, out_dir, device):
         torch.cuda.synchronize(device)
     t0 = time.time()
     ev.manifold(dev, out_dir, it)
+    if device.type == 'cuda':
+        torch.cuda.synchronize(device)
+    return (time.time() - t0) * 1e3
+
+
+def _mmd(ev, dev, device):
+    """the dev-set MMD^2 scores, logged through lib.plot -> milliseconds they took"""
+    if device.type == 'cuda':
+        torch.cuda.synchronize(device)
+    t0 = time.time()
+    for k, v in ev.mmd_scores(dev).items():
+        lib.plot.plot(k, v)
     if device.type == 'cuda':
         torch.cuda.synchronize(device)
     return (time.time() - t0) * 1e3

@@ -403,6 +403,26 @@ int ggan_mix_rbf_mmd2_fwd(const float* X, const float* Y, int m, int n, int d, c
                           float* out, float* row_scratch, ggan_stream_t stream);
 int ggan_mix_rbf_mmd2_bwd(const float* X, const float* Y, int m, int n, int d, const float* sigmas, const float* wts, int ns,
                           const float* gout, float* dX, float* dY, ggan_stream_t stream);
+/* The unbiased estimator (tflib/objs/mmd.py:53-61, _mmd2 with biased=False) at the same sizes and with the same arguments: the diagonals of
+ * the same-set blocks are left out and those blocks are averaged over m (m - 1) and n (n - 1) ordered pairs; m, n >= 2. */
+int ggan_mix_rbf_mmd2_unbiased_fwd(const float* X, const float* Y, int m, int n, int d, const float* sigmas, const float* wts, int ns,
+                                   float* out, float* row_scratch, ggan_stream_t stream);
+int ggan_mix_rbf_mmd2_unbiased_bwd(const float* X, const float* Y, int m, int n, int d, const float* sigmas, const float* wts, int ns,
+                                   const float* gout, float* dX, float* dY, ggan_stream_t stream);
+
+/* The three pairwise kernel sums behind both MMD^2 estimators, at set sizes (tflib/objs/mmd.py:20-67: _mix_rbf_kernel's three Gram
+ * matrices and _mmd2's sums, never materialised here): X[m,d], Y[n,d] row-major device fp32, any d >= 1, 1 <= m, n <= 131072, X == Y allowed;
+ * sigmas / wts HOST arrays (wts may be NULL = all 1), ns <= 8.  sums3 (device, 3 doubles):
+ *   [0] S_xx = sum_{i != j} k(x_i, x_j)   [1] S_yy = sum_{i != j} k(y_i, y_j)   [2] S_xy = sum_{i, j} k(x_i, y_j)
+ * with k as above.  The reference's diagonal is the constant sum(wts) (mmd.py:52-54), so
+ *   biased   = (S_xx + m sum(wts)) / m^2 + (S_yy + n sum(wts)) / n^2 - 2 S_xy / (m n)
+ *   unbiased = S_xx / (m (m - 1)) + S_yy / (n (n - 1)) - 2 S_xy / (m n).
+ * Gram tiles on the fp32 MFMA, distances / exponentials / sums in the tiles' epilogue; per-workgroup partials added in a fixed order in
+ * double (no atomics: repeated calls give the same bits).  ws: ggan_mix_rbf_sums_workspace(m, n) bytes of 16-byte aligned device scratch
+ * (linear in m + n; 0 = sizes out of range), all of it scratch -- no arrival counters.  Forward only. */
+size_t ggan_mix_rbf_sums_workspace(int m, int n);
+int ggan_mix_rbf_sums(const float* X, const float* Y, int m, int n, int d, const float* sigmas, const float* wts, int ns,
+                      double* sums3, void* ws, size_t ws_bytes, ggan_stream_t stream);
 
 /* Stochastic encoder head, TYPE_Q = 'learn_std' (gan_inference_cifar10.py:173-188): std = exp(log_std), z = mean + eps * std; the backward
  * takes the gradients arriving at z and at std (either may be NULL). */
