@@ -20,65 +20,21 @@
 // calls on the same input give the same bits.  S is chosen so that nb * S is about 2048 workgroups, so the workspace (T norms + nb * S
 // triples) is linear in m + n.
 #include "common.h"
+#include "set_rows.h"
 using namespace ggan;
 
 namespace {
 
-constexpr int BT = 128;            // rows of Z per block: a tile is BT x BT
-constexpr int KS = 16;             // k per main-loop step
-constexpr int LD = BT + 4;         // LDS tile row (floats): 4 * LD = 16 (mod 64), the four k-quads of a staging wave hit disjoint banks
 constexpr int kMaxSigmas = 8;
-constexpr int kMaxRows = 131072;
 constexpr int kTargetWgs = 2048;
 
-struct SetParams {
-    const float* X;
-    const float* Y;
-    const float* norms;            // [T] squared row norms of Z
+struct SetParams : RowSets {       // (set_rows.h: the row list, its loads and the norm pre-pass)
     double* part;                  // [nb * S][3]
-    int m, T, d, ns;
+    int ns;
     int nb, S;
-    int vec;                       // float4 loads legal on every row (d % 4 == 0 and both bases 16-byte aligned)
     float g2[kMaxSigmas];          // log2(e) / (2 sigma^2): exp(-gamma D) = exp2(-g2 D)
     float wt[kMaxSigmas];
 };
-
-__device__ __forceinline__ const float* z_row(const SetParams& P, int r) {
-    return r < P.m ? P.X + (size_t)r * P.d : P.Y + (size_t)(r - P.m) * P.d;
-}
-
-// four consecutive k of row r of Z (zeros beyond T or d), without a branch: the address is clamped into the row list and into the row, the
-// value dropped afterwards -- every load of a step can then be in flight at once (guarded loads compile to "load; wait" chains).
-// VEC (d % 4 == 0 and both bases 16-byte aligned, so every row is): one 16-byte load; k is a multiple of 4, so k < d means k + 3 < d.
-// !VEC (rows of odd d are not 16-byte aligned): four dword loads, each with its own range test.
-template <bool VEC>
-__device__ __forceinline__ float4 load4(const SetParams& P, int r, int k) {
-    const float* row = z_row(P, min(r, P.T - 1));
-    const bool rok = r < P.T;
-    if (VEC) {
-        const float4 t = *reinterpret_cast<const float4*>(row + min(k, P.d - 4));
-        const bool ok = rok && k < P.d;
-        return make_float4(ok ? t.x : 0.f, ok ? t.y : 0.f, ok ? t.z : 0.f, ok ? t.w : 0.f);
-    }
-    float v[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const float t = row[min(k + j, P.d - 1)];
-        v[j] = (rok && k + j < P.d) ? t : 0.f;
-    }
-    return make_float4(v[0], v[1], v[2], v[3]);
-}
-
-// squared norms: one wave per row, lane-strided fma chains combined by the wave's butterfly (a fixed order)
-__global__ __launch_bounds__(256) void set_norms_k(const SetParams P, float* __restrict__ norms) {
-    const int r = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (r >= P.T) return;
-    const float* z = z_row(P, r);
-    float s = 0.f;
-    for (int k = lane; k < P.d; k += 64) s = fmaf(z[k], z[k], s);
-    s = wave_sum(s);
-    if (lane == 0) norms[r] = s;
-}
 
 // is step t of block a a tile to compute (see the head of the file)
 __device__ __forceinline__ bool step_valid(int a, int t, int nb) { return 2 * t < nb || (2 * t == nb && 2 * a < nb) || t == 0; }
@@ -238,7 +194,6 @@ inline int splits_of(int nb) {
     if (S > nt) S = nt;
     return S < 1 ? 1 : S;
 }
-inline size_t norms_bytes(int m, int n) { return ((size_t)((long)m + n) * sizeof(float) + 15) & ~(size_t)15; }
 
 }  // namespace
 
@@ -247,7 +202,7 @@ extern "C" {
 size_t ggan_mix_rbf_sums_workspace(int m, int n) {
     if (m < 1 || n < 1 || m > kMaxRows || n > kMaxRows) return 0;
     const int nb = blocks_of(m, n);
-    return norms_bytes(m, n) + (size_t)nb * splits_of(nb) * 3 * sizeof(double);
+    return norms_bytes((long)m + n) + (size_t)nb * splits_of(nb) * 3 * sizeof(double);
 }
 
 int ggan_mix_rbf_sums(const float* X, const float* Y, int m, int n, int d, const float* sigmas, const float* wts, int ns,
@@ -270,7 +225,7 @@ int ggan_mix_rbf_sums(const float* X, const float* Y, int m, int n, int d, const
     }
     float* norms = (float*)ws;
     P.norms = norms;
-    P.part = (double*)((char*)ws + norms_bytes(m, n));
+    P.part = (double*)((char*)ws + norms_bytes((long)m + n));
     hipStream_t st = (hipStream_t)stream;
     GGAN_LAUNCH("mmd_set_norms", 2.0 * P.T * d, 4.0 * P.T * d, set_norms_k, dim3(cdiv(P.T, 4)), dim3(256), 0, st, P, norms);
     // tiles computed: nb diagonal ones and nb (nb - 1) / 2 pairs

@@ -14,6 +14,9 @@
   mmd_scores         `dev mmd z` / `dev mmd x`: the unbiased mixture-of-RBF MMD^2 (tflib/objs/mmd.py:20-67, sigmas 2..80) between the aggregate
                      posterior q(z) and the prior p(z), and between the dev images and as many generated ones -- two set-level sums of
                      ggan_mix_rbf_sums.  Not a pass of the reference's loops: the stand-in for its inception score (README).
+  prdc_scores        `dev precision|recall|density|coverage z|x`: k-NN-ball precision / recall (Kynkaanniemi et al. 2019) and density /
+                     coverage (Naeem et al. 2020) of the same four sets -- ggan_knn_radii and ggan_ball_counts.  Not a pass of the
+                     reference's loops either; it tells dropped modes from bad samples, which one MMD number cannot (README).
 
 The passes are safe in the middle of training: they run under torch.no_grad() on the current stream only (no second stream, no
 collective), with a feed dict and a noise generator state of their own -- the Trainer's static feed buffers, ring slots and noise state
@@ -33,7 +36,7 @@ run by SequenceEvaluator on a models_ssgan.StateSpaceGAN under the same rules:
 Each is written as a .png sheet (one sequence per row) and a looping .gif; the bytes of both come from one ggan_video_sheet_u8 launch.
 
 `python -m graphical_gan_amd.evaluate CKPT --script gmgan_inference_mnist [--data-dir DIR]` scores a saved checkpoint
-(`--out-dir DIR --manifold` also writes the latent-space pictures of the two MNIST scripts, `--mmd` adds the two MMD^2 rows);
+(`--out-dir DIR --manifold` also writes the latent-space pictures of the two MNIST scripts, `--mmd` adds the two MMD^2 rows, `--prdc` the eight precision / recall / density / coverage rows);
 `... CKPT --script ssgan_inference_moving_mnist|ssgan_inference_chairs [--data-dir DIR] --out-dir DIR` writes the four pairs of files."""
 import argparse
 import contextlib
@@ -47,6 +50,8 @@ from . import functional as F
 from . import tflib as lib
 
 MMD_MAX_ROWS = 10000      # rows per set of the mmd_scores pass (settings: MMD_MAX_ROWS)
+PRDC_MAX_ROWS = 10000     # rows per set of the prdc_scores pass (settings: PRDC_MAX_ROWS)
+PRDC_K = 5                # neighbours of its k-NN balls (settings: PRDC_K; at most functional.PRDC_MAX_K)
 EVAL_SEED = 7919          # offset of the evaluator's noise seeds from the settings seed (the Trainer's stream of draws is not touched)
 
 # the reference's output file names, per script: (samples, reconstructions), formatted with frame= and mode=
@@ -259,35 +264,71 @@ class Evaluator(_Passes):
                     out['qk'][rows].copy_(torch.argmax(q_k, dim=1))
         return out
 
+    def _score_sets(self, batches, rows):
+        """the four row sets the set-level scores compare, on the device, over the full minibatches and at most `rows` rows per set:
+        z = q_z (the sampled code of the aggregated-posterior MODEs, as latent_sets), pz = as many fresh prior draws (through HyperGenerator
+        with a mixture prior), x = real_x as the nets see it, gx = Generator(pz) minibatch by minibatch.  Called inside a pass's guard."""
+        c = self.cfg
+        X, _ = self._stage(batches)
+        B = c.B
+        n = min(X.shape[0], max(1, int(rows) // B))
+        new = lambda w: torch.empty((n * B, w), dtype=torch.float32, device=self.device)
+        sets = dict(z=new(c.dim_latent), pz=new(c.dim_latent), x=new(c.output_dim), gx=new(c.output_dim))
+        self.kept = []
+        for i in range(n):
+            rows = slice(i * B, (i + 1) * B)
+            self._load(X[i])
+            real_x = self.model.real_x(self.feed)
+            q = self.model.Extractor(real_x, eps=self.feed['q_eps']) if c.agg else self.model.Extractor(real_x)
+            sets['z'][rows].copy_(q[0] if isinstance(q, tuple) else q)
+            sets['x'][rows].copy_(real_x.float())
+            p_z = self.model.HyperGenerator(self.feed['k_onehot'], self.feed['p_z_noise']) if c.K else self.feed['p_z_noise']
+            sets['pz'][rows].copy_(p_z)
+            sets['gx'][rows].copy_(self.model.Generator(sets['pz'][rows]).float())
+        return sets
+
+    def set_scores(self, batches, mmd=False, prdc=False, return_sets=False):
+        """the set-level scores asked for, from ONE build of the sets (_score_sets: one stream of noise draws, whichever scores are on) and
+        ONE host synchronisation: mmd -> the two values of mmd_scores, prdc -> the eight of prdc_scores, in that order.  With both on, each
+        scores the leading rows its own row cap allows.  return_sets: (values, {z, pz, x, gx})."""
+        B = self.cfg.B
+        cap = {'mmd': int(self.S.get('MMD_MAX_ROWS', MMD_MAX_ROWS)), 'prdc': int(self.S.get('PRDC_MAX_ROWS', PRDC_MAX_ROWS))}
+        on = [name for name, flag in (('mmd', mmd), ('prdc', prdc)) if flag]
+        if not on:
+            raise ValueError('set_scores: neither score was asked for')
+        k = int(self.S.get('PRDC_K', PRDC_K))
+        with self._guard():
+            sets = self._score_sets(batches, max(cap[name] for name in on))
+            rows = {name: min(sets['z'].shape[0], max(1, cap[name] // B) * B) for name in on}
+            names, vals = [], []
+            if mmd:
+                if rows['mmd'] < 2:
+                    raise ValueError('the unbiased MMD needs at least 2 rows per set')
+                for space, a, b in (('z', 'z', 'pz'), ('x', 'x', 'gx')):
+                    names.append('dev mmd ' + space)
+                    vals.append(lib.objs.mmd.mix_rbf_mmd2(sets[a][:rows['mmd']], sets[b][:rows['mmd']], biased=False).double().reshape(1))
+            if prdc:
+                if k > rows['prdc'] - 1:
+                    raise ValueError('PRDC_K = %d needs more than %d rows per set' % (k, rows['prdc']))
+                for space, a, b in (('z', 'z', 'pz'), ('x', 'x', 'gx')):
+                    names += ['dev %s %s' % (what, space) for what in ('precision', 'recall', 'density', 'coverage')]
+                    vals.append(F.prdc(sets[a][:rows['prdc']], sets[b][:rows['prdc']], k))
+            vals = torch.cat(vals).cpu().numpy()
+        res = {name: float(v) for name, v in zip(names, vals)}
+        return (res, sets) if return_sets else res
+
     def mmd_scores(self, batches, return_sets=False):
         """{'dev mmd z': unbiased MMD^2(q_z, p_z), 'dev mmd x': unbiased MMD^2(real_x, Generator(p_z))} over the full dev minibatches, at
-        most MMD_MAX_ROWS rows per set: z = q_z (the sampled code of the aggregated-posterior MODEs, as latent_sets), pz = as many fresh
-        prior draws (through HyperGenerator with a mixture prior), x = real_x as the nets see it, gx = Generator(pz) minibatch by minibatch.
-        The sets stay on the device; the two values come back in ONE host synchronisation.  return_sets: (values, {z, pz, x, gx})."""
-        c = self.cfg
-        with self._guard():
-            X, _ = self._stage(batches)
-            B = c.B
-            n = min(X.shape[0], max(1, int(self.S.get('MMD_MAX_ROWS', MMD_MAX_ROWS)) // B))
-            if n * B < 2:
-                raise ValueError('the unbiased MMD needs at least 2 rows per set')
-            new = lambda w: torch.empty((n * B, w), dtype=torch.float32, device=self.device)
-            sets = dict(z=new(c.dim_latent), pz=new(c.dim_latent), x=new(c.output_dim), gx=new(c.output_dim))
-            self.kept = []
-            for i in range(n):
-                rows = slice(i * B, (i + 1) * B)
-                self._load(X[i])
-                real_x = self.model.real_x(self.feed)
-                q = self.model.Extractor(real_x, eps=self.feed['q_eps']) if c.agg else self.model.Extractor(real_x)
-                sets['z'][rows].copy_(q[0] if isinstance(q, tuple) else q)
-                sets['x'][rows].copy_(real_x.float())
-                p_z = self.model.HyperGenerator(self.feed['k_onehot'], self.feed['p_z_noise']) if c.K else self.feed['p_z_noise']
-                sets['pz'][rows].copy_(p_z)
-                sets['gx'][rows].copy_(self.model.Generator(sets['pz'][rows]).float())
-            vals = torch.stack([lib.objs.mmd.mix_rbf_mmd2(sets['z'], sets['pz'], biased=False),
-                                lib.objs.mmd.mix_rbf_mmd2(sets['x'], sets['gx'], biased=False)]).cpu().numpy()
-        res = {'dev mmd z': float(vals[0]), 'dev mmd x': float(vals[1])}
-        return (res, sets) if return_sets else res
+        most MMD_MAX_ROWS rows per set (_score_sets).  The sets stay on the device; the two values come back in ONE host synchronisation.
+        return_sets: (values, {z, pz, x, gx})."""
+        return self.set_scores(batches, mmd=True, return_sets=return_sets)
+
+    def prdc_scores(self, batches, return_sets=False):
+        """{'dev precision z', 'dev recall z', 'dev density z', 'dev coverage z', and the same four with x}: precision / recall (Kynkaanniemi
+        et al. 2019) and density / coverage (Naeem et al. 2020) from PRDC_K-NN balls (default 5) of the sets of mmd_scores -- real = q_z of
+        the dev images / the dev images, generated = as many prior draws / Generator(p_z) -- at most PRDC_MAX_ROWS rows per set, by
+        functional.prdc.  ONE host synchronisation for all eight.  return_sets: (values, {z, pz, x, gx})."""
+        return self.set_scores(batches, prdc=True, return_sets=return_sets)
 
     def manifold(self, batches, out_dir, frame):
         """embeds the point sets of latent_sets with functional.tsne and writes the scatters under the reference's file names; returns
@@ -542,6 +583,7 @@ def main(argv=None):
     ap.add_argument('--out-dir', default=None, help='also write the sample grid and the reconstructions here (the state-space scripts: the video files, required)')
     ap.add_argument('--manifold', action='store_true', help='also write the latent-space t-SNE pictures of the MNIST scripts to --out-dir')
     ap.add_argument('--mmd', action='store_true', help='also score the dev set by the unbiased MMD^2 of codes and of images (dev mmd z / dev mmd x; image scripts)')
+    ap.add_argument('--prdc', action='store_true', help='also score the dev set by k-NN-ball precision / recall / density / coverage of codes and of images (eight dev rows; image scripts)')
     ap.add_argument('--set', action='append', default=[], metavar='KEY=VALUE', help='override an UPPERCASE setting (int / float / str)')
     a = ap.parse_args(argv)
     over = {}
@@ -558,6 +600,8 @@ def main(argv=None):
         over['MODE'] = a.mode
     if a.mmd and os.path.splitext(os.path.basename(a.script))[0] in run._SEQUENCE_SCRIPTS:
         ap.error('--mmd: the state-space scripts have no single code to compare')
+    if a.prdc and os.path.splitext(os.path.basename(a.script))[0] in run._SEQUENCE_SCRIPTS:
+        ap.error('--prdc: the state-space scripts have no single code to compare')
     if a.manifold:          # (checked before anything is built)
         name = os.path.splitext(os.path.basename(a.script))[0]
         if name not in MANIFOLD_SCRIPTS:
@@ -574,15 +618,15 @@ def main(argv=None):
         model = StateSpaceGAN(cfg)
     tr = Trainer(cfg, device=lib.get_device(), graph=False, model=model)
     checkpoint.restore(a.ckpt, tr)
-    res = evaluate_once(tr, S, out_dir=a.out_dir, manifold=a.manifold, mmd=a.mmd)
+    res = evaluate_once(tr, S, out_dir=a.out_dir, manifold=a.manifold, mmd=a.mmd, prdc=a.prdc)
     for k in sorted(res):
         print('%s\t%s' % (k, res[k]))
     return res
 
 
-def evaluate_once(tr, S, out_dir=None, frame='eval', manifold=False, mmd=False):
+def evaluate_once(tr, S, out_dir=None, frame='eval', manifold=False, mmd=False, prdc=False):
     """every pass the script's data allow, once -> {name: value}; manifold: the latent-space pictures too (labelled dev data only);
-    mmd: the two dev-set MMD^2 scores too"""
+    mmd: the two dev-set MMD^2 scores too; prdc: the eight precision / recall / density / coverage scores too (one build of the sets for both)"""
     from . import run
     if S['DATASET'] in run.SEQUENCE_DATASETS:       # the video passes: files only (train_data: the first dev minibatch)
         ev = SequenceEvaluator(tr, S)
@@ -595,8 +639,8 @@ def evaluate_once(tr, S, out_dir=None, frame='eval', manifold=False, mmd=False):
     res = dict(ev.dev_costs(dev))
     if tr.cfg.K and test is not None:
         res['testing accuracy'] = ev.cluster_accuracy(test)
-    if mmd:
-        res.update(ev.mmd_scores(dev))
+    if mmd or prdc:
+        res.update(ev.set_scores(dev, mmd=mmd, prdc=prdc))
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
         ev.set_fixed_data(dev[0])

@@ -332,6 +332,66 @@ def mmd2_from_sums(sums3, m, n, wt_sum, biased):
     return sxx / (float(m) * (m - 1)) + syy / (float(n) * (n - 1)) - 2.0 * sxy / (float(m) * n)
 
 
+PRDC_MAX_K = 8                # include/ggan.h: ggan_knn_radii keeps 1 <= k <= 8 neighbours per row
+
+
+def _row_sets(name, sets, k=None, radii=None):
+    """the checks the k-NN ball ops share, in this order: [rows, d] sets of one width, 1 <= k <= min(8, fewest rows - 1), one radius per row of
+    the last set (ValueError, before anything else); no gradient; fp32 on the device -> the sets, contiguous"""
+    if any(t.dim() != 2 for t in sets) or len(set(t.shape[1] for t in sets)) != 1:
+        raise ValueError('%s: [rows, d] sets of one width expected, got %s' % (name, ', '.join(str(tuple(t.shape)) for t in sets)))
+    rows = min(t.shape[0] for t in sets)
+    if k is not None and (not 1 <= int(k) <= PRDC_MAX_K or int(k) > rows - 1):
+        raise ValueError('%s: 1 <= k <= min(%d, rows - 1) expected, got k = %s with %d rows' % (name, PRDC_MAX_K, k, rows))
+    if radii is not None and (radii.dim() != 1 or radii.shape[0] != sets[-1].shape[0]):
+        raise ValueError('%s: one radius per row of the second set expected, got %s for %d rows' % (name, tuple(radii.shape), sets[-1].shape[0]))
+    if torch.is_grad_enabled() and any(t.requires_grad for t in sets):
+        raise _lib.GganError('%s has no backward: detach the inputs' % name)
+    return [_c(t) for t in sets]
+
+
+def knn_radii(z, k):
+    """squared distance from every row of z [n, d] to its k-th nearest OTHER row (ggan_knn_radii: self left out by index, duplicates
+    count) -> float32 [n] device tensor.  Forward only."""
+    (z,), k = _row_sets('knn_radii', [z], k=k), int(k)
+    n, d = z.shape
+    nbytes = int(_L().ggan_knn_radii_workspace(n, k))
+    ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=z.device)
+    r2 = torch.empty((n,), dtype=torch.float32, device=z.device)
+    check(_L().ggan_knn_radii(_p(z), n, d, k, _p(r2), _p(ws), nbytes, _stream()), 'ggan_knn_radii')
+    return r2
+
+
+def ball_counts(a, b, r2_b):
+    """per row of a [m, d]: in how many of b's balls it lies (squared radii r2_b [n], inclusive) and its squared distance to the nearest
+    row of b (ggan_ball_counts) -> (int32 [m], float32 [m]) device tensors.  Forward only."""
+    (a, b), r2_b = _row_sets('ball_counts', [a, b], radii=r2_b), _c(r2_b)
+    (m, d), n = a.shape, b.shape[0]
+    nbytes = int(_L().ggan_ball_counts_workspace(m, n))
+    ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=a.device)
+    cnt = torch.empty((m,), dtype=torch.int32, device=a.device)
+    mn = torch.empty((m,), dtype=torch.float32, device=a.device)
+    check(_L().ggan_ball_counts(_p(a), _p(b), m, n, d, _p(r2_b), _p(cnt), _p(mn), _p(ws), nbytes, _stream()), 'ggan_ball_counts')
+    return cnt, mn
+
+
+def prdc(x, y, k=5):
+    """(precision, recall, density, coverage) of the generated set y [n, d] against the real set x [m, d] from k-NN balls (Kynkaanniemi
+    et al. 2019; Naeem et al. 2020; include/ggan.h) -> float64 [4] device tensor, formed on the device: the caller takes the one host
+    synchronisation.  Forward only."""
+    (x, y), k = _row_sets('prdc', [x, y], k=k), int(k)
+    m, n = x.shape[0], y.shape[0]
+    r_x, r_y = knn_radii(x, k), knn_radii(y, k)
+    cnt_y, _ = ball_counts(y, x, r_x)                    # generated rows in real balls
+    cnt_x, mn_x = ball_counts(x, y, r_y)                 # real rows in generated balls, and their nearest generated row
+    f8 = torch.float64
+    sums = torch.stack([(cnt_y > 0).sum(dtype=f8), (cnt_x > 0).sum(dtype=f8), cnt_y.sum(dtype=f8), (mn_x <= r_x).sum(dtype=f8)])
+    # (a quotient of two tensors is a true division -- by a Python number torch multiplies by its rounded reciprocal --; the denominators
+    #  are filled on the device: a tensor made from host numbers would be an upload the host waits for)
+    den = lambda v: torch.full((), float(v), dtype=f8, device=x.device)
+    return sums / torch.stack([den(n), den(m), den(k * n), den(m)])
+
+
 class Reparam(Function):
     """(z, std) = (mean + eps * exp(log_std), exp(log_std)): the stochastic encoder head (gan_inference_cifar10.py:173-188)"""
 

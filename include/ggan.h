@@ -424,6 +424,24 @@ size_t ggan_mix_rbf_sums_workspace(int m, int n);
 int ggan_mix_rbf_sums(const float* X, const float* Y, int m, int n, int d, const float* sigmas, const float* wts, int ns,
                       double* sums3, void* ws, size_t ws_bytes, ggan_stream_t stream);
 
+/* k-NN balls of row sets: the two primitives behind improved precision / recall (Kynkaanniemi et al. 2019, "Improved Precision and Recall
+ * Metric for Assessing Generative Models") and density / coverage (Naeem et al. 2020, "Reliable Fidelity and Diversity Metrics for
+ * Generative Models") -- evaluate.Evaluator.prdc_scores, functional.prdc.  Squared Euclidean distances D throughout, as
+ * max(|a|^2 + |b|^2 - 2 a.b, 0) from fp32-MFMA Gram tiles; row-major device fp32, any d >= 1, 1 <= rows <= 131072.
+ *   ggan_knn_radii:   r2[i] = the k-th smallest of { D(z_i, z_l) : l != i }, 1 <= k <= 8, k <= n - 1.  Row i itself is left out by INDEX,
+ *                     a duplicate of it counts (a multiset order statistic: three equal rows have a k = 2 radius of 0).
+ *   ggan_ball_counts: cnt[a] = #{ j : D(a_a, b_j) <= rB2[j] } (inclusive), min2[a] = min_j D(a_a, b_j), for the m rows of A against the n
+ *                     rows of B with their squared radii rB2[n].
+ * With X the real set (m rows), Y the generated one (n rows), rX = radii(X), rY = radii(Y), (cy, .) = ball_counts(Y, X, rX) and
+ * (cx, mx) = ball_counts(X, Y, rY): precision = mean(cy > 0), density = sum(cy) / (k n), recall = mean(cx > 0), coverage = mean(mx <= rX).
+ * ws: ggan_*_workspace bytes of 16-byte aligned device scratch (0 = arguments out of range), all of it scratch.  Per-row lists, integer
+ * counts and minima only -- no floating-point atomics: repeated calls give the same bits.  Forward only. */
+size_t ggan_knn_radii_workspace(int n, int k);
+int ggan_knn_radii(const float* Z, int n, int d, int k, float* r2, void* ws, size_t ws_bytes, ggan_stream_t stream);
+size_t ggan_ball_counts_workspace(int m, int n);
+int ggan_ball_counts(const float* A, const float* B, int m, int n, int d, const float* rB2, int* cnt, float* min2, void* ws,
+                     size_t ws_bytes, ggan_stream_t stream);
+
 /* Stochastic encoder head, TYPE_Q = 'learn_std' (gan_inference_cifar10.py:173-188): std = exp(log_std), z = mean + eps * std; the backward
  * takes the gradients arriving at z and at std (either may be NULL). */
 int ggan_reparam_fwd(const float* mean, const float* log_std, const float* eps, float* z, float* std_out, size_t n, ggan_stream_t stream);
