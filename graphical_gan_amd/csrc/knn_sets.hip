@@ -34,65 +34,6 @@ struct SweepParams : RowSets {     // queries: rows [0, nq) of Z; candidates: ro
     int nbc, S;                    // candidate blocks, splits of them
 };
 
-// staging: unit u of a thread is 4 consecutive k of one tile row; 4 lanes cover the 16 k of a row (64 contiguous bytes)
-template <bool VEC>
-__device__ __forceinline__ void load_step(const RowSets& P, int r0a, int r0b, int k0, float4 (&xa)[2], float4 (&xb)[2]) {
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        const int unit = threadIdx.x + 256 * u, row = unit >> 2, k = k0 + (unit & 3) * 4;
-        xa[u] = load4<VEC>(P, r0a + row, k);
-        xb[u] = load4<VEC>(P, r0b + row, k);
-    }
-}
-__device__ __forceinline__ void store_step(float* As, float* Bs, const float4 (&xa)[2], const float4 (&xb)[2]) {
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        const int unit = threadIdx.x + 256 * u, row = unit >> 2, kq = unit & 3;
-        float* da = &As[(kq * 4) * LD + row];
-        float* db = &Bs[(kq * 4) * LD + row];
-        da[0] = xa[u].x; da[LD] = xa[u].y; da[2 * LD] = xa[u].z; da[3 * LD] = xa[u].w;
-        db[0] = xb[u].x; db[LD] = xb[u].y; db[2 * LD] = xb[u].z; db[3 * LD] = xb[u].w;
-    }
-}
-
-// one tile: acc = Z[r0a .. r0a + 128) Z[r0b .. r0b + 128)^T (set_sums_k's main loop).  On entry ra / rb hold the tile's first step; on
-// exit, if `next`, the first step of tile (n0a, n0b), in flight during the caller's epilogue.  Ends behind a barrier.
-template <bool VEC>
-__device__ __forceinline__ void gram_tile(const RowSets& P, int r0a, int r0b, bool next, int n0a, int n0b, float (&As)[2][KS * LD],
-                                          float (&Bs)[2][KS * LD], float4 (&ra)[2], float4 (&rb)[2], f32x16 (&acc)[2][2]) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int wm = wave & 1, wn = wave >> 1, half = lane >> 5, l31 = lane & 31;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-    store_step(As[0], Bs[0], ra, rb);
-    __syncthreads();
-    int buf = 0;
-    for (int k0 = 0; k0 < P.d; k0 += KS) {
-        const bool more = k0 + KS < P.d;
-        if (more) load_step<VEC>(P, r0a, r0b, k0 + KS, ra, rb);        // in flight while the MFMA block runs
-        const float* Ab = As[buf];
-        const float* Bb = Bs[buf];
-#pragma unroll
-        for (int kk = 0; kk < KS / 2; ++kk) {
-            const int k = 2 * kk + half;
-            const float a0 = Ab[k * LD + wm * 64 + l31], a1 = Ab[k * LD + wm * 64 + 32 + l31];
-            const float b0 = Bb[k * LD + wn * 64 + l31], b1 = Bb[k * LD + wn * 64 + 32 + l31];
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-        }
-        if (more) store_step(As[buf ^ 1], Bs[buf ^ 1], ra, rb);
-        __syncthreads();
-        buf ^= 1;
-    }
-    if (next) load_step<VEC>(P, n0a, n0b, 0, ra, rb);
-}
-
 // v into the ascending list L of the K smallest values seen so far: tested against the K-th first; then every slot takes the median of
 // its lower neighbour, itself and v (the lower neighbour is never the larger of the two).  Equal values are kept: a multiset.
 template <int K>

@@ -17,6 +17,9 @@
   prdc_scores        `dev precision|recall|density|coverage z|x`: k-NN-ball precision / recall (Kynkaanniemi et al. 2019) and density /
                      coverage (Naeem et al. 2020) of the same four sets -- ggan_knn_radii and ggan_ball_counts.  Not a pass of the
                      reference's loops either; it tells dropped modes from bad samples, which one MMD number cannot (README).
+  knn_scores         `dev knn accuracy z|x`: the leave-one-out KNN_K-nearest-neighbour accuracy of the labelled dev set in code space
+                     (q_z) and in pixel space -- ggan_knn_lists and ggan_knn_vote.  The one number that looks at a label: whether
+                     images of one class are neighbours in z more often than in x (README).
 
 The passes are safe in the middle of training: they run under torch.no_grad() on the current stream only (no second stream, no
 collective), with a feed dict and a noise generator state of their own -- the Trainer's static feed buffers, ring slots and noise state
@@ -36,7 +39,7 @@ run by SequenceEvaluator on a models_ssgan.StateSpaceGAN under the same rules:
 Each is written as a .png sheet (one sequence per row) and a looping .gif; the bytes of both come from one ggan_video_sheet_u8 launch.
 
 `python -m graphical_gan_amd.evaluate CKPT --script gmgan_inference_mnist [--data-dir DIR]` scores a saved checkpoint
-(`--out-dir DIR --manifold` also writes the latent-space pictures of the two MNIST scripts, `--mmd` adds the two MMD^2 rows, `--prdc` the eight precision / recall / density / coverage rows);
+(`--out-dir DIR --manifold` also writes the latent-space pictures of the two MNIST scripts, `--mmd` adds the two MMD^2 rows, `--prdc` the eight precision / recall / density / coverage rows, `--knn` the two k-NN accuracy rows);
 `... CKPT --script ssgan_inference_moving_mnist|ssgan_inference_chairs [--data-dir DIR] --out-dir DIR` writes the four pairs of files."""
 import argparse
 import contextlib
@@ -52,6 +55,8 @@ from . import tflib as lib
 MMD_MAX_ROWS = 10000      # rows per set of the mmd_scores pass (settings: MMD_MAX_ROWS)
 PRDC_MAX_ROWS = 10000     # rows per set of the prdc_scores pass (settings: PRDC_MAX_ROWS)
 PRDC_K = 5                # neighbours of its k-NN balls (settings: PRDC_K; at most functional.PRDC_MAX_K)
+KNN_MAX_ROWS = 10000      # rows of the knn_scores pass (settings: KNN_MAX_ROWS)
+KNN_K = 5                 # neighbours that vote in it (settings: KNN_K; at most functional.KNN_MAX_K)
 EVAL_SEED = 7919          # offset of the evaluator's noise seeds from the settings seed (the Trainer's stream of draws is not touched)
 
 # the reference's output file names, per script: (samples, reconstructions), formatted with frame= and mode=
@@ -264,16 +269,22 @@ class Evaluator(_Passes):
                     out['qk'][rows].copy_(torch.argmax(q_k, dim=1))
         return out
 
-    def _score_sets(self, batches, rows):
+    def _score_sets(self, batches, rows, generated=True, labels=False):
         """the four row sets the set-level scores compare, on the device, over the full minibatches and at most `rows` rows per set:
         z = q_z (the sampled code of the aggregated-posterior MODEs, as latent_sets), pz = as many fresh prior draws (through HyperGenerator
-        with a mixture prior), x = real_x as the nets see it, gx = Generator(pz) minibatch by minibatch.  Called inside a pass's guard."""
+        with a mixture prior), x = real_x as the nets see it, gx = Generator(pz) minibatch by minibatch.  generated=False: z and x alone
+        (the noise is drawn all the same: one stream of draws whichever sets are built).  labels: also y = the int32 labels of the same
+        _stage call, row for row (labelled minibatches only).  Called inside a pass's guard."""
         c = self.cfg
-        X, _ = self._stage(batches)
+        X, Y = self._stage(batches, want_labels=labels)
         B = c.B
         n = min(X.shape[0], max(1, int(rows) // B))
         new = lambda w: torch.empty((n * B, w), dtype=torch.float32, device=self.device)
-        sets = dict(z=new(c.dim_latent), pz=new(c.dim_latent), x=new(c.output_dim), gx=new(c.output_dim))
+        sets = dict(z=new(c.dim_latent), x=new(c.output_dim))
+        if generated:
+            sets = dict(z=sets['z'], pz=new(c.dim_latent), x=sets['x'], gx=new(c.output_dim))
+        if labels:
+            sets['y'] = Y[:n * B]
         self.kept = []
         for i in range(n):
             rows = slice(i * B, (i + 1) * B)
@@ -282,23 +293,31 @@ class Evaluator(_Passes):
             q = self.model.Extractor(real_x, eps=self.feed['q_eps']) if c.agg else self.model.Extractor(real_x)
             sets['z'][rows].copy_(q[0] if isinstance(q, tuple) else q)
             sets['x'][rows].copy_(real_x.float())
+            if not generated:
+                continue
             p_z = self.model.HyperGenerator(self.feed['k_onehot'], self.feed['p_z_noise']) if c.K else self.feed['p_z_noise']
             sets['pz'][rows].copy_(p_z)
             sets['gx'][rows].copy_(self.model.Generator(sets['pz'][rows]).float())
         return sets
 
-    def set_scores(self, batches, mmd=False, prdc=False, return_sets=False):
+    def set_scores(self, batches, mmd=False, prdc=False, knn=False, return_sets=False):
         """the set-level scores asked for, from ONE build of the sets (_score_sets: one stream of noise draws, whichever scores are on) and
-        ONE host synchronisation: mmd -> the two values of mmd_scores, prdc -> the eight of prdc_scores, in that order.  With both on, each
-        scores the leading rows its own row cap allows.  return_sets: (values, {z, pz, x, gx})."""
+        ONE host synchronisation: mmd -> the two values of mmd_scores, prdc -> the eight of prdc_scores, knn -> the two of knn_scores, in
+        that order.  With several on, each scores the leading rows its own row cap allows.  knn needs labelled minibatches (the labels come
+        from the sets' own _stage call); with knn alone the generated sets are not built.  return_sets: (values, {z, pz, x, gx}), with
+        knn also y, with knn alone {z, x, y}."""
         B = self.cfg.B
-        cap = {'mmd': int(self.S.get('MMD_MAX_ROWS', MMD_MAX_ROWS)), 'prdc': int(self.S.get('PRDC_MAX_ROWS', PRDC_MAX_ROWS))}
-        on = [name for name, flag in (('mmd', mmd), ('prdc', prdc)) if flag]
+        cap = {'mmd': int(self.S.get('MMD_MAX_ROWS', MMD_MAX_ROWS)), 'prdc': int(self.S.get('PRDC_MAX_ROWS', PRDC_MAX_ROWS)),
+               'knn': int(self.S.get('KNN_MAX_ROWS', KNN_MAX_ROWS))}
+        on = [name for name, flag in (('mmd', mmd), ('prdc', prdc), ('knn', knn)) if flag]
         if not on:
-            raise ValueError('set_scores: neither score was asked for')
+            raise ValueError('set_scores: no score was asked for')
         k = int(self.S.get('PRDC_K', PRDC_K))
+        knn_k = int(self.S.get('KNN_K', KNN_K))
+        if knn and not 1 <= knn_k <= F.KNN_MAX_K:
+            raise ValueError('KNN_K = %d: 1 <= KNN_K <= %d expected' % (knn_k, F.KNN_MAX_K))
         with self._guard():
-            sets = self._score_sets(batches, max(cap[name] for name in on))
+            sets = self._score_sets(batches, max(cap[name] for name in on), generated=bool(mmd or prdc), labels=bool(knn))
             rows = {name: min(sets['z'].shape[0], max(1, cap[name] // B) * B) for name in on}
             names, vals = [], []
             if mmd:
@@ -313,6 +332,12 @@ class Evaluator(_Passes):
                 for space, a, b in (('z', 'z', 'pz'), ('x', 'x', 'gx')):
                     names += ['dev %s %s' % (what, space) for what in ('precision', 'recall', 'density', 'coverage')]
                     vals.append(F.prdc(sets[a][:rows['prdc']], sets[b][:rows['prdc']], k))
+            if knn:
+                if knn_k > rows['knn'] - 1:
+                    raise ValueError('KNN_K = %d needs more than %d rows' % (knn_k, rows['knn']))
+                for space in ('z', 'x'):
+                    names.append('dev knn accuracy ' + space)
+                    vals.append(F.knn_accuracy(sets[space][:rows['knn']], sets['y'][:rows['knn']], knn_k))
             vals = torch.cat(vals).cpu().numpy()
         res = {name: float(v) for name, v in zip(names, vals)}
         return (res, sets) if return_sets else res
@@ -329,6 +354,14 @@ class Evaluator(_Passes):
         the dev images / the dev images, generated = as many prior draws / Generator(p_z) -- at most PRDC_MAX_ROWS rows per set, by
         functional.prdc.  ONE host synchronisation for all eight.  return_sets: (values, {z, pz, x, gx})."""
         return self.set_scores(batches, prdc=True, return_sets=return_sets)
+
+    def knn_scores(self, batches, return_sets=False):
+        """{'dev knn accuracy z', 'dev knn accuracy x'}: the leave-one-out KNN_K-nearest-neighbour (default 5) accuracy of the labelled dev
+        minibatches -- every row classified by the vote of its nearest OTHER rows, a tied vote to the smallest label -- in code space
+        (q_z as _score_sets builds it) and in pixel space (real_x as the nets see it), at most KNN_MAX_ROWS rows, by
+        functional.knn_accuracy.  ONE host synchronisation for both.  Unlabelled minibatches raise ValueError.
+        return_sets: (values, {z, x, y})."""
+        return self.set_scores(batches, knn=True, return_sets=return_sets)
 
     def manifold(self, batches, out_dir, frame):
         """embeds the point sets of latent_sets with functional.tsne and writes the scatters under the reference's file names; returns
@@ -584,6 +617,7 @@ def main(argv=None):
     ap.add_argument('--manifold', action='store_true', help='also write the latent-space t-SNE pictures of the MNIST scripts to --out-dir')
     ap.add_argument('--mmd', action='store_true', help='also score the dev set by the unbiased MMD^2 of codes and of images (dev mmd z / dev mmd x; image scripts)')
     ap.add_argument('--prdc', action='store_true', help='also score the dev set by k-NN-ball precision / recall / density / coverage of codes and of images (eight dev rows; image scripts)')
+    ap.add_argument('--knn', action='store_true', help='also score the labelled dev set by the leave-one-out k-NN accuracy of codes and of images (dev knn accuracy z / x; image scripts)')
     ap.add_argument('--set', action='append', default=[], metavar='KEY=VALUE', help='override an UPPERCASE setting (int / float / str)')
     a = ap.parse_args(argv)
     over = {}
@@ -602,6 +636,8 @@ def main(argv=None):
         ap.error('--mmd: the state-space scripts have no single code to compare')
     if a.prdc and os.path.splitext(os.path.basename(a.script))[0] in run._SEQUENCE_SCRIPTS:
         ap.error('--prdc: the state-space scripts have no single code to compare')
+    if a.knn and os.path.splitext(os.path.basename(a.script))[0] in run._SEQUENCE_SCRIPTS:
+        ap.error('--knn: the state-space scripts have no single code to compare')
     if a.manifold:          # (checked before anything is built)
         name = os.path.splitext(os.path.basename(a.script))[0]
         if name not in MANIFOLD_SCRIPTS:
@@ -618,15 +654,16 @@ def main(argv=None):
         model = StateSpaceGAN(cfg)
     tr = Trainer(cfg, device=lib.get_device(), graph=False, model=model)
     checkpoint.restore(a.ckpt, tr)
-    res = evaluate_once(tr, S, out_dir=a.out_dir, manifold=a.manifold, mmd=a.mmd, prdc=a.prdc)
+    res = evaluate_once(tr, S, out_dir=a.out_dir, manifold=a.manifold, mmd=a.mmd, prdc=a.prdc, knn=a.knn)
     for k in sorted(res):
         print('%s\t%s' % (k, res[k]))
     return res
 
 
-def evaluate_once(tr, S, out_dir=None, frame='eval', manifold=False, mmd=False, prdc=False):
+def evaluate_once(tr, S, out_dir=None, frame='eval', manifold=False, mmd=False, prdc=False, knn=False):
     """every pass the script's data allow, once -> {name: value}; manifold: the latent-space pictures too (labelled dev data only);
-    mmd: the two dev-set MMD^2 scores too; prdc: the eight precision / recall / density / coverage scores too (one build of the sets for both)"""
+    mmd: the two dev-set MMD^2 scores too; prdc: the eight precision / recall / density / coverage scores too; knn: the two k-NN
+    accuracies too (labelled dev data only) -- one build of the sets for the three"""
     from . import run
     if S['DATASET'] in run.SEQUENCE_DATASETS:       # the video passes: files only (train_data: the first dev minibatch)
         ev = SequenceEvaluator(tr, S)
@@ -639,8 +676,11 @@ def evaluate_once(tr, S, out_dir=None, frame='eval', manifold=False, mmd=False, 
     res = dict(ev.dev_costs(dev))
     if tr.cfg.K and test is not None:
         res['testing accuracy'] = ev.cluster_accuracy(test)
-    if mmd or prdc:
-        res.update(ev.set_scores(dev, mmd=mmd, prdc=prdc))
+    if knn and not run.labelled(dev):
+        print('[evaluate] dev knn accuracy skipped: no labelled dev set')
+        knn = False
+    if mmd or prdc or knn:
+        res.update(ev.set_scores(dev, mmd=mmd, prdc=prdc, knn=knn))
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
         ev.set_fixed_data(dev[0])

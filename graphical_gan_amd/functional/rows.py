@@ -392,6 +392,83 @@ def prdc(x, y, k=5):
     return sums / torch.stack([den(n), den(m), den(k * n), den(m)])
 
 
+KNN_MAX_K = 8                 # include/ggan.h: GGAN_KNN_MAX_K neighbours per list
+KNN_MAX_CLASSES = 1024        # ... and the widest confusion matrix of ggan_knn_vote
+
+
+def knn_lists(q, c, k, skip_diag=False, return_d2=False):
+    """per row of q [m, d]: the indices of its k nearest rows of c [n, d], ascending in the total order (squared distance, index) -- a tie
+    in distance goes to the lower index (ggan_knn_lists) -> int32 [m, k] device tensor, with return_d2 also the float32 [m, k] squared
+    distances.  skip_diag (m == n): candidate i is left out for query i, by index.  Forward only."""
+    name = 'knn_lists'
+    if q.dim() != 2 or c.dim() != 2 or q.shape[1] != c.shape[1]:
+        raise ValueError('%s: [rows, d] sets of one width expected, got %s, %s' % (name, tuple(q.shape), tuple(c.shape)))
+    (m, d), n, k, skip = q.shape, c.shape[0], int(k), bool(skip_diag)
+    if skip and m != n:
+        raise ValueError('%s: skip_diag needs as many candidates as queries, got %d and %d' % (name, n, m))
+    if not 1 <= k <= KNN_MAX_K or k > n - (1 if skip else 0):
+        raise ValueError('%s: 1 <= k <= min(%d, candidates%s) expected, got k = %s with %d candidates'
+                         % (name, KNN_MAX_K, ' - 1' if skip else '', k, n))
+    if torch.is_grad_enabled() and (q.requires_grad or c.requires_grad):
+        raise _lib.GganError('%s has no backward: detach the inputs' % name)
+    q, c = _c(q), _c(c)
+    nbytes = int(_L().ggan_knn_lists_workspace(m, n, k))
+    ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=q.device)
+    idx = torch.empty((m, k), dtype=torch.int32, device=q.device)
+    d2 = torch.empty((m, k), dtype=torch.float32, device=q.device) if return_d2 else None
+    check(_L().ggan_knn_lists(_p(q), _p(c), m, n, d, k, 1 if skip else 0, _p(idx), _p(d2), _p(ws), nbytes, _stream()), 'ggan_knn_lists')
+    return (idx, d2) if return_d2 else idx
+
+
+def _labels(name, what, t, rows, device):
+    if t.dim() != 1 or t.dtype != torch.int32 or (rows is not None and t.shape[0] != rows) or t.device != device:
+        raise ValueError('%s: %s must be int32 [%s] on %s, got %s %s on %s'
+                         % (name, what, 'rows' if rows is None else rows, device, t.dtype, tuple(t.shape), t.device))
+    return t.contiguous()
+
+
+def knn_vote(idx, labels_c, labels_q=None, classes=None):
+    """the k-NN vote of neighbour lists idx [m, k] (int32, rows of the candidate set) over the candidates' labels_c (int32): pred[i] = the
+    most frequent label of the list, the smallest one on a tied vote (ggan_knn_vote) -> pred int32 [m]; with labels_q (int32 [m]) also
+    correct = #{pred == labels_q} (int32 [1]): (pred, correct); with classes (<= 1024) too the confusion matrix int32 [classes, classes],
+    rows the queries' labels: (pred, correct, confusion).  Every index must be a row of labels_c.  Device tensors; forward only."""
+    name = 'knn_vote'
+    if idx.dim() != 2 or idx.dtype != torch.int32 or not 1 <= idx.shape[1] <= KNN_MAX_K or idx.shape[0] < 1:
+        raise ValueError('%s: int32 lists [m, 1 <= k <= %d] expected, got %s %s' % (name, KNN_MAX_K, idx.dtype, tuple(idx.shape)))
+    if idx.device.type != 'cuda':
+        raise _lib.GganError('%s has no CPU path' % name)
+    (m, k), dev = idx.shape, idx.device
+    idx, labels_c = idx.contiguous(), _labels(name, 'labels_c', labels_c, None, dev)
+    if classes is not None and labels_q is None:
+        raise ValueError('%s: a confusion matrix needs labels_q' % name)
+    if classes is not None and not 1 <= int(classes) <= KNN_MAX_CLASSES:
+        raise ValueError('%s: 1 <= classes <= %d expected, got %s' % (name, KNN_MAX_CLASSES, classes))
+    pred = torch.empty((m,), dtype=torch.int32, device=dev)
+    correct = confusion = None
+    if labels_q is not None:
+        labels_q = _labels(name, 'labels_q', labels_q, m, dev)
+        correct = torch.zeros((1,), dtype=torch.int32, device=dev)
+        if classes is not None:
+            confusion = torch.zeros((int(classes), int(classes)), dtype=torch.int32, device=dev)
+    check(_L().ggan_knn_vote(_p(idx), _p(labels_c), _p(labels_q), m, k, int(classes or 0), _p(pred), _p(correct), _p(confusion), _stream()),
+          'ggan_knn_vote')
+    if labels_q is None:
+        return pred
+    return (pred, correct) if confusion is None else (pred, correct, confusion)
+
+
+def knn_accuracy(z, y, k, classes=None, return_pred=False):
+    """leave-one-out k-NN accuracy of the labelled set (z [n, d], y int32 [n]): every row is classified by the vote of its k nearest OTHER
+    rows (knn_lists with skip_diag, knn_vote) -> float64 [1] device tensor, formed on the device: the caller takes the host
+    synchronisation.  classes only checks the bound of the vote's optional outputs.  return_pred: (accuracy, pred int32 [n])."""
+    if classes is not None and not 1 <= int(classes) <= KNN_MAX_CLASSES:
+        raise ValueError('knn_accuracy: 1 <= classes <= %d expected, got %s' % (KNN_MAX_CLASSES, classes))
+    idx = knn_lists(z, z, k, skip_diag=True)
+    pred, correct = knn_vote(idx, y, y)
+    acc = correct.double() / torch.full((1,), float(z.shape[0]), dtype=torch.float64, device=z.device)
+    return (acc, pred) if return_pred else acc
+
+
 class Reparam(Function):
     """(z, std) = (mean + eps * exp(log_std), exp(log_std)): the stochastic encoder head (gan_inference_cifar10.py:173-188)"""
 

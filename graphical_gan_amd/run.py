@@ -160,6 +160,24 @@ def prdc_due(S, it):
     return bool(n and it % n == n - 1)
 
 
+# the dev-set k-NN accuracy of codes and of images (evaluate.Evaluator.knn_scores): as the two passes above, off unless asked for, a switch
+# and a cadence of their own; it needs a labelled dev set
+def knn_settings(script):
+    """{'KNN_EVERY': N} for the eight image scripts when $GGAN_KNN_EVERY = N is set, {} otherwise -- and always {} for the two state-space
+    scripts, which have no single code to compare"""
+    name = os.path.splitext(os.path.basename(script))[0]
+    every = os.environ.get('GGAN_KNN_EVERY')
+    if name not in _IMAGE_SCRIPTS or not every:
+        return {}
+    return {'KNN_EVERY': int(every)}
+
+
+def knn_due(S, it):
+    """does the pass fire after iteration `it`: it % N == N - 1, the cadence of the other passes"""
+    n = int(S.get('KNN_EVERY') or 0)
+    return bool(n and it % n == n - 1)
+
+
 def labelled(batches):
     """are these minibatches (images, labels) pairs"""
     return bool(batches) and all(isinstance(b, (tuple, list)) and len(b) > 1 and b[1] is not None for b in batches)
@@ -361,16 +379,22 @@ def train(S, cfg, model=None, out_dir=None):
             manifold = None
         else:
             m_eval = evaluator if evaluator is not None else Evaluator(tr, S)
-    mmd_eval = None            # the evaluator of the set-level scores: dev mmd (MMD_EVERY) and dev precision / ... / coverage (PRDC_EVERY)
-    if (S.get('MMD_EVERY') or S.get('PRDC_EVERY')) and (tr.world == 1 or torch.distributed.get_rank() == 0):
+    # the evaluator of the set-level scores: dev mmd (MMD_EVERY), dev precision / ... / coverage (PRDC_EVERY), dev knn accuracy (KNN_EVERY)
+    mmd_eval, knn_on = None, False
+    if (S.get('MMD_EVERY') or S.get('PRDC_EVERY') or S.get('KNN_EVERY')) and (tr.world == 1 or torch.distributed.get_rank() == 0):
         from .evaluate import Evaluator
         from .models_ssgan import StateSpaceGAN
         if isinstance(tr.model, StateSpaceGAN):
             print('[run] %s skipped: the state-space models have no single code to compare'
-                  % ' and '.join(n for n, key in (('dev mmd', 'MMD_EVERY'), ('dev precision / recall / density / coverage', 'PRDC_EVERY')) if S.get(key)))
+                  % ' and '.join(n for n, key in (('dev mmd', 'MMD_EVERY'), ('dev precision / recall / density / coverage', 'PRDC_EVERY'),
+                                                    ('dev knn accuracy', 'KNN_EVERY')) if S.get(key)))
         else:
             mmd_eval = evaluator if evaluator is not None else (m_eval if manifold else Evaluator(tr, S))
             mmd_dev = ev_dev if evaluator is not None else (m_dev if manifold else eval_sets(S, tr.model, device)[0])
+            knn_on = bool(S.get('KNN_EVERY'))
+            if knn_on and not labelled(mmd_dev):
+                print('[run] dev knn accuracy skipped: no labelled dev set (%s data)' % source)
+                knn_on = False
     eval_ms = 0.0            # wall time of the evaluation passes (kept out of `time`)
     for it in range(S['ITERS']):
         if (it == 2 and isinstance(batches, DevicePrefetcher) and S.get('RING_FEED', True) and tr.graph_enabled
@@ -396,8 +420,8 @@ def train(S, cfg, model=None, out_dir=None):
             lib.plot.flush(out_dir, os.path.join(out_dir, 'logfile.txt') if out_dir else None)
         if manifold_due(manifold, it, S['ITERS']):
             eval_ms += _manifold(m_eval, m_dev, it, out_dir, device)
-        if mmd_eval is not None and (mmd_due(S, it) or prdc_due(S, it)):
-            eval_ms += _set_scores(mmd_eval, mmd_dev, device, mmd_due(S, it), prdc_due(S, it))
+        if mmd_eval is not None and (mmd_due(S, it) or prdc_due(S, it) or (knn_on and knn_due(S, it))):
+            eval_ms += _set_scores(mmd_eval, mmd_dev, device, mmd_due(S, it), prdc_due(S, it), knn_on and knn_due(S, it))
             lib.plot.flush(out_dir, os.path.join(out_dir, 'logfile.txt') if out_dir else None)
         lib.plot.tick()
         if out_dir and S.get('SAVE_EVERY') and (it + 1) % S['SAVE_EVERY'] == 0:
@@ -449,13 +473,13 @@ def _manifold(ev, dev, it, out_dir, device):
     return (time.time() - t0) * 1e3
 
 
-def _set_scores(ev, dev, device, mmd, prdc):
-    """the dev-set MMD^2 and / or precision / recall / density / coverage scores, from one build of the sets, logged through lib.plot ->
-    milliseconds they took"""
+def _set_scores(ev, dev, device, mmd, prdc, knn=False):
+    """the dev-set MMD^2, precision / recall / density / coverage and k-NN accuracy scores that are due, from one build of the sets, logged
+    through lib.plot -> milliseconds they took"""
     if device.type == 'cuda':
         torch.cuda.synchronize(device)
     t0 = time.time()
-    for k, v in ev.set_scores(dev, mmd=mmd, prdc=prdc).items():
+    for k, v in ev.set_scores(dev, mmd=mmd, prdc=prdc, knn=knn).items():
         lib.plot.plot(k, v)
     if device.type == 'cuda':
         torch.cuda.synchronize(device)

@@ -442,6 +442,27 @@ size_t ggan_ball_counts_workspace(int m, int n);
 int ggan_ball_counts(const float* A, const float* B, int m, int n, int d, const float* rB2, int* cnt, float* min2, void* ws,
                      size_t ws_bytes, ggan_stream_t stream);
 
+/* Labelled neighbour lists across two row sets: the primitive behind the k-NN accuracy of the codes (evaluate.Evaluator.knn_scores,
+ * functional.knn_lists / knn_vote / knn_accuracy).  Q[m,d] queries, C[n,d] candidates, row-major device fp32, Q == C allowed, any d >= 1,
+ * 1 <= m, n <= 131072; D(i,j) = max(|q_i|^2 + |c_j|^2 - 2 q_i.c_j, 0) from the Gram tiles of ggan_knn_radii.
+ *   ggan_knn_lists: idx[i, 0..k) (int32 [m,k]) = the k candidates smallest under the TOTAL order (D(i,j), j), ascending: a tie in distance
+ *                   goes to the lower candidate index, whatever the launch shape, so the result is unique.  d2 [m,k] (may be NULL) their
+ *                   distances.  skip_diag != 0 (needs m == n) leaves out candidate j == i by INDEX; a duplicate of row i still counts.
+ *                   1 <= k <= GGAN_KNN_MAX_K, k <= n - (skip_diag ? 1 : 0).  ws: ggan_knn_lists_workspace(m, n, k) bytes of 16-byte
+ *                   aligned device scratch (0 = arguments out of range).  No floating-point atomics: repeated calls give the same bits.
+ *   ggan_knn_vote:  pred[i] = the label that occurs most often among labels_c[idx[i, 0..k)], the SMALLEST such label on a tied vote: a
+ *                   function of the label multiset, not of the order in the list.  Every idx value must index labels_c.  labels_q
+ *                   (may be NULL) the queries' own labels: correct[0] += #{i : pred[i] == labels_q[i]} and
+ *                   confusion[labels_q[i] * classes + pred[i]] += 1 (int32 [classes, classes], classes <= 1024; a pair with a label
+ *                   outside 0 .. classes-1 is not counted); either may be NULL, the caller zeroes them.  Integer adds only.
+ * Forward only.  Added without a version change: no existing entry point or struct is touched. */
+#define GGAN_KNN_MAX_K 8
+size_t ggan_knn_lists_workspace(int m, int n, int k);
+int ggan_knn_lists(const float* Q, const float* C, int m, int n, int d, int k, int skip_diag, int32_t* idx, float* d2, void* ws,
+                   size_t ws_bytes, ggan_stream_t stream);
+int ggan_knn_vote(const int32_t* idx, const int32_t* labels_c, const int32_t* labels_q, int m, int k, int classes, int32_t* pred,
+                  int32_t* correct, int32_t* confusion, ggan_stream_t stream);
+
 /* Stochastic encoder head, TYPE_Q = 'learn_std' (gan_inference_cifar10.py:173-188): std = exp(log_std), z = mean + eps * std; the backward
  * takes the gradients arriving at z and at std (either may be NULL). */
 int ggan_reparam_fwd(const float* mean, const float* log_std, const float* eps, float* z, float* std_out, size_t n, ggan_stream_t stream);

@@ -14,6 +14,7 @@ SETTINGS.update(DATA_DIR=os.environ.get('GGAN_DATA_DIR', ''), OUT_DIR=os.environ
 SETTINGS.update(run.eval_settings(__file__))     # dev costs / samples / reconstructions (/ testing accuracy) at the reference's cadence
 SETTINGS.update(run.mmd_settings(__file__))      # dev mmd z / dev mmd x every $GGAN_MMD_EVERY iterations (off when unset)
 SETTINGS.update(run.prdc_settings(__file__))     # dev precision / recall / density / coverage z / x every $GGAN_PRDC_EVERY iterations (off when unset)
+SETTINGS.update(run.knn_settings(__file__))      # dev knn accuracy z / x every $GGAN_KNN_EVERY iterations (off when unset; needs a labelled dev set)
 if len(sys.argv) > 1:
     SETTINGS['ITERS'] = int(sys.argv[1])
 globals().update(SETTINGS)          # BATCH_SIZE, DIM, DIM_LATENT, CRITIC_ITERS, ... as module constants, as in the reference
