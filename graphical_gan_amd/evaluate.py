@@ -20,6 +20,10 @@
   knn_scores         `dev knn accuracy z|x`: the leave-one-out KNN_K-nearest-neighbour accuracy of the labelled dev set in code space
                      (q_z) and in pixel space -- ggan_knn_lists and ggan_knn_vote.  The one number that looks at a label: whether
                      images of one class are neighbours in z more often than in x (README).
+  parzen_scores      `dev parzen ll x` / `dev parzen se x` / `dev parzen sigma x`: the Gaussian Parzen-window log-likelihood of held-out dev
+                     images under a kernel density fitted to as many generated ones (Breuleux et al. 2011; Goodfellow et al. 2014),
+                     pixels in [0, 1], the bandwidth chosen on the leading validation rows from PARZEN_SIGMAS -- ggan_parzen_lse, one
+                     log-sum-exp sweep for all rows and bandwidths.  The one number with a published protocol (README for its limits).
 
 The passes are safe in the middle of training: they run under torch.no_grad() on the current stream only (no second stream, no
 collective), with a feed dict and a noise generator state of their own -- the Trainer's static feed buffers, ring slots and noise state
@@ -39,7 +43,7 @@ run by SequenceEvaluator on a models_ssgan.StateSpaceGAN under the same rules:
 Each is written as a .png sheet (one sequence per row) and a looping .gif; the bytes of both come from one ggan_video_sheet_u8 launch.
 
 `python -m graphical_gan_amd.evaluate CKPT --script gmgan_inference_mnist [--data-dir DIR]` scores a saved checkpoint
-(`--out-dir DIR --manifold` also writes the latent-space pictures of the two MNIST scripts, `--mmd` adds the two MMD^2 rows, `--prdc` the eight precision / recall / density / coverage rows, `--knn` the two k-NN accuracy rows);
+(`--out-dir DIR --manifold` also writes the latent-space pictures of the two MNIST scripts, `--mmd` adds the two MMD^2 rows, `--prdc` the eight precision / recall / density / coverage rows, `--knn` the two k-NN accuracy rows, `--parzen` the three Parzen-window rows);
 `... CKPT --script ssgan_inference_moving_mnist|ssgan_inference_chairs [--data-dir DIR] --out-dir DIR` writes the four pairs of files."""
 import argparse
 import contextlib
@@ -57,6 +61,9 @@ PRDC_MAX_ROWS = 10000     # rows per set of the prdc_scores pass (settings: PRDC
 PRDC_K = 5                # neighbours of its k-NN balls (settings: PRDC_K; at most functional.PRDC_MAX_K)
 KNN_MAX_ROWS = 10000      # rows of the knn_scores pass (settings: KNN_MAX_ROWS)
 KNN_K = 5                 # neighbours that vote in it (settings: KNN_K; at most functional.KNN_MAX_K)
+PARZEN_MAX_ROWS = 10000   # rows per set of the parzen_scores pass (settings: PARZEN_MAX_ROWS): the protocol's 10000 generated samples
+PARZEN_VALID_ROWS = 1000  # leading dev rows its bandwidth is chosen on (settings: PARZEN_VALID_ROWS)
+PARZEN_SIGMAS = np.logspace(-1, 0, 10)    # the protocol's bandwidth grid, in [0, 1] pixel units (settings: PARZEN_SIGMAS; at most functional.PARZEN_MAX_SIGMAS)
 EVAL_SEED = 7919          # offset of the evaluator's noise seeds from the settings seed (the Trainer's stream of draws is not touched)
 
 # the reference's output file names, per script: (samples, reconstructions), formatted with frame= and mode=
@@ -300,24 +307,33 @@ class Evaluator(_Passes):
             sets['gx'][rows].copy_(self.model.Generator(sets['pz'][rows]).float())
         return sets
 
-    def set_scores(self, batches, mmd=False, prdc=False, knn=False, return_sets=False):
+    def set_scores(self, batches, mmd=False, prdc=False, knn=False, return_sets=False, parzen=False):
         """the set-level scores asked for, from ONE build of the sets (_score_sets: one stream of noise draws, whichever scores are on) and
-        ONE host synchronisation: mmd -> the two values of mmd_scores, prdc -> the eight of prdc_scores, knn -> the two of knn_scores, in
-        that order.  With several on, each scores the leading rows its own row cap allows.  knn needs labelled minibatches (the labels come
-        from the sets' own _stage call); with knn alone the generated sets are not built.  return_sets: (values, {z, pz, x, gx}), with
-        knn also y, with knn alone {z, x, y}."""
+        ONE host synchronisation: mmd -> the two values of mmd_scores, prdc -> the eight of prdc_scores, knn -> the two of knn_scores,
+        parzen -> the three of parzen_scores, in that order.  With several on, each scores the leading rows its own row cap allows.  knn
+        needs labelled minibatches (the labels come from the sets' own _stage call); with knn alone the generated sets are not built.
+        parzen needs at least two full minibatches within its row cap (one to choose the bandwidth on, one to score) and at most
+        functional.PARZEN_MAX_SIGMAS bandwidths.  return_sets: (values, {z, pz, x, gx}), with knn also y, with knn alone {z, x, y}."""
         B = self.cfg.B
         cap = {'mmd': int(self.S.get('MMD_MAX_ROWS', MMD_MAX_ROWS)), 'prdc': int(self.S.get('PRDC_MAX_ROWS', PRDC_MAX_ROWS)),
-               'knn': int(self.S.get('KNN_MAX_ROWS', KNN_MAX_ROWS))}
-        on = [name for name, flag in (('mmd', mmd), ('prdc', prdc), ('knn', knn)) if flag]
+               'knn': int(self.S.get('KNN_MAX_ROWS', KNN_MAX_ROWS)), 'parzen': int(self.S.get('PARZEN_MAX_ROWS', PARZEN_MAX_ROWS))}
+        on = [name for name, flag in (('mmd', mmd), ('prdc', prdc), ('knn', knn), ('parzen', parzen)) if flag]
         if not on:
             raise ValueError('set_scores: no score was asked for')
         k = int(self.S.get('PRDC_K', PRDC_K))
         knn_k = int(self.S.get('KNN_K', KNN_K))
         if knn and not 1 <= knn_k <= F.KNN_MAX_K:
             raise ValueError('KNN_K = %d: 1 <= KNN_K <= %d expected' % (knn_k, F.KNN_MAX_K))
+        if parzen:
+            sigmas = [float(v) for v in np.asarray(self.S.get('PARZEN_SIGMAS', PARZEN_SIGMAS), dtype=np.float64).reshape(-1)]
+            if not 1 <= len(sigmas) <= F.PARZEN_MAX_SIGMAS:
+                raise ValueError('PARZEN_SIGMAS: 1 .. %d bandwidths expected, got %d' % (F.PARZEN_MAX_SIGMAS, len(sigmas)))
+            full = sum(1 for b in batches if _split(b)[0].shape[0] == B)
+            if min(full, max(1, cap['parzen'] // B)) < 2:
+                raise ValueError('the Parzen pass needs at least 2 full minibatches of %d rows within PARZEN_MAX_ROWS = %d: one to '
+                                 'choose the bandwidth on, one to score' % (B, cap['parzen']))
         with self._guard():
-            sets = self._score_sets(batches, max(cap[name] for name in on), generated=bool(mmd or prdc), labels=bool(knn))
+            sets = self._score_sets(batches, max(cap[name] for name in on), generated=bool(mmd or prdc or parzen), labels=bool(knn))
             rows = {name: min(sets['z'].shape[0], max(1, cap[name] // B) * B) for name in on}
             names, vals = [], []
             if mmd:
@@ -338,6 +354,9 @@ class Evaluator(_Passes):
                 for space in ('z', 'x'):
                     names.append('dev knn accuracy ' + space)
                     vals.append(F.knn_accuracy(sets[space][:rows['knn']], sets['y'][:rows['knn']], knn_k))
+            if parzen:
+                names += ['dev parzen ll x', 'dev parzen se x', 'dev parzen sigma x']
+                vals.append(self._parzen(sets['x'][:rows['parzen']], sets['gx'][:rows['parzen']], sigmas))
             vals = torch.cat(vals).cpu().numpy()
         res = {name: float(v) for name, v in zip(names, vals)}
         return (res, sets) if return_sets else res
@@ -362,6 +381,34 @@ class Evaluator(_Passes):
         functional.knn_accuracy.  ONE host synchronisation for both.  Unlabelled minibatches raise ValueError.
         return_sets: (values, {z, x, y})."""
         return self.set_scores(batches, knn=True, return_sets=return_sets)
+
+    def _parzen(self, x, gx, sigmas):
+        """(mean, standard error, bandwidth) of the Parzen-window log-likelihood of the held-out rows of x under the kernel density of gx
+        -> float64 [3] device tensor.  ONE parzen_ll call over all rows and bandwidths; the leading v rows of x choose the bandwidth (the
+        arg-max of their mean, the first on a tie), the rest are scored.  Selection and statistics stay on the device."""
+        B, rows = self.cfg.B, x.shape[0]
+        v = B * max(1, min(int(self.S.get('PARZEN_VALID_ROWS', PARZEN_VALID_ROWS)) // B, (rows // B) // 2))
+        lo = 0.0 if self.cfg.out_act == 'sigmoid' else -1.0                 # (as _to_unit: the width of the pixel range is 1 - lo)
+        ll = F.parzen_ll(x, gx, sigmas, scale=1.0 - lo)                       # [ns, rows] float64
+        valid = ll[:, :v].mean(dim=1)
+        # the first bandwidth whose validation mean is the largest (argmax alone does not promise which of equal values it returns)
+        order = torch.arange(len(sigmas), device=ll.device)
+        best = torch.where(valid == valid.max(), order, torch.full_like(order, len(sigmas))).min().reshape(1)
+        held = ll[:, v:].index_select(0, best).reshape(-1)
+        grid = torch.empty((len(sigmas),), dtype=torch.float64, device=ll.device)
+        for g, sg in enumerate(sigmas):
+            grid[g].fill_(sg)
+        count = torch.full((), float(held.shape[0]), dtype=torch.float64, device=ll.device)
+        return torch.stack([held.mean(), held.std(unbiased=False) / torch.sqrt(count), grid.index_select(0, best).reshape(())])
+
+    def parzen_scores(self, batches, return_sets=False):
+        """{'dev parzen ll x', 'dev parzen se x', 'dev parzen sigma x'}: the Gaussian Parzen-window log-likelihood (nats, pixels in [0, 1])
+        of held-out dev images under a kernel density fitted to as many generated images (Breuleux et al. 2011; Goodfellow et al. 2014),
+        over at most PARZEN_MAX_ROWS rows per set of _score_sets: the leading B max(1, min(PARZEN_VALID_ROWS // B, minibatches // 2)) dev
+        rows choose the bandwidth from PARZEN_SIGMAS, the rest give the mean and its standard error (the population std / sqrt(count), as
+        the protocol's script); sigma is the chosen bandwidth.  functional.parzen_ll, ONE host synchronisation for the three.  Fewer than
+        two full minibatches raise ValueError.  There is no z twin: in code space the prior's density is known in closed form.  return_sets: (values, {z, pz, x, gx})."""
+        return self.set_scores(batches, parzen=True, return_sets=return_sets)
 
     def manifold(self, batches, out_dir, frame):
         """embeds the point sets of latent_sets with functional.tsne and writes the scatters under the reference's file names; returns
@@ -618,6 +665,7 @@ def main(argv=None):
     ap.add_argument('--mmd', action='store_true', help='also score the dev set by the unbiased MMD^2 of codes and of images (dev mmd z / dev mmd x; image scripts)')
     ap.add_argument('--prdc', action='store_true', help='also score the dev set by k-NN-ball precision / recall / density / coverage of codes and of images (eight dev rows; image scripts)')
     ap.add_argument('--knn', action='store_true', help='also score the labelled dev set by the leave-one-out k-NN accuracy of codes and of images (dev knn accuracy z / x; image scripts)')
+    ap.add_argument('--parzen', action='store_true', help='also score the dev set by the Gaussian Parzen-window log-likelihood of held-out images under generated ones (dev parzen ll / se / sigma x; image scripts)')
     ap.add_argument('--set', action='append', default=[], metavar='KEY=VALUE', help='override an UPPERCASE setting (int / float / str)')
     a = ap.parse_args(argv)
     over = {}
@@ -638,6 +686,8 @@ def main(argv=None):
         ap.error('--prdc: the state-space scripts have no single code to compare')
     if a.knn and os.path.splitext(os.path.basename(a.script))[0] in run._SEQUENCE_SCRIPTS:
         ap.error('--knn: the state-space scripts have no single code to compare')
+    if a.parzen and os.path.splitext(os.path.basename(a.script))[0] in run._SEQUENCE_SCRIPTS:
+        ap.error('--parzen: the state-space scripts have no single set of images to compare')
     if a.manifold:          # (checked before anything is built)
         name = os.path.splitext(os.path.basename(a.script))[0]
         if name not in MANIFOLD_SCRIPTS:
@@ -654,16 +704,16 @@ def main(argv=None):
         model = StateSpaceGAN(cfg)
     tr = Trainer(cfg, device=lib.get_device(), graph=False, model=model)
     checkpoint.restore(a.ckpt, tr)
-    res = evaluate_once(tr, S, out_dir=a.out_dir, manifold=a.manifold, mmd=a.mmd, prdc=a.prdc, knn=a.knn)
+    res = evaluate_once(tr, S, out_dir=a.out_dir, manifold=a.manifold, mmd=a.mmd, prdc=a.prdc, knn=a.knn, parzen=a.parzen)
     for k in sorted(res):
         print('%s\t%s' % (k, res[k]))
     return res
 
 
-def evaluate_once(tr, S, out_dir=None, frame='eval', manifold=False, mmd=False, prdc=False, knn=False):
+def evaluate_once(tr, S, out_dir=None, frame='eval', manifold=False, mmd=False, prdc=False, knn=False, parzen=False):
     """every pass the script's data allow, once -> {name: value}; manifold: the latent-space pictures too (labelled dev data only);
     mmd: the two dev-set MMD^2 scores too; prdc: the eight precision / recall / density / coverage scores too; knn: the two k-NN
-    accuracies too (labelled dev data only) -- one build of the sets for the three"""
+    accuracies too (labelled dev data only); parzen: the three Parzen-window values too -- one build of the sets for the four"""
     from . import run
     if S['DATASET'] in run.SEQUENCE_DATASETS:       # the video passes: files only (train_data: the first dev minibatch)
         ev = SequenceEvaluator(tr, S)
@@ -679,8 +729,8 @@ def evaluate_once(tr, S, out_dir=None, frame='eval', manifold=False, mmd=False, 
     if knn and not run.labelled(dev):
         print('[evaluate] dev knn accuracy skipped: no labelled dev set')
         knn = False
-    if mmd or prdc or knn:
-        res.update(ev.set_scores(dev, mmd=mmd, prdc=prdc, knn=knn))
+    if mmd or prdc or knn or parzen:
+        res.update(ev.set_scores(dev, mmd=mmd, prdc=prdc, knn=knn, parzen=parzen))
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
         ev.set_fixed_data(dev[0])

@@ -1,5 +1,6 @@
 """row glue of the objectives: joins / splits / fan-out of row blocks, mixture and reparameterisation ops, the wali-gp interpolates."""
 import ctypes as C
+import math
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
@@ -467,6 +468,60 @@ def knn_accuracy(z, y, k, classes=None, return_pred=False):
     pred, correct = knn_vote(idx, y, y)
     acc = correct.double() / torch.full((1,), float(z.shape[0]), dtype=torch.float64, device=z.device)
     return (acc, pred) if return_pred else acc
+
+
+PARZEN_MAX_SIGMAS = 16        # include/ggan.h: GGAN_PARZEN_MAX_SIGMAS bandwidths per call
+
+
+def _sigmas(name, sigmas):
+    """the bandwidths as a list of 1 .. 16 finite positive floats (ValueError otherwise)"""
+    try:
+        sig = [float(v) for v in sigmas]
+    except TypeError:                  # one number
+        sig = [float(sigmas)]
+    if not 1 <= len(sig) <= PARZEN_MAX_SIGMAS:
+        raise ValueError('%s: 1 <= ns <= %d bandwidths expected, got %d' % (name, PARZEN_MAX_SIGMAS, len(sig)))
+    if any(not (math.isfinite(v) and v > 0.0) for v in sig):
+        raise ValueError('%s: every sigma must be finite and positive, got %s' % (name, sig))
+    return sig
+
+
+def parzen_lse(q, s, sigmas):
+    """lse[g, i] = log sum_j exp(-D(q_i, s_j) / (2 sigmas[g]^2)) over the rows of s [n, d], per row of q [m, d] and per bandwidth (at most
+    16 host numbers), D the squared distance of knn_lists; the sums are carried shifted by the row's minimum distance, so the result is
+    finite where a plain sum of kernel values is log 0 (ggan_parzen_lse) -> float32 [ns, m] device tensor.  Forward only."""
+    name = 'parzen_lse'
+    if q.dim() != 2 or s.dim() != 2 or q.shape[1] != s.shape[1]:
+        raise ValueError('%s: [rows, d] sets of one width expected, got %s, %s' % (name, tuple(q.shape), tuple(s.shape)))
+    sig = _sigmas(name, sigmas)
+    if torch.is_grad_enabled() and (q.requires_grad or s.requires_grad):
+        raise _lib.GganError('%s has no backward: detach the inputs' % name)
+    q, s = _c(q), _c(s)
+    (m, d), n, ns = q.shape, s.shape[0], len(sig)
+    nbytes = int(_L().ggan_parzen_lse_workspace(m, n, ns))
+    ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=q.device)
+    lse = torch.empty((ns, m), dtype=torch.float32, device=q.device)
+    host = (C.c_float * ns)(*sig)
+    check(_L().ggan_parzen_lse(_p(q), _p(s), m, n, d, C.cast(host, C.c_void_p), ns, _p(lse), _p(ws), nbytes, _stream()), 'ggan_parzen_lse')
+    return lse
+
+
+def parzen_ll(q, s, sigmas, scale=1.0):
+    """the Gaussian Parzen-window log-likelihood of every row of q under the kernel density of the rows of s, per bandwidth, in the
+    UNIT-INTERVAL pixel scale: ll[g, i] = parzen_lse(q, s, scale * sigmas)[g, i] - log n - (d / 2) log(2 pi sigmas[g]^2).  The rows are
+    handed in as the nets see them; scale is the width of their pixel range (1 for sigmoid outputs, 2 for tanh outputs): the bandwidth
+    times scale in the nets' units, normalised with the unscaled one, is exactly the density of the data mapped to [0, 1]
+    -> float64 [ns, m] device tensor, formed on the device: the caller takes the host synchronisation.  Forward only."""
+    sig, scale = _sigmas('parzen_ll', sigmas), float(scale)
+    if not (math.isfinite(scale) and scale > 0.0):
+        raise ValueError('parzen_ll: scale must be finite and positive, got %s' % scale)
+    lse = parzen_lse(q, s, [scale * v for v in sig])
+    n, d = s.shape
+    # (the constants are filled on the device, one launch per bandwidth: a tensor made from host numbers would be an upload the host waits for)
+    const = torch.empty((len(sig), 1), dtype=torch.float64, device=lse.device)
+    for g, v in enumerate(sig):
+        const[g].fill_(math.log(n) + 0.5 * d * math.log(2.0 * math.pi * v * v))
+    return lse.double() - const
 
 
 class Reparam(Function):

@@ -178,6 +178,24 @@ def knn_due(S, it):
     return bool(n and it % n == n - 1)
 
 
+# the Parzen-window log-likelihood of held-out dev images under generated ones (evaluate.Evaluator.parzen_scores): as the three passes
+# above, off unless asked for, a switch and a cadence of their own
+def parzen_settings(script):
+    """{'PARZEN_EVERY': N} for the eight image scripts when $GGAN_PARZEN_EVERY = N is set, {} otherwise -- and always {} for the two
+    state-space scripts, which have no single set of images to compare"""
+    name = os.path.splitext(os.path.basename(script))[0]
+    every = os.environ.get('GGAN_PARZEN_EVERY')
+    if name not in _IMAGE_SCRIPTS or not every:
+        return {}
+    return {'PARZEN_EVERY': int(every)}
+
+
+def parzen_due(S, it):
+    """does the pass fire after iteration `it`: it % N == N - 1, the cadence of the other passes"""
+    n = int(S.get('PARZEN_EVERY') or 0)
+    return bool(n and it % n == n - 1)
+
+
 def labelled(batches):
     """are these minibatches (images, labels) pairs"""
     return bool(batches) and all(isinstance(b, (tuple, list)) and len(b) > 1 and b[1] is not None for b in batches)
@@ -379,15 +397,16 @@ def train(S, cfg, model=None, out_dir=None):
             manifold = None
         else:
             m_eval = evaluator if evaluator is not None else Evaluator(tr, S)
-    # the evaluator of the set-level scores: dev mmd (MMD_EVERY), dev precision / ... / coverage (PRDC_EVERY), dev knn accuracy (KNN_EVERY)
+    # the evaluator of the set-level scores: dev mmd (MMD_EVERY), dev precision / ... / coverage (PRDC_EVERY), dev knn accuracy (KNN_EVERY),
+    # dev parzen ll / se / sigma (PARZEN_EVERY)
     mmd_eval, knn_on = None, False
-    if (S.get('MMD_EVERY') or S.get('PRDC_EVERY') or S.get('KNN_EVERY')) and (tr.world == 1 or torch.distributed.get_rank() == 0):
+    if (S.get('MMD_EVERY') or S.get('PRDC_EVERY') or S.get('KNN_EVERY') or S.get('PARZEN_EVERY')) and (tr.world == 1 or torch.distributed.get_rank() == 0):
         from .evaluate import Evaluator
         from .models_ssgan import StateSpaceGAN
         if isinstance(tr.model, StateSpaceGAN):
             print('[run] %s skipped: the state-space models have no single code to compare'
                   % ' and '.join(n for n, key in (('dev mmd', 'MMD_EVERY'), ('dev precision / recall / density / coverage', 'PRDC_EVERY'),
-                                                    ('dev knn accuracy', 'KNN_EVERY')) if S.get(key)))
+                                                    ('dev knn accuracy', 'KNN_EVERY'), ('dev parzen ll', 'PARZEN_EVERY')) if S.get(key)))
         else:
             mmd_eval = evaluator if evaluator is not None else (m_eval if manifold else Evaluator(tr, S))
             mmd_dev = ev_dev if evaluator is not None else (m_dev if manifold else eval_sets(S, tr.model, device)[0])
@@ -420,8 +439,8 @@ def train(S, cfg, model=None, out_dir=None):
             lib.plot.flush(out_dir, os.path.join(out_dir, 'logfile.txt') if out_dir else None)
         if manifold_due(manifold, it, S['ITERS']):
             eval_ms += _manifold(m_eval, m_dev, it, out_dir, device)
-        if mmd_eval is not None and (mmd_due(S, it) or prdc_due(S, it) or (knn_on and knn_due(S, it))):
-            eval_ms += _set_scores(mmd_eval, mmd_dev, device, mmd_due(S, it), prdc_due(S, it), knn_on and knn_due(S, it))
+        if mmd_eval is not None and (mmd_due(S, it) or prdc_due(S, it) or (knn_on and knn_due(S, it)) or parzen_due(S, it)):
+            eval_ms += _set_scores(mmd_eval, mmd_dev, device, mmd_due(S, it), prdc_due(S, it), knn_on and knn_due(S, it), parzen_due(S, it))
             lib.plot.flush(out_dir, os.path.join(out_dir, 'logfile.txt') if out_dir else None)
         lib.plot.tick()
         if out_dir and S.get('SAVE_EVERY') and (it + 1) % S['SAVE_EVERY'] == 0:
@@ -473,13 +492,13 @@ def _manifold(ev, dev, it, out_dir, device):
     return (time.time() - t0) * 1e3
 
 
-def _set_scores(ev, dev, device, mmd, prdc, knn=False):
-    """the dev-set MMD^2, precision / recall / density / coverage and k-NN accuracy scores that are due, from one build of the sets, logged
-    through lib.plot -> milliseconds they took"""
+def _set_scores(ev, dev, device, mmd, prdc, knn=False, parzen=False):
+    """the dev-set MMD^2, precision / recall / density / coverage, k-NN accuracy and Parzen-window scores that are due, from one build of the
+    sets, logged through lib.plot -> milliseconds they took"""
     if device.type == 'cuda':
         torch.cuda.synchronize(device)
     t0 = time.time()
-    for k, v in ev.set_scores(dev, mmd=mmd, prdc=prdc, knn=knn).items():
+    for k, v in ev.set_scores(dev, mmd=mmd, prdc=prdc, knn=knn, parzen=parzen).items():
         lib.plot.plot(k, v)
     if device.type == 'cuda':
         torch.cuda.synchronize(device)

@@ -463,6 +463,23 @@ int ggan_knn_lists(const float* Q, const float* C, int m, int n, int d, int k, i
 int ggan_knn_vote(const int32_t* idx, const int32_t* labels_c, const int32_t* labels_q, int m, int k, int classes, int32_t* pred,
                   int32_t* correct, int32_t* confusion, ggan_stream_t stream);
 
+/* Parzen-window log-sums across two row sets: the primitive behind the Gaussian Parzen-window log-likelihood of held-out rows under a
+ * kernel density fitted to generated ones (evaluate.Evaluator.parzen_scores, functional.parzen_lse / parzen_ll).  Q[m,d] queries, S[n,d]
+ * samples, row-major device fp32, Q == S allowed, any d >= 1, 1 <= m, n <= 131072; D(i,j) = max(|q_i|^2 + |s_j|^2 - 2 q_i.s_j, 0) from the
+ * Gram tiles of ggan_knn_radii; no row is left out.
+ *   ggan_parzen_lse: lse[s, i] (fp32 [ns,m]) = log sum_j exp(-D(i,j) / (2 sigmas[s]^2)) for the ns bandwidths of the HOST array sigmas,
+ *                    1 <= ns <= GGAN_PARZEN_MAX_SIGMAS, every one finite and positive.  The sums are carried shifted by the row's
+ *                    running minimum distance (one minimum serves all bandwidths), so the result is finite for every finite input;
+ *                    where only the nearest sample survives in fp32 it is -D_min / (2 sigma^2).  One pass over the Gram tiles.
+ *                    ws: ggan_parzen_lse_workspace(m, n, ns) bytes of 16-byte aligned device scratch, linear in m + n (times ns)
+ *                    (0 = arguments out of range).  Partial sums are combined in a fixed order, no floating-point atomics: repeated
+ *                    calls give the same bits, and a bandwidth's value does not depend on the others in the call.
+ * Forward only.  Added without a version change: no existing entry point or struct is touched. */
+#define GGAN_PARZEN_MAX_SIGMAS 16
+size_t ggan_parzen_lse_workspace(int m, int n, int ns);
+int ggan_parzen_lse(const float* Q, const float* S, int m, int n, int d, const float* sigmas /*host*/, int ns,
+                    float* lse /*device [ns, m]*/, void* ws, size_t ws_bytes, ggan_stream_t stream);
+
 /* Stochastic encoder head, TYPE_Q = 'learn_std' (gan_inference_cifar10.py:173-188): std = exp(log_std), z = mean + eps * std; the backward
  * takes the gradients arriving at z and at std (either may be NULL). */
 int ggan_reparam_fwd(const float* mean, const float* log_std, const float* eps, float* z, float* std_out, size_t n, ggan_stream_t stream);
