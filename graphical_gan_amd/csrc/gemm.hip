@@ -761,6 +761,25 @@ struct GemmPlan {
     void* ws;
 };
 
+// GGAN_TRACE_GEMM=1: one stderr line per launch with what a kernel name cannot show -- waves per workgroup, operand path (fast; -1: the
+// kernel has no such choice), loads in flight of the skinny kernel (ns; 0: not that kernel), split count and k per split, 16-byte
+// legality, second source / second output, column sums, grid.  A member product of a grouped launch adds its workgroup range.
+// Diagnostic only (tests/test_gemm_dispatch_gpu.py reads the lines); looked up per launch on the host, like GGAN_TRACE_CONV.
+static bool trace_gemm_on() { return getenv("GGAN_TRACE_GEMM") != nullptr; }
+static void trace_gemm(const char* name, int waves, int fast, int ns, int SK, int kps, int vecA, int vecA2, int vecB, bool a2, bool c2,
+                       bool colsum, int gx, int gy, int gz, int wg0 = -1, int wg1 = -1) {
+    fprintf(stderr, "[ggan] gemm %s waves=%d fast=%d ns=%d SK=%d kps=%d vecA=%d vecA2=%d vecB=%d a2=%d c2=%d colsum=%d grid=(%d,%d,%d)", name,
+            waves, fast, ns, SK, kps, vecA, vecA2, vecB, (int)a2, (int)c2, (int)colsum, gx, gy, gz);
+    if (wg0 >= 0) fprintf(stderr, " wgs=[%d,%d)", wg0, wg1);
+    fputc('\n', stderr);
+}
+static void trace_gemm_plan(const char* name, const GemmPlan& G, int waves, int wg0 = -1, int wg1 = -1) {
+    const GemmParams& P = G.P;
+    trace_gemm(name, waves, P.fast, 0, P.SK, P.kps, P.vecA, P.A2 ? P.vecA : 0, P.vecB, P.A2 != nullptr, P.C2 != nullptr, P.colsum != nullptr,
+               G.gx, G.gy, P.SK, wg0, wg1);
+}
+static void trace_gemm_tail(const char* name, int wg0, int wg1) { fprintf(stderr, "[ggan] gemm tail %s wgs=[%d,%d)\n", name, wg0, wg1); }
+
 static int gemm_plan(GemmPlan& G, int mode, int ta, int tb, int M, int N, int K, const float* A, const float* B, const float* bias,
                      float* C, float* colsum, int act, float alpha, void* ws, size_t ws_bytes, const float* a_ref = nullptr,
                      const float* b_ref = nullptr, int ref_act = 0, float ref_alpha = 0.f, const float* A2 = nullptr,
@@ -848,6 +867,7 @@ static int gemm_launch_planned(const GemmPlan& G, int ta, int tb, hipStream_t s)
     const bool w8 = P.fast != 0 && P.kps >= 2 * KSTEP;
 #define GGAN_GEMM_CASE(TA_, TB_, MK_, NAME_)                                                                                      \
     do {                                                                                                                           \
+        if (trace_gemm_on()) trace_gemm_plan(w8 ? "gemm_kernel8" NAME_ : "gemm_kernel" NAME_, G, w8 ? 8 : 4);                      \
         if (w8 && P.fast == 1) { GGAN_LAUNCH("gemm_kernel8" NAME_, fl, 0, (gemm_kernel8<TA_, TB_, MK_, 1>), grid, dim3(512), 0, s, P); }   \
         else if (w8) { GGAN_LAUNCH("gemm_kernel8" NAME_, fl, 0, (gemm_kernel8<TA_, TB_, MK_, 2>), grid, dim3(512), 0, s, P); }            \
         else if (P.fast == 1) { GGAN_LAUNCH("gemm_kernel" NAME_, fl, 0, (gemm_kernel<TA_, TB_, MK_, 1>), grid, block, 0, s, P); }              \
@@ -872,6 +892,7 @@ static int gemm_launch(int ta, int tb, int M, int N, int K, const float* A, cons
                        const float* a_ref = nullptr, const float* b_ref = nullptr, int ref_act = 0, float ref_alpha = 0.f,
                        const float* A2 = nullptr, int a_split = 0, float* C2 = nullptr, int c_split = 0) {
     if (N == 1 && !ta && !tb && !colsum && !a_ref && !b_ref) {
+        if (trace_gemm_on()) trace_gemm("gemv_rows_k", 4, -1, 0, 1, K, 0, 0, 0, false, false, false, cdiv(M, 4), 1, 1);
         GGAN_LAUNCH("gemv_rows_k", 2.0 * M * K, 0, gemv_rows_k, dim3(cdiv(M, 4)), dim3(256), 0, s, A, B, bias, C, M, K, act, alpha);
         return 0;
     }
@@ -901,6 +922,9 @@ static int gemm_launch(int ta, int tb, int M, int N, int K, const float* A, cons
         const double fl = 2.0 * M * N * (double)K;
 #define GGAN_SKINNY_NS(TB_, MK_, NAME_)                                                                                              \
         do {                                                                                                                         \
+            if (trace_gemm_on())                                                                                                     \
+                trace_gemm("gemm_skinny_k" NAME_, 8, -1, ns, 1, K, P.vecA, P.vecA2, P.vecB, A2 != nullptr, C2 != nullptr, false, grid.x,  \
+                           grid.y, 1);                                                                                               \
             if (ns == 1) { GGAN_LAUNCH("gemm_skinny_k" NAME_, fl, 0, (gemm_skinny_k<TB_, MK_, 1>), grid, dim3(512), 0, s, P); }      \
             else if (ns == 2) { GGAN_LAUNCH("gemm_skinny_k" NAME_, fl, 0, (gemm_skinny_k<TB_, MK_, 2>), grid, dim3(512), 0, s, P); } \
             else if (ns == 4) { GGAN_LAUNCH("gemm_skinny_k" NAME_, fl, 0, (gemm_skinny_k<TB_, MK_, 4>), grid, dim3(512), 0, s, P); } \
@@ -944,6 +968,7 @@ int ggan_critic_head_fwd(int M, int K1, int K2, int H, const float* a1, const fl
     rc = gemm_launch_planned(G, 0, 0, s);
     if (rc) return rc;
     const float* part = G.P.SK > 1 ? (const float*)G.ws : h;          // (SK == 1: the product already sits in h; summed "slab" of one)
+    if (trace_gemm_on()) trace_gemm("head_out_fwd_k", 4, -1, 0, G.P.SK, G.P.kps, 0, 0, 0, K2 != 0, false, false, cdiv(M, 2), 1, 1);
     GGAN_LAUNCH("head_out_fwd_k", 2.0 * M * H, 4.0 * M * H * (G.P.SK + 1), head_out_fwd_k, dim3(cdiv(M, 2)), dim3(256), 0, s, part,
                 G.P.SK, G.P.slab_stride, b, w_out, b_out, alpha, h, logits, M, H);
     return 0;
@@ -985,6 +1010,7 @@ int ggan_critic_head_fwd_bce(int M, int K1, int K2, int H, const float* a1, cons
     rc = gemm_launch_planned(G, 0, 0, s);
     if (rc) return rc;
     const float* part = G.P.SK > 1 ? (const float*)G.ws : h;
+    if (trace_gemm_on()) trace_gemm("head_out_fwd_bce_k", 4, -1, 0, G.P.SK, G.P.kps, 0, 0, 0, K2 != 0, false, false, cdiv(M, 2), 1, 1);
     GGAN_LAUNCH("head_out_fwd_bce_k", 5.0 * M * H, 4.0 * M * H * (G.P.SK + 2), head_out_fwd_bce_k, dim3(cdiv(M, 2)), dim3(256), 0, s, part,
                 G.P.SK, G.P.slab_stride, b, w_out, b_out, alpha, h, logits, M, H, T, g, gh);
     return 0;
@@ -1039,6 +1065,11 @@ static int critic_head_bwd_impl(int M, int K1, int K2, int H, const float* g, co
             GG.tail.first = nwg;
             nwg += 1 + cdiv(H, 16);
         }
+        if (trace_gemm_on()) {
+            trace_gemm_plan("gemm_group_kernel<8>", Ga, 8, GG.first[0], GG.first[1]);
+            trace_gemm_plan("gemm_group_kernel<8>", Gw, 8, GG.first[1], GG.first[2]);
+            if (tail) trace_gemm_tail("gemm_group_kernel<8>", GG.first[2], nwg);
+        }
         GGAN_LAUNCH("gemm_group_kernel<8>", 4.0 * M * K * (double)H, 0, gemm_group_kernel<8>, dim3(nwg), dim3(512), 0, s, GG);
         return 0;
     }
@@ -1052,6 +1083,10 @@ static int critic_head_bwd_impl(int M, int K1, int K2, int H, const float* g, co
         GG.has_tail = 1;
         GG.tail = *tail;
         GG.tail.first = GG.first[1];
+        if (trace_gemm_on()) {
+            trace_gemm_plan("gemm_group_kernel<8>", Ga, 8, GG.first[0], GG.first[1]);
+            trace_gemm_tail("gemm_group_kernel<8>", GG.first[1], GG.first[1] + 1 + cdiv(H, 16));
+        }
         GGAN_LAUNCH("gemm_group_kernel<8>", 2.0 * M * K * (double)H, 0, gemm_group_kernel<8>, dim3(GG.first[1] + 1 + cdiv(H, 16)), dim3(512), 0,
                     s, GG);
         return 0;
@@ -1059,6 +1094,7 @@ static int critic_head_bwd_impl(int M, int K1, int K2, int H, const float* g, co
     if (tail) {
         HeadTail T = *tail;
         T.first = 0;
+        if (trace_gemm_on()) trace_gemm_tail("head_tail_k", 0, 1 + cdiv(H, 16));
         GGAN_LAUNCH("head_tail_k", 3.0 * M * H, 4.0 * M * H, head_tail_k, dim3(1 + cdiv(H, 16)), dim3(256), 0, s, T);
     }
     if (nw) { int rc = gemm_launch_planned(Gw, 1, 0, s); if (rc) return rc; }
