@@ -86,6 +86,8 @@ SIGNATURES = {
     'ggan_knn_vote': (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
     'ggan_parzen_lse_workspace': (_Z, [_I, _I, _I]),
     'ggan_parzen_lse': (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _P, _Z, _P]),
+    'ggan_ssim_pairs_workspace': (_Z, [_I, _I, _I, _I]),
+    'ggan_ssim_pairs': (_I, [_P, _P, _I, _I, _I, _I, _F, _F, _F, _F, _P, _P, _P, _Z, _P]),
     'ggan_noise_fill': (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _P]),
     'ggan_gmm_latent_fwd': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _P]),
     'ggan_gmm_latent_bwd': (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P]),

@@ -24,6 +24,10 @@
                      images under a kernel density fitted to as many generated ones (Breuleux et al. 2011; Goodfellow et al. 2014),
                      pixels in [0, 1], the bandwidth chosen on the leading validation rows from PARZEN_SIGMAS -- ggan_parzen_lse, one
                      log-sum-exp sweep for all rows and bandwidths.  The one number with a published protocol (README for its limits).
+  rec_scores         `dev rec mse x` / `dev rec psnr x` / `dev rec ssim x` / `dev rec ssim se x`: how well Generator(Extractor(x)) gives the dev
+                     images back -- per-image mean squared error, PSNR and SSIM (Wang et al. 2004) in the unit pixel range, ggan_ssim_pairs.
+                     The one pass that measures the round trip x -> q(z | x) -> Generator(z), and the one all ten scripts have:
+                     SequenceEvaluator.rec_scores scores the state-space scripts' reconstructed sequences frame by frame.
 
 The passes are safe in the middle of training: they run under torch.no_grad() on the current stream only (no second stream, no
 collective), with a feed dict and a noise generator state of their own -- the Trainer's static feed buffers, ring slots and noise state
@@ -43,8 +47,9 @@ run by SequenceEvaluator on a models_ssgan.StateSpaceGAN under the same rules:
 Each is written as a .png sheet (one sequence per row) and a looping .gif; the bytes of both come from one ggan_video_sheet_u8 launch.
 
 `python -m graphical_gan_amd.evaluate CKPT --script gmgan_inference_mnist [--data-dir DIR]` scores a saved checkpoint
-(`--out-dir DIR --manifold` also writes the latent-space pictures of the two MNIST scripts, `--mmd` adds the two MMD^2 rows, `--prdc` the eight precision / recall / density / coverage rows, `--knn` the two k-NN accuracy rows, `--parzen` the three Parzen-window rows);
-`... CKPT --script ssgan_inference_moving_mnist|ssgan_inference_chairs [--data-dir DIR] --out-dir DIR` writes the four pairs of files."""
+(`--out-dir DIR --manifold` also writes the latent-space pictures of the two MNIST scripts, `--mmd` adds the two MMD^2 rows, `--prdc` the eight precision / recall / density / coverage rows, `--knn` the two k-NN accuracy rows, `--parzen` the three Parzen-window rows, `--rec` the four reconstruction rows);
+`... CKPT --script ssgan_inference_moving_mnist|ssgan_inference_chairs [--data-dir DIR] --out-dir DIR` writes the four pairs of files;
+`--rec` prints the four reconstruction rows of the sequences' frames, and alone needs no --out-dir."""
 import argparse
 import contextlib
 import os
@@ -64,6 +69,7 @@ KNN_K = 5                 # neighbours that vote in it (settings: KNN_K; at most
 PARZEN_MAX_ROWS = 10000   # rows per set of the parzen_scores pass (settings: PARZEN_MAX_ROWS): the protocol's 10000 generated samples
 PARZEN_VALID_ROWS = 1000  # leading dev rows its bandwidth is chosen on (settings: PARZEN_VALID_ROWS)
 PARZEN_SIGMAS = np.logspace(-1, 0, 10)    # the protocol's bandwidth grid, in [0, 1] pixel units (settings: PARZEN_SIGMAS; at most functional.PARZEN_MAX_SIGMAS)
+REC_MAX_ROWS = 10000      # rows (images; frames of the state-space scripts) of the rec_scores passes (settings: REC_MAX_ROWS)
 EVAL_SEED = 7919          # offset of the evaluator's noise seeds from the settings seed (the Trainer's stream of draws is not touched)
 
 # the reference's output file names, per script: (samples, reconstructions), formatted with frame= and mode=
@@ -120,6 +126,17 @@ def _split(b):
     if isinstance(b, (tuple, list)):
         return b[0], (b[1] if len(b) > 1 else None)
     return b, None
+
+
+REC_KEYS = ('dev rec mse x', 'dev rec psnr x', 'dev rec ssim x', 'dev rec ssim se x')
+
+
+def _rec_stats(mse, ssim):
+    """per-image device rows -> (float64 [4] device tensor: mean mse, mean of the per-image PSNR, mean SSIM, its standard error -- the
+    population std / sqrt(count), as the Parzen pass --, the per-image PSNR rows)"""
+    psnr, s = F.psnr_from_mse(mse), ssim.double()
+    count = torch.full((), float(s.shape[0]), dtype=torch.float64, device=s.device)
+    return torch.stack([mse.double().mean(), psnr.mean(), s.mean(), s.std(unbiased=False) / torch.sqrt(count)]), psnr
 
 
 class _Passes(object):
@@ -276,12 +293,14 @@ class Evaluator(_Passes):
                     out['qk'][rows].copy_(torch.argmax(q_k, dim=1))
         return out
 
-    def _score_sets(self, batches, rows, generated=True, labels=False):
+    def _score_sets(self, batches, rows, generated=True, labels=False, rec=False):
         """the four row sets the set-level scores compare, on the device, over the full minibatches and at most `rows` rows per set:
         z = q_z (the sampled code of the aggregated-posterior MODEs, as latent_sets), pz = as many fresh prior draws (through HyperGenerator
         with a mixture prior), x = real_x as the nets see it, gx = Generator(pz) minibatch by minibatch.  generated=False: z and x alone
         (the noise is drawn all the same: one stream of draws whichever sets are built).  labels: also y = the int32 labels of the same
-        _stage call, row for row (labelled minibatches only).  Called inside a pass's guard."""
+        _stage call, row for row (labelled minibatches only).  rec: also rx = Generator(q_z) minibatch by minibatch -- the full minibatches
+        reconstructions() runs, the Generator's BatchNorm on batch statistics; it draws no noise and moves no other set.  Called inside a
+        pass's guard."""
         c = self.cfg
         X, Y = self._stage(batches, want_labels=labels)
         B = c.B
@@ -292,14 +311,19 @@ class Evaluator(_Passes):
             sets = dict(z=sets['z'], pz=new(c.dim_latent), x=sets['x'], gx=new(c.output_dim))
         if labels:
             sets['y'] = Y[:n * B]
+        if rec:
+            sets['rx'] = new(c.output_dim)
         self.kept = []
         for i in range(n):
             rows = slice(i * B, (i + 1) * B)
             self._load(X[i])
             real_x = self.model.real_x(self.feed)
             q = self.model.Extractor(real_x, eps=self.feed['q_eps']) if c.agg else self.model.Extractor(real_x)
-            sets['z'][rows].copy_(q[0] if isinstance(q, tuple) else q)
+            q_z = q[0] if isinstance(q, tuple) else q
+            sets['z'][rows].copy_(q_z)
             sets['x'][rows].copy_(real_x.float())
+            if rec:
+                sets['rx'][rows].copy_(self.model.Generator(q_z).float())
             if not generated:
                 continue
             p_z = self.model.HyperGenerator(self.feed['k_onehot'], self.feed['p_z_noise']) if c.K else self.feed['p_z_noise']
@@ -307,17 +331,20 @@ class Evaluator(_Passes):
             sets['gx'][rows].copy_(self.model.Generator(sets['pz'][rows]).float())
         return sets
 
-    def set_scores(self, batches, mmd=False, prdc=False, knn=False, return_sets=False, parzen=False):
+    def set_scores(self, batches, mmd=False, prdc=False, knn=False, return_sets=False, parzen=False, rec=False):
         """the set-level scores asked for, from ONE build of the sets (_score_sets: one stream of noise draws, whichever scores are on) and
         ONE host synchronisation: mmd -> the two values of mmd_scores, prdc -> the eight of prdc_scores, knn -> the two of knn_scores,
-        parzen -> the three of parzen_scores, in that order.  With several on, each scores the leading rows its own row cap allows.  knn
+        parzen -> the three of parzen_scores, rec -> the four of rec_scores, in that order.  With several on, each scores the leading rows its own row cap allows.  knn
         needs labelled minibatches (the labels come from the sets' own _stage call); with knn alone the generated sets are not built.
         parzen needs at least two full minibatches within its row cap (one to choose the bandwidth on, one to score) and at most
-        functional.PARZEN_MAX_SIGMAS bandwidths.  return_sets: (values, {z, pz, x, gx}), with knn also y, with knn alone {z, x, y}."""
+        functional.PARZEN_MAX_SIGMAS bandwidths.  rec adds the set rx = Generator(q_z) and compares it with x image by image (its per-image
+        rows stay in self.rec_rows); with knn and rec alone the generated sets are not built.  return_sets: (values, {z, pz, x, gx}), with
+        knn also y, with rec also rx, with knn alone {z, x, y}."""
         B = self.cfg.B
         cap = {'mmd': int(self.S.get('MMD_MAX_ROWS', MMD_MAX_ROWS)), 'prdc': int(self.S.get('PRDC_MAX_ROWS', PRDC_MAX_ROWS)),
-               'knn': int(self.S.get('KNN_MAX_ROWS', KNN_MAX_ROWS)), 'parzen': int(self.S.get('PARZEN_MAX_ROWS', PARZEN_MAX_ROWS))}
-        on = [name for name, flag in (('mmd', mmd), ('prdc', prdc), ('knn', knn), ('parzen', parzen)) if flag]
+               'knn': int(self.S.get('KNN_MAX_ROWS', KNN_MAX_ROWS)), 'parzen': int(self.S.get('PARZEN_MAX_ROWS', PARZEN_MAX_ROWS)),
+               'rec': int(self.S.get('REC_MAX_ROWS', REC_MAX_ROWS))}
+        on = [name for name, flag in (('mmd', mmd), ('prdc', prdc), ('knn', knn), ('parzen', parzen), ('rec', rec)) if flag]
         if not on:
             raise ValueError('set_scores: no score was asked for')
         k = int(self.S.get('PRDC_K', PRDC_K))
@@ -333,7 +360,7 @@ class Evaluator(_Passes):
                 raise ValueError('the Parzen pass needs at least 2 full minibatches of %d rows within PARZEN_MAX_ROWS = %d: one to '
                                  'choose the bandwidth on, one to score' % (B, cap['parzen']))
         with self._guard():
-            sets = self._score_sets(batches, max(cap[name] for name in on), generated=bool(mmd or prdc or parzen), labels=bool(knn))
+            sets = self._score_sets(batches, max(cap[name] for name in on), generated=bool(mmd or prdc or parzen), labels=bool(knn), rec=bool(rec))
             rows = {name: min(sets['z'].shape[0], max(1, cap[name] // B) * B) for name in on}
             names, vals = [], []
             if mmd:
@@ -357,6 +384,9 @@ class Evaluator(_Passes):
             if parzen:
                 names += ['dev parzen ll x', 'dev parzen se x', 'dev parzen sigma x']
                 vals.append(self._parzen(sets['x'][:rows['parzen']], sets['gx'][:rows['parzen']], sigmas))
+            if rec:
+                names += list(REC_KEYS)
+                vals.append(self._rec(sets['x'][:rows['rec']], sets['rx'][:rows['rec']]))
             vals = torch.cat(vals).cpu().numpy()
         res = {name: float(v) for name, v in zip(names, vals)}
         return (res, sets) if return_sets else res
@@ -409,6 +439,28 @@ class Evaluator(_Passes):
         the protocol's script); sigma is the chosen bandwidth.  functional.parzen_ll, ONE host synchronisation for the three.  Fewer than
         two full minibatches raise ValueError.  There is no z twin: in code space the prior's density is known in closed form.  return_sets: (values, {z, pz, x, gx})."""
         return self.set_scores(batches, parzen=True, return_sets=return_sets)
+
+    def _rec(self, x, rx):
+        """the four reconstruction values of the rows of rx against those of x -> float64 [4] device tensor.  ONE ssim_pairs call over all
+        rows, both sets in the range the nets see (the unit-scale map is in the kernel's formula); the per-image rows stay on the device in
+        self.rec_rows = {mse, psnr, ssim}."""
+        c = self.cfg
+        unit = (1.0, 0.0) if c.out_act == 'sigmoid' else (0.5, 0.5)         # (as _to_unit)
+        mse, ssim = F.ssim_pairs(rx, x, (c.C, c.S, c.S), unit)
+        vals, psnr = _rec_stats(mse, ssim)
+        self.rec_rows = dict(mse=mse, psnr=psnr, ssim=ssim)
+        return vals
+
+    def rec_scores(self, batches, return_rows=False):
+        """{'dev rec mse x', 'dev rec psnr x', 'dev rec ssim x', 'dev rec ssim se x'}: how well the round trip Generator(Extractor(x)) gives
+        the dev images back, image by image and with pixels in [0, 1] -- the mean squared error per image, the mean of the per-image PSNR in
+        dB (-10 log10 max(mse, 1e-10)), the mean of the per-image SSIM (Wang et al. 2004: 11x11 Gaussian window, sigma 1.5, data range 1) and
+        that mean's standard error -- over the full dev minibatches, at most REC_MAX_ROWS rows and at least one minibatch.  The
+        reconstructions are those reconstructions() draws: Generator(q_z) a full minibatch at a time (with a stochastic Extractor the code is
+        one sample).  functional.ssim_pairs, the statistics in float64 on the device, ONE host synchronisation for the four.
+        return_rows: (values, {mse, psnr, ssim}: the per-image device rows)."""
+        res = self.set_scores(batches, rec=True)
+        return (res, self.rec_rows) if return_rows else res
 
     def manifold(self, batches, out_dir, frame):
         """embeds the point sets of latent_sets with functional.tsne and writes the scatters under the reference's file names; returns
@@ -610,6 +662,41 @@ class SequenceEvaluator(_Passes):
             _, _, q_z_l = self._extract(data)
             return self.model.Generator(self.dis_g, q_z_l, self.dis_y)
 
+    def rec_scores(self, batches, return_rows=False, per_frame=False):
+        """{'dev rec mse x', 'dev rec psnr x', 'dev rec ssim x', 'dev rec ssim se x'} of reconstructions(batch) against the data over the full
+        dev minibatches, FRAME by frame (n = B * LEN rows per minibatch; at most REC_MAX_ROWS frames and at least one minibatch): the
+        generated frames in the tanh range, the data in the loader's units, both mapped to [0, 1] inside the kernel's formula -- the
+        per-frame figures the video-prediction literature reports.  functional.ssim_pairs per minibatch, the statistics in float64 on
+        the device, ONE host synchronisation.  per_frame: the values also hold mse_t, psnr_t, ssim_t, the [LEN] means by frame index
+        (numpy).  return_rows: (values, {mse, psnr, ssim}: the per-frame device rows, sequence-major).  The evaluator's own feed and
+        noise state; the Trainer is left untouched."""
+        c = self.cfg
+        full = [b for b in batches if _split(b)[0].shape[0] == c.B]
+        if not full:
+            raise ValueError('no full minibatch of %d sequences to evaluate on' % c.B)
+        full = full[:max(1, int(self.S.get('REC_MAX_ROWS', REC_MAX_ROWS)) // (c.B * c.LEN))]
+        t0 = time.time()
+        mse, ssim = [], []
+        for b in full:
+            data = self._batch(b)
+            rec = self.reconstructions(data)
+            with self._guard():
+                m, s = F.ssim_pairs(rec.float(), data[0], (c.C, c.S, c.S), (0.5, 0.5), (1.0 / c.x_div, 0.0))
+            mse.append(m)
+            ssim.append(s)
+        with self._guard():
+            mse, ssim = torch.cat(mse), torch.cat(ssim)
+            vals, psnr = _rec_stats(mse, ssim)
+            if per_frame:
+                vals = torch.cat([vals] + [v.double().view(-1, c.LEN).mean(dim=0) for v in (mse, psnr, ssim)])
+            vals = vals.cpu().numpy()
+        self.last_seconds = time.time() - t0
+        res = {name: float(v) for name, v in zip(REC_KEYS, vals[:4])}
+        if per_frame:
+            for i, name in enumerate(('mse_t', 'psnr_t', 'ssim_t')):
+                res[name] = vals[4 + i * c.LEN:4 + (i + 1) * c.LEN].copy()
+        return (res, dict(mse=mse, psnr=psnr, ssim=ssim)) if return_rows else res
+
     # ---- files ---------------------------------------------------------------------------------------------------------------------
     def sheets(self, train_data=None):
         """{name: (sheet bytes, index planes)} on the device for the passes' files: one ggan_video_sheet_u8 launch each"""
@@ -666,6 +753,7 @@ def main(argv=None):
     ap.add_argument('--prdc', action='store_true', help='also score the dev set by k-NN-ball precision / recall / density / coverage of codes and of images (eight dev rows; image scripts)')
     ap.add_argument('--knn', action='store_true', help='also score the labelled dev set by the leave-one-out k-NN accuracy of codes and of images (dev knn accuracy z / x; image scripts)')
     ap.add_argument('--parzen', action='store_true', help='also score the dev set by the Gaussian Parzen-window log-likelihood of held-out images under generated ones (dev parzen ll / se / sigma x; image scripts)')
+    ap.add_argument('--rec', action='store_true', help='also score how well Generator(Extractor(x)) gives the dev set back: per-image (state-space scripts: per-frame) mse / PSNR / SSIM in the unit pixel range (dev rec mse / psnr / ssim / ssim se x; every script)')
     ap.add_argument('--set', action='append', default=[], metavar='KEY=VALUE', help='override an UPPERCASE setting (int / float / str)')
     a = ap.parse_args(argv)
     over = {}
@@ -699,28 +787,34 @@ def main(argv=None):
     cfg, model = run.config(S), None
     if S['DATASET'] in run.SEQUENCE_DATASETS:
         from .models_ssgan import StateSpaceGAN
-        if not a.out_dir:
+        if not a.out_dir and not a.rec:
             ap.error('--out-dir is required for %s: its passes are files' % a.script)
         model = StateSpaceGAN(cfg)
     tr = Trainer(cfg, device=lib.get_device(), graph=False, model=model)
     checkpoint.restore(a.ckpt, tr)
-    res = evaluate_once(tr, S, out_dir=a.out_dir, manifold=a.manifold, mmd=a.mmd, prdc=a.prdc, knn=a.knn, parzen=a.parzen)
+    res = evaluate_once(tr, S, out_dir=a.out_dir, manifold=a.manifold, mmd=a.mmd, prdc=a.prdc, knn=a.knn, parzen=a.parzen, rec=a.rec)
     for k in sorted(res):
         print('%s\t%s' % (k, res[k]))
     return res
 
 
-def evaluate_once(tr, S, out_dir=None, frame='eval', manifold=False, mmd=False, prdc=False, knn=False, parzen=False):
+def evaluate_once(tr, S, out_dir=None, frame='eval', manifold=False, mmd=False, prdc=False, knn=False, parzen=False, rec=False):
     """every pass the script's data allow, once -> {name: value}; manifold: the latent-space pictures too (labelled dev data only);
     mmd: the two dev-set MMD^2 scores too; prdc: the eight precision / recall / density / coverage scores too; knn: the two k-NN
-    accuracies too (labelled dev data only); parzen: the three Parzen-window values too -- one build of the sets for the four"""
+    accuracies too (labelled dev data only); parzen: the three Parzen-window values too; rec: the four reconstruction values too -- one build of the sets for the five.  The
+    state-space scripts: the video files (with out_dir) and, with rec, the four reconstruction values of the dev sequences' frames"""
     from . import run
     if S['DATASET'] in run.SEQUENCE_DATASETS:       # the video passes: files only (train_data: the first dev minibatch)
         ev = SequenceEvaluator(tr, S)
         dev, _ = run.eval_sets(S, tr.model, tr.device)
-        ev.set_fixed_data(dev[0])
-        os.makedirs(out_dir, exist_ok=True)
-        return {'files': ' '.join(os.path.basename(p) for p in ev.save_videos(out_dir, frame, train_data=dev[0]))}
+        res = {}
+        if rec:
+            res.update(ev.rec_scores(run.rec_sequences(S, tr.model, tr.device)))
+        if out_dir:
+            ev.set_fixed_data(dev[0])
+            os.makedirs(out_dir, exist_ok=True)
+            res['files'] = ' '.join(os.path.basename(p) for p in ev.save_videos(out_dir, frame, train_data=dev[0]))
+        return res
     ev = Evaluator(tr, S)
     dev, test = run.eval_sets(S, tr.model, tr.device)
     res = dict(ev.dev_costs(dev))
@@ -729,8 +823,8 @@ def evaluate_once(tr, S, out_dir=None, frame='eval', manifold=False, mmd=False, 
     if knn and not run.labelled(dev):
         print('[evaluate] dev knn accuracy skipped: no labelled dev set')
         knn = False
-    if mmd or prdc or knn or parzen:
-        res.update(ev.set_scores(dev, mmd=mmd, prdc=prdc, knn=knn, parzen=parzen))
+    if mmd or prdc or knn or parzen or rec:
+        res.update(ev.set_scores(dev, mmd=mmd, prdc=prdc, knn=knn, parzen=parzen, rec=rec))
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
         ev.set_fixed_data(dev[0])

@@ -524,6 +524,59 @@ def parzen_ll(q, s, sigmas, scale=1.0):
     return lse.double() - const
 
 
+SSIM_MAX_ROWS, SSIM_MAX_C, SSIM_MIN_SIDE, SSIM_MAX_SIDE = 131072, 4, 11, 64        # include/ggan.h: the ranges ggan_ssim_pairs accepts
+
+
+def _unit_map(name, m):
+    """a unit-scale map as two finite floats (scale, shift) (ValueError otherwise)"""
+    try:
+        scale, shift = (float(v) for v in m)
+    except (TypeError, ValueError):
+        raise ValueError('%s: a map is a (scale, shift) pair, got %r' % (name, m))
+    if not (math.isfinite(scale) and math.isfinite(shift)):
+        raise ValueError('%s: a map must be finite, got %r' % (name, m))
+    return scale, shift
+
+
+def ssim_pairs(a, b, shape, map_a=(1., 0.), map_b=None):
+    """per-image reconstruction fidelity of rows a[i] against b[i] (ggan_ssim_pairs): a, b [n, C*H*W] fp32 device rows of channel-major
+    planes (or [B, LEN, C*H*W]: n = B*LEN frames), shape = (C, H, W), C in 1..4 and 11 <= H, W <= 64.  The pixel of an input in unit scale
+    is scale * x + shift with (scale, shift) = map_a for a and map_b (default: map_a) for b -- (0.5, 0.5) for the tanh range, (1, 0) for the
+    sigmoid range, (1/255, 0) for data in 0..255.  -> (mse [n], ssim [n]) float32 device tensors: the mean squared error, and the mean
+    structural similarity under the 11x11 Gaussian window of sigma 1.5 (Wang et al. 2004; data range 1).  a is b is allowed.  Forward only."""
+    name = 'ssim_pairs'
+    try:
+        c, h, w = (int(v) for v in shape)
+    except (TypeError, ValueError):
+        raise ValueError('%s: shape = (C, H, W) expected, got %r' % (name, shape))
+    if not (1 <= c <= SSIM_MAX_C and SSIM_MIN_SIDE <= h <= SSIM_MAX_SIDE and SSIM_MIN_SIDE <= w <= SSIM_MAX_SIDE):
+        raise ValueError('%s: 1 <= C <= %d and %d <= H, W <= %d expected, got %r' % (name, SSIM_MAX_C, SSIM_MIN_SIDE, SSIM_MAX_SIDE, (c, h, w)))
+    if a.shape != b.shape or a.dim() < 2 or a.shape[-1] != c * h * w:
+        raise ValueError('%s: two sets of rows [n, %d] expected, got %s, %s' % (name, c * h * w, tuple(a.shape), tuple(b.shape)))
+    n = a.numel() // (c * h * w)
+    if not 1 <= n <= SSIM_MAX_ROWS:
+        raise ValueError('%s: 1 <= n <= %d images expected, got %d' % (name, SSIM_MAX_ROWS, n))
+    (sa, ha), (sb, hb) = _unit_map(name, map_a), _unit_map(name, map_a if map_b is None else map_b)
+    if torch.is_grad_enabled() and (a.requires_grad or b.requires_grad):
+        raise _lib.GganError('%s has no backward: detach the inputs' % name)
+    same = a is b
+    a = _c(a)
+    b = a if same else _c(b)
+    nbytes = int(_L().ggan_ssim_pairs_workspace(n, c, h, w))
+    ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=a.device)
+    mse = torch.empty((n,), dtype=torch.float32, device=a.device)
+    ssim = torch.empty((n,), dtype=torch.float32, device=a.device)
+    check(_L().ggan_ssim_pairs(_p(a), _p(b), n, c, h, w, sa, ha, sb, hb, _p(mse), _p(ssim), _p(ws), nbytes, _stream()), 'ggan_ssim_pairs')
+    return mse, ssim
+
+
+def psnr_from_mse(mse):
+    """-10 log10(max(mse, 1e-10)) per element of a tensor of unit-range mean squared errors, in dB: a perfect image scores 100 dB and not
+    inf, which would poison a mean -> float64 tensor on the same device (plain torch arithmetic on n numbers: the caller keeps the one host
+    synchronisation)"""
+    return -10.0 * torch.log10(torch.clamp(mse.double(), min=1e-10))
+
+
 class Reparam(Function):
     """(z, std) = (mean + eps * exp(log_std), exp(log_std)): the stochastic encoder head (gan_inference_cifar10.py:173-188)"""
 

@@ -2,6 +2,7 @@
 reference's gan_inference_* / gmgan_inference_* / ssgan_inference_* scripts; their train loop is
 gmgan_inference_cifar10.py:470-549: alternate one generator step and CRITIC_ITERS critic steps on fresh minibatches, log the
 costs through tflib.plot, dump sample grids and a checkpoint every so often)."""
+import itertools
 import os
 import time
 
@@ -194,6 +195,47 @@ def parzen_due(S, it):
     """does the pass fire after iteration `it`: it % N == N - 1, the cadence of the other passes"""
     n = int(S.get('PARZEN_EVERY') or 0)
     return bool(n and it % n == n - 1)
+
+
+# the reconstruction fidelity of the dev set (evaluate.Evaluator.rec_scores, evaluate.SequenceEvaluator.rec_scores): as the four passes
+# above, off unless asked for, a switch and a cadence of their own -- and the one set-level pass the two state-space scripts have too
+def rec_settings(script):
+    """{'REC_EVERY': N} for the ten scripts when $GGAN_REC_EVERY = N is set, {} otherwise"""
+    name = os.path.splitext(os.path.basename(script))[0]
+    every = os.environ.get('GGAN_REC_EVERY')
+    if (name not in _IMAGE_SCRIPTS and name not in _SEQUENCE_SCRIPTS) or not every:
+        return {}
+    return {'REC_EVERY': int(every)}
+
+
+def rec_due(S, it):
+    """does the pass fire after iteration `it`: it % N == N - 1, the cadence of the other passes"""
+    n = int(S.get('REC_EVERY') or 0)
+    return bool(n and it % n == n - 1)
+
+
+def rec_sequences(S, model, device):
+    """the dev minibatches the state-space scripts' reconstruction pass scores: the leading ones of the loader's dev split, as many as
+    REC_MAX_ROWS frames take (at least one) -- eval_sets keeps the first alone, which is all the video passes use; without the dataset,
+    eval_sets' synthetic ones"""
+    from .evaluate import REC_MAX_ROWS
+    ds, B = S['DATASET'], S['BATCH_SIZE']
+    n = max(1, int(S.get('REC_MAX_ROWS', REC_MAX_ROWS)) // (B * S['LEN']))
+    state = np.random.get_state()
+    try:
+        if S.get('SYNTHETIC') == 'force':
+            raise FileNotFoundError('synthetic data requested')
+        if ds == 'moving_mnist':
+            _, dev = lib.simple_moving_mnist.load_video(S['LEN'], B)
+        elif ds == 'chairs':
+            _, dev = lib.chairs.load(S['LEN'], B, 64, S.get('DATA_DIR', ''))
+        else:
+            raise ValueError('%r is no sequence dataset' % ds)
+        return list(itertools.islice(dev(), n))
+    except FileNotFoundError:
+        return eval_sets(S, model, device)[0][:n]
+    finally:
+        np.random.set_state(state)
 
 
 def labelled(batches):
@@ -398,15 +440,20 @@ def train(S, cfg, model=None, out_dir=None):
         else:
             m_eval = evaluator if evaluator is not None else Evaluator(tr, S)
     # the evaluator of the set-level scores: dev mmd (MMD_EVERY), dev precision / ... / coverage (PRDC_EVERY), dev knn accuracy (KNN_EVERY),
-    # dev parzen ll / se / sigma (PARZEN_EVERY)
-    mmd_eval, knn_on = None, False
-    if (S.get('MMD_EVERY') or S.get('PRDC_EVERY') or S.get('KNN_EVERY') or S.get('PARZEN_EVERY')) and (tr.world == 1 or torch.distributed.get_rank() == 0):
-        from .evaluate import Evaluator
+    # dev parzen ll / se / sigma (PARZEN_EVERY), dev rec mse / psnr / ssim / ssim se (REC_EVERY: the state-space scripts too, through
+    # their own evaluator and on dev minibatches of their own)
+    mmd_eval, knn_on, rec_eval = None, False, None
+    if (S.get('MMD_EVERY') or S.get('PRDC_EVERY') or S.get('KNN_EVERY') or S.get('PARZEN_EVERY') or S.get('REC_EVERY')) and (tr.world == 1 or torch.distributed.get_rank() == 0):
+        from .evaluate import Evaluator, SequenceEvaluator
         from .models_ssgan import StateSpaceGAN
+        if isinstance(tr.model, StateSpaceGAN) and S.get('REC_EVERY'):
+            rec_eval = evaluator if evaluator is not None else SequenceEvaluator(tr, S)
+            rec_dev = rec_sequences(S, tr.model, device)
         if isinstance(tr.model, StateSpaceGAN):
-            print('[run] %s skipped: the state-space models have no single code to compare'
-                  % ' and '.join(n for n, key in (('dev mmd', 'MMD_EVERY'), ('dev precision / recall / density / coverage', 'PRDC_EVERY'),
-                                                    ('dev knn accuracy', 'KNN_EVERY'), ('dev parzen ll', 'PARZEN_EVERY')) if S.get(key)))
+            if S.get('MMD_EVERY') or S.get('PRDC_EVERY') or S.get('KNN_EVERY') or S.get('PARZEN_EVERY'):
+                print('[run] %s skipped: the state-space models have no single code to compare'
+                      % ' and '.join(n for n, key in (('dev mmd', 'MMD_EVERY'), ('dev precision / recall / density / coverage', 'PRDC_EVERY'),
+                                                        ('dev knn accuracy', 'KNN_EVERY'), ('dev parzen ll', 'PARZEN_EVERY')) if S.get(key)))
         else:
             mmd_eval = evaluator if evaluator is not None else (m_eval if manifold else Evaluator(tr, S))
             mmd_dev = ev_dev if evaluator is not None else (m_dev if manifold else eval_sets(S, tr.model, device)[0])
@@ -439,8 +486,12 @@ def train(S, cfg, model=None, out_dir=None):
             lib.plot.flush(out_dir, os.path.join(out_dir, 'logfile.txt') if out_dir else None)
         if manifold_due(manifold, it, S['ITERS']):
             eval_ms += _manifold(m_eval, m_dev, it, out_dir, device)
-        if mmd_eval is not None and (mmd_due(S, it) or prdc_due(S, it) or (knn_on and knn_due(S, it)) or parzen_due(S, it)):
-            eval_ms += _set_scores(mmd_eval, mmd_dev, device, mmd_due(S, it), prdc_due(S, it), knn_on and knn_due(S, it), parzen_due(S, it))
+        if mmd_eval is not None and (mmd_due(S, it) or prdc_due(S, it) or (knn_on and knn_due(S, it)) or parzen_due(S, it) or rec_due(S, it)):
+            eval_ms += _set_scores(mmd_eval, mmd_dev, device, mmd_due(S, it), prdc_due(S, it), knn_on and knn_due(S, it), parzen_due(S, it),
+                                   rec_due(S, it))
+            lib.plot.flush(out_dir, os.path.join(out_dir, 'logfile.txt') if out_dir else None)
+        if rec_eval is not None and rec_due(S, it):
+            eval_ms += _rec_sequences(rec_eval, rec_dev, device)
             lib.plot.flush(out_dir, os.path.join(out_dir, 'logfile.txt') if out_dir else None)
         lib.plot.tick()
         if out_dir and S.get('SAVE_EVERY') and (it + 1) % S['SAVE_EVERY'] == 0:
@@ -492,13 +543,25 @@ def _manifold(ev, dev, it, out_dir, device):
     return (time.time() - t0) * 1e3
 
 
-def _set_scores(ev, dev, device, mmd, prdc, knn=False, parzen=False):
-    """the dev-set MMD^2, precision / recall / density / coverage, k-NN accuracy and Parzen-window scores that are due, from one build of the
-    sets, logged through lib.plot -> milliseconds they took"""
+def _set_scores(ev, dev, device, mmd, prdc, knn=False, parzen=False, rec=False):
+    """the dev-set MMD^2, precision / recall / density / coverage, k-NN accuracy, Parzen-window and reconstruction scores that are due, from
+    one build of the sets, logged through lib.plot -> milliseconds they took"""
     if device.type == 'cuda':
         torch.cuda.synchronize(device)
     t0 = time.time()
-    for k, v in ev.set_scores(dev, mmd=mmd, prdc=prdc, knn=knn, parzen=parzen).items():
+    for k, v in ev.set_scores(dev, mmd=mmd, prdc=prdc, knn=knn, parzen=parzen, rec=rec).items():
+        lib.plot.plot(k, v)
+    if device.type == 'cuda':
+        torch.cuda.synchronize(device)
+    return (time.time() - t0) * 1e3
+
+
+def _rec_sequences(ev, dev, device):
+    """the state-space scripts' reconstruction scores of the dev sequences' frames, logged through lib.plot -> milliseconds they took"""
+    if device.type == 'cuda':
+        torch.cuda.synchronize(device)
+    t0 = time.time()
+    for k, v in ev.rec_scores(dev).items():
         lib.plot.plot(k, v)
     if device.type == 'cuda':
         torch.cuda.synchronize(device)

@@ -480,6 +480,27 @@ size_t ggan_parzen_lse_workspace(int m, int n, int ns);
 int ggan_parzen_lse(const float* Q, const float* S, int m, int n, int d, const float* sigmas /*host*/, int ns,
                     float* lse /*device [ns, m]*/, void* ws, size_t ws_bytes, ggan_stream_t stream);
 
+/* Reconstruction fidelity of image pairs: per-image mean squared error and mean structural similarity (Wang, Bovik, Sheikh, Simoncelli
+ * 2004) of A[i] against B[i] (evaluate.Evaluator.rec_scores / SequenceEvaluator.rec_scores, functional.ssim_pairs).  A, B: row-major device
+ * fp32 [n, c*h*w], channel-major planes -- the layout of [B, OUTPUT_DIM] rows and of [B, LEN, OUTPUT_DIM] with n = B*LEN --, A == B allowed;
+ * 1 <= n <= 131072, 1 <= c <= 4, 11 <= h, w <= 64.  The pixel of input X in unit scale is u = scale_x * x + shift_x (tanh range: 0.5, 0.5;
+ * sigmoid range: 1, 0; data in 0..255: 1/255, 0): the rescaling is in the formula, the data stay as the nets see them.
+ *   mse[i]  = mean over c*h*w of (ua - ub)^2
+ *   ssim[i] = mean over the c channels and the (h-10)*(w-10) valid window positions of
+ *             ((2 mx my + C1)(2 sxy + C2)) / ((mx^2 + my^2 + C1)(sxx + syy + C2)),  C1 = 0.01^2, C2 = 0.03^2 (data range 1),
+ *             mx, my, sxx, syy, sxy the means, population variances and covariance under the separable 11x11 Gaussian window of
+ *             sigma 1.5, normalised to sum 1 (scikit-image structural_similarity(gaussian_weights=True, sigma=1.5,
+ *             use_sample_covariance=False), cropped by 5 on every side).  The second moments are taken of values CENTRED by each plane's
+ *             mean, so that E[x^2] - mx^2 does not cancel on bright flat regions.
+ * ws: ggan_ssim_pairs_workspace(n, c, h, w) bytes of 4-byte aligned device scratch (0 = arguments out of range): the per-plane sums, which a
+ * second launch combines over the c planes of an image in index order.  Sums are reduced in a fixed order, no floating-point atomics:
+ * repeated calls give the same bits, and an image's values depend neither on its neighbours nor on n.  Arguments out of range, a null
+ * pointer or a short workspace return a negative code before any device work.
+ * Forward only.  Added without a version change: no existing entry point or struct is touched. */
+size_t ggan_ssim_pairs_workspace(int n, int c, int h, int w);
+int ggan_ssim_pairs(const float* A, const float* B, int n, int c, int h, int w, float scale_a, float shift_a, float scale_b, float shift_b,
+                    float* mse /*[n]*/, float* ssim /*[n]*/, void* ws, size_t ws_bytes, ggan_stream_t stream);
+
 /* Stochastic encoder head, TYPE_Q = 'learn_std' (gan_inference_cifar10.py:173-188): std = exp(log_std), z = mean + eps * std; the backward
  * takes the gradients arriving at z and at std (either may be NULL). */
 int ggan_reparam_fwd(const float* mean, const float* log_std, const float* eps, float* z, float* std_out, size_t n, ggan_stream_t stream);

@@ -17,6 +17,7 @@ SETTINGS.update(run.mmd_settings(__file__))      # dev mmd z / dev mmd x every $
 SETTINGS.update(run.prdc_settings(__file__))     # dev precision / recall / density / coverage z / x every $GGAN_PRDC_EVERY iterations (off when unset)
 SETTINGS.update(run.knn_settings(__file__))      # dev knn accuracy z / x every $GGAN_KNN_EVERY iterations (off when unset; needs a labelled dev set)
 SETTINGS.update(run.parzen_settings(__file__))   # dev parzen ll / se / sigma x every $GGAN_PARZEN_EVERY iterations (off when unset)
+SETTINGS.update(run.rec_settings(__file__))      # dev rec mse / psnr / ssim / ssim se x every $GGAN_REC_EVERY iterations (off when unset)
 if len(sys.argv) > 1:
     SETTINGS['ITERS'] = int(sys.argv[1])
 globals().update(SETTINGS)          # BATCH_SIZE, DIM, DIM_LATENT, CRITIC_ITERS, ... as module constants, as in the reference

@@ -12,6 +12,7 @@ BN_FLAG = False  # BatchNorm in the frame generator, extractors and critics (BN_
 SETTINGS = run.reference_block(__file__, MODE=MODE, BN_FLAG=BN_FLAG)
 # edit the block here, e.g. SETTINGS['N_COMS'] = 10 -- or pass it to reference_block, which then derives N_VIS etc. from it
 SETTINGS.update(run.eval_settings(__file__))  # the video passes every 5000 iterations: samples / train_data / reconstruction / disentangle
+SETTINGS.update(run.rec_settings(__file__))      # dev rec mse / psnr / ssim / ssim se x every $GGAN_REC_EVERY iterations (off when unset)
 SETTINGS.update(DATA_DIR=os.environ.get('GGAN_DATA_DIR', ''), OUT_DIR=os.environ.get('GGAN_OUT_DIR', ''), SAVE_EVERY=10000, LOG_EVERY=100)
 if len(sys.argv) > 1:
     SETTINGS['ITERS'] = int(sys.argv[1])
