@@ -804,12 +804,12 @@ int ggan_bn_fwd_train(const float* x, const float* scale, const float* offset, f
     hipStream_t s = (hipStream_t)stream;
     const double bytes = 12.0 * N * C * HW;
     if (HW > 1 && N * HW <= kRegE * kThreads) {
-        GGAN_LAUNCH("bn_fwd_nchw", 0, 8.0 * N * C * HW, bn_fwd_nchw_reg_k, dim3(C), dim3(kThreads), 0, s, x, scale, offset, y, save_mean, save_invstd, N, C, HW, eps, act, alpha,
+        GGAN_LAUNCH("bn_fwd_nchw_reg_k", 0, 8.0 * N * C * HW, bn_fwd_nchw_reg_k, dim3(C), dim3(kThreads), 0, s, x, scale, offset, y, save_mean, save_invstd, N, C, HW, eps, act, alpha,
                     make_fastdiv((uint32_t)HW));
     } else if (HW > 1) {
-        GGAN_LAUNCH("bn_fwd_nchw", 0, bytes, bn_fwd_nchw_k, dim3(C), dim3(kThreads), 0, s, x, scale, offset, y, save_mean, save_invstd, N, C, HW, eps, act, alpha);
+        GGAN_LAUNCH("bn_fwd_nchw_k", 0, bytes, bn_fwd_nchw_k, dim3(C), dim3(kThreads), 0, s, x, scale, offset, y, save_mean, save_invstd, N, C, HW, eps, act, alpha);
     } else {
-        GGAN_LAUNCH("bn_fwd_rows", 0, bytes, bn_fwd_rows_k, dim3(cdiv(C, kCols)), dim3(kCols, kSlices), 0, s, x, scale, offset, y, save_mean, save_invstd, N, C, eps, act, alpha);
+        GGAN_LAUNCH("bn_fwd_rows_k", 0, bytes, bn_fwd_rows_k, dim3(cdiv(C, kCols)), dim3(kCols, kSlices), 0, s, x, scale, offset, y, save_mean, save_invstd, N, C, eps, act, alpha);
     }
     return 0;
 }
@@ -825,19 +825,19 @@ int ggan_bn_bwd_act(const float* x, const float* gy, const float* y, int y_act, 
     const double bytes = 20.0 * N * C * HW;
     const bool v4 = (HW & 3) == 0 && ((((uintptr_t)x) | ((uintptr_t)gy) | ((uintptr_t)gx) | ((uintptr_t)mk.ref)) & 15) == 0;
     if (HW > 1 && v4 && N * HW <= 16 * 256) {
-        GGAN_LAUNCH("bn_bwd_nchw", 0, 12.0 * N * C * HW, bn_bwd_nchw_reg4_k<256>, dim3(C), dim3(256), 0, s, x, gy, mk, scale, save_mean, save_invstd, gx, gscale, goffset, gx_chansum, N, C, HW,
+        GGAN_LAUNCH("bn_bwd_nchw_reg4_k<256>", 0, 12.0 * N * C * HW, bn_bwd_nchw_reg4_k<256>, dim3(C), dim3(256), 0, s, x, gy, mk, scale, save_mean, save_invstd, gx, gscale, goffset, gx_chansum, N, C, HW,
                     make_fastdiv((uint32_t)HW));
     } else if (HW > 1 && v4 && N * HW <= 16 * 1024) {
-        GGAN_LAUNCH("bn_bwd_nchw", 0, 12.0 * N * C * HW, bn_bwd_nchw_reg4_k<1024>, dim3(C), dim3(1024), 0, s, x, gy, mk, scale, save_mean, save_invstd, gx, gscale, goffset, gx_chansum, N, C, HW,
+        GGAN_LAUNCH("bn_bwd_nchw_reg4_k<1024>", 0, 12.0 * N * C * HW, bn_bwd_nchw_reg4_k<1024>, dim3(C), dim3(1024), 0, s, x, gy, mk, scale, save_mean, save_invstd, gx, gscale, goffset, gx_chansum, N, C, HW,
                     make_fastdiv((uint32_t)HW));
     } else if (HW > 1 && N * HW <= kRegE * kThreads) {
-        GGAN_LAUNCH("bn_bwd_nchw", 0, 12.0 * N * C * HW, bn_bwd_nchw_reg_k, dim3(C), dim3(kThreads), 0, s, x, gy, mk, scale, save_mean, save_invstd, gx, gscale, goffset, gx_chansum, N, C, HW,
+        GGAN_LAUNCH("bn_bwd_nchw_reg_k", 0, 12.0 * N * C * HW, bn_bwd_nchw_reg_k, dim3(C), dim3(kThreads), 0, s, x, gy, mk, scale, save_mean, save_invstd, gx, gscale, goffset, gx_chansum, N, C, HW,
                     make_fastdiv((uint32_t)HW));
     } else if (HW > 1) {
-        GGAN_LAUNCH("bn_bwd_nchw", 0, bytes, bn_bwd_nchw_k, dim3(C), dim3(kThreads), 0, s, x, gy, mk, scale, save_mean, save_invstd, gx, gscale, goffset, gx_chansum, N, C, HW);
+        GGAN_LAUNCH("bn_bwd_nchw_k", 0, bytes, bn_bwd_nchw_k, dim3(C), dim3(kThreads), 0, s, x, gy, mk, scale, save_mean, save_invstd, gx, gscale, goffset, gx_chansum, N, C, HW);
     } else {
         GGAN_CHECK_ARG(!gx_chansum, "gx_chansum is only produced for NCHW inputs (HW > 1)");
-        GGAN_LAUNCH("bn_bwd_rows", 0, bytes, bn_bwd_rows_k, dim3(cdiv(C, kCols)), dim3(kCols, kSlices), 0, s, x, gy, mk, scale, save_mean, save_invstd, gx, gscale, goffset, N, C);
+        GGAN_LAUNCH("bn_bwd_rows_k", 0, bytes, bn_bwd_rows_k, dim3(cdiv(C, kCols)), dim3(kCols, kSlices), 0, s, x, gy, mk, scale, save_mean, save_invstd, gx, gscale, goffset, N, C);
     }
     return 0;
 }
@@ -916,9 +916,9 @@ int ggan_bn_split_fwd_train(const float* x, const float* scale, const float* off
     float* part = (float*)ws;
     const double bytes = 4.0 * N * C * HW;
     if (HW > 1) {
-        GGAN_LAUNCH("bn_split_stats", 0, bytes, bn_sp_stats_nchw_k, dim3(C, d.S, groups), dim3(kSpThreads), 0, s, x, part, d);
+        GGAN_LAUNCH("bn_split_stats_nchw", 0, bytes, bn_sp_stats_nchw_k, dim3(C, d.S, groups), dim3(kSpThreads), 0, s, x, part, d);
     } else {
-        GGAN_LAUNCH("bn_split_stats", 0, bytes, bn_sp_stats_rows_k, dim3(cdiv(C, kSpCols), d.S, groups), dim3(kSpCols, kSpLanes), 0, s,
+        GGAN_LAUNCH("bn_split_stats_rows", 0, bytes, bn_sp_stats_rows_k, dim3(cdiv(C, kSpCols), d.S, groups), dim3(kSpCols, kSpLanes), 0, s,
                     x, part, d);
     }
     GGAN_LAUNCH("bn_split_merge", 0, 12.0 * groups * d.S * C, bn_sp_merge_k, dim3(cdiv(C, kSpCols), groups), dim3(kSpCols, kSpMerge), 0,
@@ -951,10 +951,10 @@ int ggan_bn_split_bwd_act(const float* x, const float* gy, int act, float alpha,
     float* coef = part + part_floats;
     const double bytes = 8.0 * N * C * HW / groups * sgroups;
     if (HW > 1) {
-        GGAN_LAUNCH("bn_split_bwd_stats", 0, bytes, bn_sp_bwd_stats_nchw_k, dim3(C, d.S, sgroups), dim3(kSpThreads), 0, s, x, gy, scale,
+        GGAN_LAUNCH("bn_split_bwd_stats_nchw", 0, bytes, bn_sp_bwd_stats_nchw_k, dim3(C, d.S, sgroups), dim3(kSpThreads), 0, s, x, gy, scale,
                     offset, save_mean, save_invstd, part, d, act, alpha);
     } else {
-        GGAN_LAUNCH("bn_split_bwd_stats", 0, bytes, bn_sp_bwd_stats_rows_k, dim3(cdiv(C, kSpCols), d.S, sgroups), dim3(kSpCols, kSpLanes),
+        GGAN_LAUNCH("bn_split_bwd_stats_rows", 0, bytes, bn_sp_bwd_stats_rows_k, dim3(cdiv(C, kSpCols), d.S, sgroups), dim3(kSpCols, kSpLanes),
                     0, s, x, gy, scale, offset, save_mean, save_invstd, part, d, act, alpha);
     }
     GGAN_LAUNCH("bn_split_bwd_merge", 0, 12.0 * sgroups * d.S * C, bn_sp_bwd_merge_k, dim3(cdiv(C, kSpCols)), dim3(kSpCols, kSpMerge), 0,

@@ -238,9 +238,9 @@ extern "C" int ggan_linear_bn_rows_bwd(const float* x, const float* gy, const fl
         once = true;
     }
     const dim3 grid(N / LB_COLS), block(LB_THR);
-    if (K == 64) { GGAN_LAUNCH("linear_bn_rows_bwd_k", fl, bytes, linear_bn_rows_bwd_k<4>, grid, block, shmem, s, P); }
-    else if (K == 128) { GGAN_LAUNCH("linear_bn_rows_bwd_k", fl, bytes, linear_bn_rows_bwd_k<8>, grid, block, shmem, s, P); }
-    else { GGAN_LAUNCH("linear_bn_rows_bwd_k", fl, bytes, linear_bn_rows_bwd_k<16>, grid, block, shmem, s, P); }
+    if (K == 64) { GGAN_LAUNCH("linear_bn_rows_bwd_k<4>", fl, bytes, linear_bn_rows_bwd_k<4>, grid, block, shmem, s, P); }
+    else if (K == 128) { GGAN_LAUNCH("linear_bn_rows_bwd_k<8>", fl, bytes, linear_bn_rows_bwd_k<8>, grid, block, shmem, s, P); }
+    else { GGAN_LAUNCH("linear_bn_rows_bwd_k<16>", fl, bytes, linear_bn_rows_bwd_k<16>, grid, block, shmem, s, P); }
     return 0;
 }
 
@@ -273,14 +273,14 @@ extern "C" int ggan_linear_bn_rows_fwd(const float* x, const float* w, const flo
     }
     const dim3 grid(N / LB_COLS), block(LB_THR);
     switch (M / LB_GROUPS) {
-        case 1: GGAN_LAUNCH("linear_bn_rows_k", fl, bytes, linear_bn_rows_k<1>, grid, block, shmem, s, P); break;
-        case 2: GGAN_LAUNCH("linear_bn_rows_k", fl, bytes, linear_bn_rows_k<2>, grid, block, shmem, s, P); break;
-        case 3: GGAN_LAUNCH("linear_bn_rows_k", fl, bytes, linear_bn_rows_k<3>, grid, block, shmem, s, P); break;
-        case 4: GGAN_LAUNCH("linear_bn_rows_k", fl, bytes, linear_bn_rows_k<4>, grid, block, shmem, s, P); break;
-        case 5: GGAN_LAUNCH("linear_bn_rows_k", fl, bytes, linear_bn_rows_k<5>, grid, block, shmem, s, P); break;
-        case 6: GGAN_LAUNCH("linear_bn_rows_k", fl, bytes, linear_bn_rows_k<6>, grid, block, shmem, s, P); break;
-        case 7: GGAN_LAUNCH("linear_bn_rows_k", fl, bytes, linear_bn_rows_k<7>, grid, block, shmem, s, P); break;
-        case 8: GGAN_LAUNCH("linear_bn_rows_k", fl, bytes, linear_bn_rows_k<8>, grid, block, shmem, s, P); break;
+        case 1: GGAN_LAUNCH("linear_bn_rows_k<1>", fl, bytes, linear_bn_rows_k<1>, grid, block, shmem, s, P); break;
+        case 2: GGAN_LAUNCH("linear_bn_rows_k<2>", fl, bytes, linear_bn_rows_k<2>, grid, block, shmem, s, P); break;
+        case 3: GGAN_LAUNCH("linear_bn_rows_k<3>", fl, bytes, linear_bn_rows_k<3>, grid, block, shmem, s, P); break;
+        case 4: GGAN_LAUNCH("linear_bn_rows_k<4>", fl, bytes, linear_bn_rows_k<4>, grid, block, shmem, s, P); break;
+        case 5: GGAN_LAUNCH("linear_bn_rows_k<5>", fl, bytes, linear_bn_rows_k<5>, grid, block, shmem, s, P); break;
+        case 6: GGAN_LAUNCH("linear_bn_rows_k<6>", fl, bytes, linear_bn_rows_k<6>, grid, block, shmem, s, P); break;
+        case 7: GGAN_LAUNCH("linear_bn_rows_k<7>", fl, bytes, linear_bn_rows_k<7>, grid, block, shmem, s, P); break;
+        case 8: GGAN_LAUNCH("linear_bn_rows_k<8>", fl, bytes, linear_bn_rows_k<8>, grid, block, shmem, s, P); break;
         default: return 1;
     }
     return 0;     // (GGAN_LAUNCH checks the launch: a refused one returns -2 with the error text)
