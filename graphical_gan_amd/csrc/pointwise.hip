@@ -740,6 +740,44 @@ __global__ void rmsprop_k(float* __restrict__ theta, const float* __restrict__ g
     }
 }
 
+// ---- exponential moving average of the weights (evaluation only) ---------------------------------
+// No call site in the reference: the semantics are those of TensorFlow 1's documented tf.train.ExponentialMovingAverage(decay,
+// num_updates): d_t = min(decay, (1 + t) / (10 + t)); shadow -= (1 - d_t) * (shadow - theta), with t = step[0], the ordinal of the
+// update just applied (the optimizer's device-side counter, already advanced).  theta is only read.
+__global__ void ema_k(float* __restrict__ shadow, const float* __restrict__ theta, size_t n, const int32_t* __restrict__ step,
+                      float decay) {
+    const float t = (float)step[0];
+    const float w = 1.f - fminf(decay, (1.f + t) / (10.f + t));
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+    size_t n4 = n >> 2;
+    float4* s4 = reinterpret_cast<float4*>(shadow);
+    const float4* th4 = reinterpret_cast<const float4*>(theta);
+    for (size_t j = i; j < n4; j += stride) {
+        float4 s = s4[j];
+        const float4 th = th4[j];
+        s.x -= w * (s.x - th.x); s.y -= w * (s.y - th.y);
+        s.z -= w * (s.z - th.z); s.w -= w * (s.w - th.w);
+        s4[j] = s;
+    }
+    for (size_t j = (n4 << 2) + i; j < n; j += stride) shadow[j] -= w * (shadow[j] - theta[j]);
+}
+
+// a <-> b in one pass (the averaged weights visit the live storage for an evaluation: captured graphs bake theta's address)
+__global__ void swap_k(float* __restrict__ a, float* __restrict__ b, size_t n) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+    size_t n4 = n >> 2;
+    float4* a4 = reinterpret_cast<float4*>(a);
+    float4* b4 = reinterpret_cast<float4*>(b);
+    for (size_t j = i; j < n4; j += stride) {
+        const float4 va = a4[j], vb = b4[j];
+        a4[j] = vb; b4[j] = va;
+    }
+    for (size_t j = (n4 << 2) + i; j < n; j += stride) {
+        const float va = a[j], vb = b[j];
+        a[j] = vb; b[j] = va;
+    }
+}
+
 struct PackTable {
     const float* src[GGAN_PACK_MAX];
     size_t size[GGAN_PACK_MAX];
@@ -1735,6 +1773,26 @@ int ggan_rmsprop_step(float* theta, const float* g, float* ms, size_t n, float l
     if (n == 0) return 0;
     GGAN_LAUNCH("rmsprop_step", 0, 20.0 * n, rmsprop_k, dim3(grid_for(n, 8)), dim3(kBlock), 0, (hipStream_t)stream, theta, g, ms, n, lr,
                 decay, eps, grad_scale, clip_lo, clip_hi);
+    return 0;
+}
+
+int ggan_ema_step(float* shadow, const float* theta, size_t n, const int32_t* step, float decay, ggan_stream_t stream) {
+    GGAN_CHECK_ARG(shadow && theta && step, "null pointer");
+    GGAN_CHECK_ARG(decay >= 0.f && decay < 1.f, "decay must lie in [0, 1)");
+    GGAN_CHECK_ARG(shadow != theta, "shadow and theta are the same buffer");
+    GGAN_CHECK_ARG(shadow + n <= theta || theta + n <= shadow, "the buffers overlap");
+    if (n == 0) return 0;
+    GGAN_CHECK_ARG(aligned16(shadow) && aligned16(theta), "buffers must be 16-byte aligned");
+    GGAN_LAUNCH("ema_step", 0, 12.0 * n, ema_k, dim3(grid_for(n)), dim3(kBlock), 0, (hipStream_t)stream, shadow, theta, n, step, decay);
+    return 0;
+}
+
+int ggan_swap(float* a, float* b, size_t n, ggan_stream_t stream) {
+    GGAN_CHECK_ARG(a && b, "null pointer");
+    GGAN_CHECK_ARG(a + n <= b || b + n <= a, "the buffers overlap");
+    if (n == 0) return 0;
+    GGAN_CHECK_ARG(aligned16(a) && aligned16(b), "buffers must be 16-byte aligned");
+    GGAN_LAUNCH("swap", 0, 16.0 * n, swap_k, dim3(grid_for(n)), dim3(kBlock), 0, (hipStream_t)stream, a, b, n);
     return 0;
 }
 

@@ -95,8 +95,11 @@ def dp_graph_selftest(device, comm):
 
 
 class Trainer(object):
-    def __init__(self, cfg, device=None, graph=True, seed=1234, inject_noise=False, model=None, sync_bn=False):
-        """sync_bn: BatchNorm statistics over the global batch of all replicas (N GPUs x B/N then reproduce
+    def __init__(self, cfg, device=None, graph=True, seed=1234, inject_noise=False, model=None, sync_bn=False, ema_decay=None):
+        """ema_decay: a float in [0, 1) keeps an exponential moving average of the generator-side weights (the `gen` optimizer's
+        var_list) on the device, advanced inside every generator step and read only by get_params(weights='ema'), ema_weights() and a
+        checkpoint; None (default): no buffer, no launch.
+        sync_bn: BatchNorm statistics over the global batch of all replicas (N GPUs x B/N then reproduce
         1 GPU x B).  The statistics exchange is a host-issued collective inside the forward and the backward, so this mode
         runs the steps eagerly (no HIP graphs); it is the parity mode, per-replica statistics stay the throughput default.
         model: an object with forward_nets / forward / feed_buffers / sample_noise / set_batch / single_contribution
@@ -150,6 +153,12 @@ class Trainer(object):
         self._opts = None
         self.keep_outputs, self.last_out = False, {}
         self._pending = None         # (work handle, Adam graph) of a critic-step exchange still in flight (see step())
+        # for the optimizer the first generator step builds (None: a Trainer that averaged before this one leaves no setting behind); a live
+        # optimizer stays as it was built -- its captured graphs hold its launches and its buffers
+        _optim.set_ema('gen', ema_decay)
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self._ema_inside = False
+        self.ema_loaded = False      # (evaluate --ema: the live weights of this process ARE averaged ones read from a checkpoint)
 
     # ---- inputs ---------------------------------------------------------------------------------------
     def set_feed(self, feed):
@@ -557,15 +566,19 @@ class Trainer(object):
 
     @contextlib.contextmanager
     def _restored(self):
-        """the optimizers' state (theta, m, v, step counts) and the device noise state as they were in front of the block: warm-up steps and
-        the dress rehearsal of a capture leave no trace (a graph=True and a graph=False run with the same seed take the same steps and draw
-        the same noise sequence).  Snapshot and restore are issued on the current stream."""
+        """the optimizers' state (theta, m, v, step counts, the weight average) and the device noise state as they were in front of the
+        block: warm-up steps and the dress rehearsal of a capture leave no trace (a graph=True and a graph=False run with the same seed take
+        the same steps and draw the same noise sequence; the average never sees weights that were rolled back).  Snapshot and restore are
+        issued on the current stream."""
         snap = [(o, o.theta.clone(), o.m.clone(), o.v.clone(), o.step.clone()) for o in self._optimizers()]
+        shadows = [(o, o.shadow.clone()) for o in self._optimizers() if o.shadow is not None]
         rng = self.feed.get('rng_state') if isinstance(self.feed, dict) else None
         rng_snap = rng.clone() if torch.is_tensor(rng) else None
         yield
         for o, th, m, v, st in snap:
             o.theta.copy_(th); o.m.copy_(m); o.v.copy_(v); o.step.copy_(st)
+        for o, sh in shadows:
+            o.shadow.copy_(sh)
         if rng_snap is not None:
             rng.copy_(rng_snap)
 
@@ -616,6 +629,8 @@ class Trainer(object):
 
     def _count(self, kinds):
         """the steps [kinds] are about to be taken"""
+        if self._ema_inside:
+            raise RuntimeError('a training step inside Trainer.ema_weights(): the parameters hold the averaged weights')
         for k in kinds:
             self._calls[k] += 1
         if self._calls['gen'] >= 2 and (self._calls['disc'] >= 2 or not getattr(self.cfg, 'critic_iters', 1)):
@@ -802,10 +817,70 @@ class Trainer(object):
                 trainable = not (name.endswith('.moving_mean') or name.endswith('.moving_variance'))
                 p = lib.param(name, np.asarray(v, dtype=np.float32), trainable=trainable)
                 p.data.copy_(torch.as_tensor(np.asarray(v, dtype=np.float32)).reshape(p.shape))
+        for o in self._optimizers():             # the average of an overwritten parameter restarts from its new value
+            o.seed_ema(set(params))
 
-    def get_params(self):
+    def _ema_optimizer(self, need=True):
+        """the `gen` optimizer when it keeps an average; None (need=False) or an error saying why there is none"""
+        opt = next((o for key, o in _optim._optimizers.items() if key[0] == 'gen'), None)
+        if opt is not None and opt.shadow is not None:
+            return opt
+        if not need:
+            return None
+        if self.ema_decay is None:
+            raise RuntimeError('no averaged weights: this Trainer was built without ema_decay ($GGAN_EMA_DECAY / EMA_DECAY is unset)')
+        if opt is not None:
+            raise RuntimeError('no averaged weights: the generator-side optimizer was built before this Trainer asked for an average '
+                               '(optim.reset_optimizers() first)')
+        raise RuntimeError('no averaged weights yet: the generator-side optimizer is built by the first generator step')
+
+    def has_ema(self):
+        """does the generator-side optimizer exist and keep an average (from the first generator step of an averaging Trainer on)"""
+        return self._ema_optimizer(need=False) is not None
+
+    def ema_pending(self):
+        """averaging was asked for and no generator-side optimizer exists yet: until the first generator step the average IS the weights"""
+        return self.ema_decay is not None and not any(key[0] == 'gen' for key in _optim._optimizers)
+
+    def get_params(self, weights='live'):
+        """name -> numpy array of every registry entry.  weights='ema': the averaged values of the generator-side parameters (before the
+        first generator step the average IS the initial weights) and the live values of everything else, the critic included."""
+        if weights not in ('live', 'ema'):
+            raise ValueError("weights: 'live' or 'ema', not %r" % (weights,))
         self.flush()
-        return {n: p.detach().cpu().numpy().copy() for n, p in lib.named_params().items()}
+        out = {n: p.detach().cpu().numpy().copy() for n, p in lib.named_params().items()}
+        if weights == 'live' and not self._ema_inside:
+            return out
+        if weights == 'ema' and self.ema_decay is None:
+            self._ema_optimizer()
+        opt = self._ema_optimizer(need=False)
+        if opt is not None and (weights == 'ema') != self._ema_inside:      # (inside ema_weights() the two buffers are exchanged)
+            flat = opt.shadow.cpu().numpy()
+            for p, (o, n) in zip(opt.params, opt.slots):
+                out[p.param_name] = flat[o:o + n].reshape(tuple(p.shape)).copy()
+        return out
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """inside the block the generator-side parameters hold their averaged values, in their own storage (captured graphs and evaluators
+        keep the addresses they know); the live values wait in the average's buffer and come back bit for bit on the way out, also after
+        an exception.  One exchange kernel each way, the device idle around both.  Entering again while inside does nothing.  No training
+        step may run inside."""
+        if self._ema_inside:
+            yield
+            return
+        opt = self._ema_optimizer()
+        self.flush()
+        torch.cuda.synchronize(self.device)
+        F.swap_(opt.theta, opt.shadow)
+        self._ema_inside, opt.ema_live = True, False
+        try:
+            yield
+        finally:
+            torch.cuda.synchronize(self.device)       # (whatever stream the block's passes ran on)
+            F.swap_(opt.theta, opt.shadow)
+            self._ema_inside, opt.ema_live = False, True
+            torch.cuda.synchronize(self.device)
 
 
 def broadcast_params(src=0):

@@ -49,7 +49,12 @@ Each is written as a .png sheet (one sequence per row) and a looping .gif; the b
 `python -m graphical_gan_amd.evaluate CKPT --script gmgan_inference_mnist [--data-dir DIR]` scores a saved checkpoint
 (`--out-dir DIR --manifold` also writes the latent-space pictures of the two MNIST scripts, `--mmd` adds the two MMD^2 rows, `--prdc` the eight precision / recall / density / coverage rows, `--knn` the two k-NN accuracy rows, `--parzen` the three Parzen-window rows, `--rec` the four reconstruction rows);
 `... CKPT --script ssgan_inference_moving_mnist|ssgan_inference_chairs [--data-dir DIR] --out-dir DIR` writes the four pairs of files;
-`--rec` prints the four reconstruction rows of the sequences' frames, and alone needs no --out-dir."""
+`--rec` prints the four reconstruction rows of the sequences' frames, and alone needs no --out-dir.
+
+Every pass can look at an exponential moving average of the generator-side weights instead of the last iterate (engine.Trainer's
+ema_decay; no part of the reference): an evaluator with `weights = 'ema'` runs its passes inside Trainer.ema_weights(), `tag` / `_fname`
+give the names (' ema') and files ('_ema') of what it then reports, and `... CKPT --ema` scores the `ema/gen/` keys of a checkpoint.
+The critic has no average: `dev gen cost ema` sets the averaged Generator / Extractor against the live critic."""
 import argparse
 import contextlib
 import os
@@ -140,16 +145,42 @@ def _rec_stats(mse, ssim):
 
 
 class _Passes(object):
-    """what the image and the sequence evaluator share: the guard every pass runs under"""
+    """what the image and the sequence evaluator share: the guard every pass runs under, and which weights it looks at"""
     last_seconds = 0.0            # wall time of the last pass (device work included)
+    weights = 'live'              # 'ema': every pass runs on the averaged generator-side weights (Trainer.ema_weights; the critic stays live)
+
+    def tag(self, names):
+        """the names a pass's values are logged under: {name: value} -> the same with ' ema' appended while weights == 'ema'"""
+        return {k + ' ema': v for k, v in names.items()} if self.weights == 'ema' else names
+
+    def _fname(self, path):
+        """the file a pass writes: '_ema' in front of the extension while weights == 'ema'"""
+        if self.weights != 'ema':
+            return path
+        stem, ext = os.path.splitext(path)
+        return stem + '_ema' + ext
+
+    @contextlib.contextmanager
+    def _visit(self):
+        """inside the block the parameters hold what `weights` names.  'live': nothing to do.  'ema': Trainer.ema_weights() (entering it
+        again inside is free), except where the parameters already hold the average -- a Trainer whose weights ARE averaged ones read
+        from a checkpoint (main --ema), or an averaging Trainer before its first generator step, whose average still is the weights"""
+        if self.weights not in ('live', 'ema'):
+            raise ValueError("weights: 'live' or 'ema', not %r" % (self.weights,))
+        if self.weights == 'live' or self.tr.ema_loaded or self.tr.ema_pending():
+            yield
+        else:
+            with self.tr.ema_weights():
+                yield
 
     @contextlib.contextmanager
     def _guard(self):
-        """a pass: no tape, the current stream only, the model's step-building state and numpy's RNG state as they were"""
+        """a pass: on the weights `weights` names (_visit), no tape, the current stream only, the model's step-building state and numpy's
+        RNG state as they were"""
         np_state = np.random.get_state()
         t0 = time.time()
         try:
-            with torch.no_grad(), self.model.single_stream():
+            with self._visit(), torch.no_grad(), self.model.single_stream():
                 yield
         finally:
             np.random.set_state(np_state)
@@ -484,8 +515,9 @@ class Evaluator(_Passes):
                     embedded[points] = Y.cpu().numpy()
                     self.manifold_log.append((points, kl, time.time() - t0))
                     print('[eval] t-SNE of %s %s: KL %.4f, %.2f s' % (points, tuple(sets[points].shape), kl, time.time() - t0))
-                lib.visualization.scatter(embedded[points], sets[labels].cpu().numpy(), out_dir, fname.format(frame=frame, mode=mode))
-                paths.append(os.path.join(out_dir, fname.format(frame=frame, mode=mode)))
+                out_name = self._fname(fname.format(frame=frame, mode=mode))
+                lib.visualization.scatter(embedded[points], sets[labels].cpu().numpy(), out_dir, out_name)
+                paths.append(os.path.join(out_dir, out_name))
         self.last_seconds += t_sets
         return paths
 
@@ -529,14 +561,14 @@ class Evaluator(_Passes):
         shape = (-1, c.C, c.S, c.S)
         paths = []
         grid = self._to_unit(self.sample_grid()).reshape(shape)
-        p = os.path.join(out_dir, fs.format(frame=frame, mode=mode))
+        p = self._fname(os.path.join(out_dir, fs.format(frame=frame, mode=mode)))
         lib.save_images.save_images(grid, p, size=[grid.shape[0] // c.K, c.K] if c.K else None)
         paths.append(p)
         if self.fixed_data is not None:
             real, rec = self.reconstructions()
             pairs = np.empty((2 * c.B, c.output_dim), dtype=np.float32)
             pairs[0::2], pairs[1::2] = self._to_unit(real), self._to_unit(rec)
-            p = os.path.join(out_dir, fr.format(frame=frame, mode=mode))
+            p = self._fname(os.path.join(out_dir, fr.format(frame=frame, mode=mode)))
             lib.save_images.save_images(pairs.reshape(shape), p)
             paths.append(p)
         return paths
@@ -729,7 +761,8 @@ class SequenceEvaluator(_Passes):
             if name not in host:
                 continue
             sheet, planes = host[name]
-            stem = os.path.join(out_dir, '%s_%s' % (name, frame))
+            # (train_data holds data only: one file whatever weights the other three were drawn from)
+            stem = os.path.join(out_dir, '%s_%s' % (name, frame)) + ('_ema' if self.weights == 'ema' and name != 'train_data' else '')
             S.write_png(stem + '.png', sheet)
             S.write_gif(stem + '.gif', planes, palette)
             paths += [stem + '.png', stem + '.gif']
@@ -754,6 +787,7 @@ def main(argv=None):
     ap.add_argument('--knn', action='store_true', help='also score the labelled dev set by the leave-one-out k-NN accuracy of codes and of images (dev knn accuracy z / x; image scripts)')
     ap.add_argument('--parzen', action='store_true', help='also score the dev set by the Gaussian Parzen-window log-likelihood of held-out images under generated ones (dev parzen ll / se / sigma x; image scripts)')
     ap.add_argument('--rec', action='store_true', help='also score how well Generator(Extractor(x)) gives the dev set back: per-image (state-space scripts: per-frame) mse / PSNR / SSIM in the unit pixel range (dev rec mse / psnr / ssim / ssim se x; every script)')
+    ap.add_argument('--ema', action='store_true', help="score the averaged generator-side weights the checkpoint holds (its ema/gen/ keys, written by a run with $GGAN_EMA_DECAY) instead of the last iterate: every name gets the suffix ' ema', every file '_ema'; the critic of 'dev gen cost ema' is the live one")
     ap.add_argument('--set', action='append', default=[], metavar='KEY=VALUE', help='override an UPPERCASE setting (int / float / str)')
     a = ap.parse_args(argv)
     over = {}
@@ -790,8 +824,19 @@ def main(argv=None):
         if not a.out_dir and not a.rec:
             ap.error('--out-dir is required for %s: its passes are files' % a.script)
         model = StateSpaceGAN(cfg)
+    ema = None
+    if a.ema:
+        try:
+            ema = checkpoint.ema_params(a.ckpt)
+        except ValueError as e:
+            ap.error('--ema: %s' % e)
     tr = Trainer(cfg, device=lib.get_device(), graph=False, model=model)
     checkpoint.restore(a.ckpt, tr)
+    if a.ema:
+        # no optimizer is built here, so there is no average to visit: the averaged values ARE this process's weights (the critic's stay
+        # the checkpoint's live ones), and the evaluators only name what they write
+        tr.load_params(ema)
+        tr.ema_loaded = True
     res = evaluate_once(tr, S, out_dir=a.out_dir, manifold=a.manifold, mmd=a.mmd, prdc=a.prdc, knn=a.knn, parzen=a.parzen, rec=a.rec)
     for k in sorted(res):
         print('%s\t%s' % (k, res[k]))
@@ -801,30 +846,34 @@ def main(argv=None):
 def evaluate_once(tr, S, out_dir=None, frame='eval', manifold=False, mmd=False, prdc=False, knn=False, parzen=False, rec=False):
     """every pass the script's data allow, once -> {name: value}; manifold: the latent-space pictures too (labelled dev data only);
     mmd: the two dev-set MMD^2 scores too; prdc: the eight precision / recall / density / coverage scores too; knn: the two k-NN
-    accuracies too (labelled dev data only); parzen: the three Parzen-window values too; rec: the four reconstruction values too -- one build of the sets for the five.  The
+    accuracies too (labelled dev data only); a trainer whose weights are averaged ones loaded from a checkpoint (tr.ema_loaded, main --ema):
+    names and files carry the suffixes; parzen: the three Parzen-window values too; rec: the four reconstruction values too -- one build of the sets for the five.  The
     state-space scripts: the video files (with out_dir) and, with rec, the four reconstruction values of the dev sequences' frames"""
     from . import run
+    ema_names = bool(getattr(tr, 'ema_loaded', False))
     if S['DATASET'] in run.SEQUENCE_DATASETS:       # the video passes: files only (train_data: the first dev minibatch)
         ev = SequenceEvaluator(tr, S)
+        ev.weights = 'ema' if ema_names else 'live'
         dev, _ = run.eval_sets(S, tr.model, tr.device)
         res = {}
         if rec:
-            res.update(ev.rec_scores(run.rec_sequences(S, tr.model, tr.device)))
+            res.update(ev.tag(ev.rec_scores(run.rec_sequences(S, tr.model, tr.device))))
         if out_dir:
             ev.set_fixed_data(dev[0])
             os.makedirs(out_dir, exist_ok=True)
             res['files'] = ' '.join(os.path.basename(p) for p in ev.save_videos(out_dir, frame, train_data=dev[0]))
         return res
     ev = Evaluator(tr, S)
+    ev.weights = 'ema' if ema_names else 'live'
     dev, test = run.eval_sets(S, tr.model, tr.device)
-    res = dict(ev.dev_costs(dev))
+    res = dict(ev.tag(ev.dev_costs(dev)))
     if tr.cfg.K and test is not None:
-        res['testing accuracy'] = ev.cluster_accuracy(test)
+        res.update(ev.tag({'testing accuracy': ev.cluster_accuracy(test)}))
     if knn and not run.labelled(dev):
         print('[evaluate] dev knn accuracy skipped: no labelled dev set')
         knn = False
     if mmd or prdc or knn or parzen or rec:
-        res.update(ev.set_scores(dev, mmd=mmd, prdc=prdc, knn=knn, parzen=parzen, rec=rec))
+        res.update(ev.tag(ev.set_scores(dev, mmd=mmd, prdc=prdc, knn=knn, parzen=parzen, rec=rec)))
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
         ev.set_fixed_data(dev[0])

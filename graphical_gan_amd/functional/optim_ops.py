@@ -29,6 +29,25 @@ def rmsprop_step_(theta, g, ms, lr, decay=0.9, eps=1e-10, grad_scale=1.0, clip=N
           'ggan_rmsprop_step')
 
 
+def ema_step_(shadow, theta, step, decay):
+    """shadow -= (1 - d_t) * (shadow - theta), d_t = min(decay, (1 + t) / (10 + t)) with t = step[0] read on the device: the ordinal
+    of the update just applied (tf.train.ExponentialMovingAverage(decay, num_updates)).  In place; graph-capturable."""
+    assert shadow.numel() == theta.numel() and step.dtype == torch.int32
+    assert shadow.dtype == torch.float32 and theta.dtype == torch.float32 and shadow.is_contiguous() and theta.is_contiguous()
+    if not (shadow.is_cuda and theta.is_cuda and step.is_cuda):
+        raise _lib.GganError('ema_step_ has no CPU path')
+    check(_L().ggan_ema_step(_p(shadow), _p(theta), theta.numel(), _p(step), float(decay), _stream()), 'ggan_ema_step')
+
+
+def swap_(a, b):
+    """exchanges the contents of two non-overlapping fp32 buffers, bitwise, in one pass"""
+    assert a.numel() == b.numel() and a.dtype == torch.float32 and b.dtype == torch.float32
+    assert a.is_contiguous() and b.is_contiguous()
+    if not (a.is_cuda and b.is_cuda):
+        raise _lib.GganError('swap_ has no CPU path')
+    check(_L().ggan_swap(_p(a), _p(b), a.numel(), _stream()), 'ggan_swap')
+
+
 NOISE_NORMAL, NOISE_UNIFORM, NOISE_ONEHOT = 0, 1, 2
 
 

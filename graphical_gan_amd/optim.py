@@ -109,6 +109,35 @@ class AdamOptimizer(object):
         self._one = None
         self._arrive, self._updated = None, False
         self.world = self.bucket.world
+        # evaluation-only moving average of theta (enable_ema): a flat buffer of theta's layout, written by update() and read by nobody
+        # in a step.  ema_live: False while the two buffers are exchanged (engine.Trainer.ema_weights)
+        self.shadow, self.ema_decay, self.ema_live = None, None, True
+
+    # -- the averaged weights -------------------------------------------------------------------------
+    def enable_ema(self, decay):
+        """keep shadow -= (1 - d_t) * (shadow - theta) after every update from here on (tf.train.ExponentialMovingAverage(decay,
+        num_updates = the step ordinal)); the shadow starts as the weights of this moment.  Captured graphs of this optimizer's steps
+        made before the call do not hold the launch: get_optimizer enables it as it builds the optimizer, before any capture."""
+        self.ema_decay = check_ema_decay(decay)
+        if self.shadow is None:
+            self.shadow = self.theta.clone()
+
+    def seed_ema(self, names=None):
+        """the shadow of the parameters `names` (all when None) restarts from their current weights"""
+        if self.shadow is None:
+            return
+        with torch.no_grad():
+            for p, (o, n) in zip(self.params, self.slots):
+                if names is None or getattr(p, 'param_name', None) in names:
+                    self.shadow[o:o + n].copy_(self.theta[o:o + n])
+
+    def _ema(self):
+        """the tail of every way an update is applied: one launch on the current stream, t read from the device-side counter"""
+        if self.shadow is not None:
+            if not self.ema_live:
+                raise RuntimeError('an optimizer step inside Trainer.ema_weights(): the live weights are parked in the shadow buffer')
+            _xlog('ema')
+            F.ema_step_(self.shadow, self.theta, self.step, self.ema_decay)
 
     # -- one optimizer step ---------------------------------------------------------------------------
     def compute_gradients(self, cost):
@@ -176,10 +205,12 @@ class AdamOptimizer(object):
         if self._updated:            # applied by the pack launch (pack(fuse_update=True))
             self._updated = False
             _xlog('update', 'in the pack launch')
+            self._ema()
             return
         _xlog('update')
         F.adam_step_(self.theta, self.g, self.m, self.v, self.step, self.lr, self.beta1, self.beta2, self.eps,
                      self.bucket.scale, counted=True)
+        self._ema()
 
     def apply_gradients(self, grads):
         keep = self.pack(grads, fuse_update=True)
@@ -191,7 +222,10 @@ class AdamOptimizer(object):
         return self.apply_gradients(self.compute_gradients(cost))
 
     def state_dict(self):
-        return dict(m=self.m.clone(), v=self.v.clone(), step=self.step.clone())
+        st = dict(m=self.m.clone(), v=self.v.clone(), step=self.step.clone())
+        if self.shadow is not None:
+            st.update(shadow=self.shadow.clone(), ema_decay=self.ema_decay)
+        return st
 
 
 class RMSPropOptimizer(AdamOptimizer):
@@ -205,6 +239,7 @@ class RMSPropOptimizer(AdamOptimizer):
 
     def update(self):
         F.rmsprop_step_(self.theta, self.g, self.m, self.lr, self.decay, self.eps, self.bucket.scale, self.clip)
+        self._ema()             # (the pack launch of this step advanced the counter)
 
 
 class TrainOp(object):
@@ -231,6 +266,8 @@ def get_optimizer(role, params, **hp):
         kind = hp.pop('kind', 'adam')
         opt = RMSPropOptimizer(params, **hp) if kind == 'rmsprop' else AdamOptimizer(params, **hp)
         _optimizers[key] = opt
+        if _ema_decay.get(role) is not None:            # (before the parked state: a checkpoint's shadow lands in the buffer)
+            opt.enable_ema(_ema_decay[role])
         if role in _pending_state:                      # a checkpoint restored before this optimizer existed
             load_adam_state(opt, _pending_state.pop(role))
     return opt
@@ -238,12 +275,36 @@ def get_optimizer(role, params, **hp):
 
 _pending_state = {}
 
+# role -> decay of the evaluation-only weight average its optimizer keeps (AdamOptimizer.enable_ema), consulted when get_optimizer
+# builds the optimizer of that role; empty: no optimizer allocates a shadow or adds a launch.  Only 'gen' is ever set (engine.Trainer's
+# ema_decay): no observation pass samples from the critic.
+_ema_decay = {}
+
+
+def check_ema_decay(decay):
+    d = float(decay)
+    if not 0.0 <= d < 1.0:
+        raise ValueError('ema decay %r: a float in [0, 1)' % (decay,))
+    return d
+
+
+def set_ema(role, decay):
+    """decay: a float in [0, 1), or None for no average.  Applies to the optimizer of `role` built from here on.  A live optimizer stays
+    as it was built -- captured step graphs hold its launches and the address of its shadow, so neither is added or dropped under them;
+    reset_optimizers() first."""
+    if decay is None:
+        _ema_decay.pop(role, None)
+    else:
+        _ema_decay[role] = check_ema_decay(decay)
+
 
 STATE_EPOCH = [0]       # bumped whenever an optimizer's step counter is overwritten from outside (engine.Trainer re-anchors its ring feed)
 
 
 def load_adam_state(opt, state):
-    """state: {'step': int32[1], '<param name>/m': array, '<param name>/v': array} (checkpoint.py)"""
+    """state: {'step': int32[1], '<param name>/m': array, '<param name>/v': array} and, from a run that averaged, '<param name>/ema': array
+    (checkpoint.py).  An averaging optimizer takes the shadow of a parameter from its 'ema' entry, and from the parameter's current
+    weights where the state has none; one that does not average ignores the entries."""
     STATE_EPOCH[0] += 1
     with torch.no_grad():
         opt.step.copy_(torch.as_tensor(state['step']).to(opt.step.device).reshape(opt.step.shape))
@@ -252,10 +313,17 @@ def load_adam_state(opt, state):
                 a = state.get('%s/%s' % (p.param_name, which))
                 if a is not None:
                     buf[o:o + n].copy_(torch.as_tensor(a, dtype=torch.float32).reshape(-1))
+            if opt.shadow is not None:
+                a = state.get('%s/ema' % p.param_name)
+                if a is not None:
+                    opt.shadow[o:o + n].copy_(torch.as_tensor(a, dtype=torch.float32).reshape(-1))
+                else:
+                    opt.shadow[o:o + n].copy_(opt.theta[o:o + n])
 
 
 def reset_optimizers(keep_params=True):
-    """Drop every optimizer (their flat theta / m / v / g buffers go with them).  keep_params: the parameters move back into
+    """Drop every optimizer (their flat theta / m / v / g buffers and weight averages go with them; which role averages, set_ema, is a
+    setting of the run and stays).  keep_params: the parameters move back into
     storage of their own; False when the registry is being emptied anyway (tflib.delete_all_params)."""
     for opt in _optimizers.values():
         for p in opt.params:

@@ -2,6 +2,7 @@
 reference's gan_inference_* / gmgan_inference_* / ssgan_inference_* scripts; their train loop is
 gmgan_inference_cifar10.py:470-549: alternate one generator step and CRITIC_ITERS critic steps on fresh minibatches, log the
 costs through tflib.plot, dump sample grids and a checkpoint every so often)."""
+import contextlib
 import itertools
 import os
 import time
@@ -214,6 +215,62 @@ def rec_due(S, it):
     return bool(n and it % n == n - 1)
 
 
+# an exponential moving average of the generator-side weights (engine.Trainer's ema_decay), kept on the device inside the steps and used by
+# the passes only: off unless asked for; which weights the passes score is a second switch
+EMA_EVAL_MODES = ('live', 'ema', 'both')
+
+
+def ema_settings(script):
+    """{'EMA_DECAY': d, 'EMA_EVAL': 'live' | 'ema' | 'both'} for the ten scripts when $GGAN_EMA_DECAY = d, a float in [0, 1), is set
+    ($GGAN_EMA_EVAL: which weights the evaluation passes score, default 'live'), {} otherwise.  $GGAN_EMA_EVAL without a decay is an
+    error: there would be nothing to score."""
+    name = os.path.splitext(os.path.basename(script))[0]
+    decay, which = os.environ.get('GGAN_EMA_DECAY'), os.environ.get('GGAN_EMA_EVAL')
+    if name not in _IMAGE_SCRIPTS and name not in _SEQUENCE_SCRIPTS:
+        return {}
+    if not decay:
+        if which:
+            raise ValueError('GGAN_EMA_EVAL=%r needs GGAN_EMA_DECAY: no average is kept without a decay' % which)
+        return {}
+    return ema_check({'EMA_DECAY': decay, 'EMA_EVAL': which or 'live'})
+
+
+def ema_check(S):
+    """the EMA_* keys of a settings block, validated -> {'EMA_DECAY': float, 'EMA_EVAL': mode}, or {} when the block has no EMA_DECAY"""
+    decay, which = S.get('EMA_DECAY'), S.get('EMA_EVAL')
+    if decay is None or decay == '':
+        if which and which != 'live':
+            raise ValueError('EMA_EVAL=%r needs EMA_DECAY: no average is kept without a decay' % (which,))
+        return {}
+    try:
+        d = float(decay)
+    except (TypeError, ValueError):
+        raise ValueError('EMA_DECAY=%r: a float in [0, 1)' % (decay,))
+    if not 0.0 <= d < 1.0:
+        raise ValueError('EMA_DECAY=%r: a float in [0, 1)' % (decay,))
+    which = which or 'live'
+    if which not in EMA_EVAL_MODES:
+        raise ValueError('EMA_EVAL=%r: one of %s' % (which, ' / '.join(EMA_EVAL_MODES)))
+    return {'EMA_DECAY': d, 'EMA_EVAL': which}
+
+
+def ema_passes(S):
+    """the weights the due passes run on, in order: ('live',), ('ema',) or ('live', 'ema')"""
+    which = ema_check(S).get('EMA_EVAL', 'live')
+    return ('live', 'ema') if which == 'both' else (which,)
+
+
+@contextlib.contextmanager
+def _on_weights(ev, weights):
+    """the evaluator's passes inside the block score `weights`; 'ema': ONE visit of the averaged weights for all of them"""
+    was, ev.weights = ev.weights, weights
+    try:
+        with ev._visit():
+            yield
+    finally:
+        ev.weights = was
+
+
 def rec_sequences(S, model, device):
     """the dev minibatches the state-space scripts' reconstruction pass scores: the leading ones of the loader's dev split, as many as
     REC_MAX_ROWS frames take (at least one) -- eval_sets keeps the first alone, which is all the video passes use; without the dataset,
@@ -387,12 +444,16 @@ def config(S):
 
 
 def train(S, cfg, model=None, out_dir=None):
-    """S: dict of the script's UPPERCASE settings (needs DATASET, BATCH_SIZE, ITERS; optional SAVE_EVERY, LOG_EVERY, SEED)."""
+    """S: dict of the script's UPPERCASE settings (needs DATASET, BATCH_SIZE, ITERS; optional SAVE_EVERY, LOG_EVERY, SEED;
+    EMA_DECAY keeps an average of the generator-side weights and EMA_EVAL = 'live' | 'ema' | 'both' says which weights the passes score)."""
     lib.print_model_settings_dict(S)
     device = lib.get_device()
     np.random.seed(S.get('SEED', 0))
     torch.manual_seed(S.get('SEED', 0))
-    tr = Trainer(cfg, device=device, graph=S.get('HIP_GRAPH', True), model=model, sync_bn=S.get('SYNC_BN', False))
+    ema = ema_check(S)
+    tr = Trainer(cfg, device=device, graph=S.get('HIP_GRAPH', True), model=model, sync_bn=S.get('SYNC_BN', False),
+                 ema_decay=ema.get('EMA_DECAY'))
+    passes = ema_passes(S)
     batches, source = _batches(S, tr.model, device)
     print('[run] data: %s' % source)
     out_dir = out_dir or S.get('OUT_DIR')
@@ -482,32 +543,48 @@ def train(S, cfg, model=None, out_dir=None):
             lib.plot.flush(out_dir, os.path.join(out_dir, 'logfile.txt') if out_dir else None)
         due = eval_due(plan, it) if evaluator is not None else ()
         if due:
-            eval_ms += _evaluate(evaluator, due, ev_dev, ev_test, it, out_dir, device, tr)
+            for w in passes:
+                with _on_weights(evaluator, w):
+                    eval_ms += _evaluate(evaluator, due, ev_dev, ev_test, it, out_dir, device, tr)
             lib.plot.flush(out_dir, os.path.join(out_dir, 'logfile.txt') if out_dir else None)
         if manifold_due(manifold, it, S['ITERS']):
-            eval_ms += _manifold(m_eval, m_dev, it, out_dir, device)
+            for w in passes:
+                with _on_weights(m_eval, w):
+                    eval_ms += _manifold(m_eval, m_dev, it, out_dir, device)
         if mmd_eval is not None and (mmd_due(S, it) or prdc_due(S, it) or (knn_on and knn_due(S, it)) or parzen_due(S, it) or rec_due(S, it)):
-            eval_ms += _set_scores(mmd_eval, mmd_dev, device, mmd_due(S, it), prdc_due(S, it), knn_on and knn_due(S, it), parzen_due(S, it),
-                                   rec_due(S, it))
+            for w in passes:
+                with _on_weights(mmd_eval, w):
+                    eval_ms += _set_scores(mmd_eval, mmd_dev, device, mmd_due(S, it), prdc_due(S, it), knn_on and knn_due(S, it),
+                                           parzen_due(S, it), rec_due(S, it))
             lib.plot.flush(out_dir, os.path.join(out_dir, 'logfile.txt') if out_dir else None)
         if rec_eval is not None and rec_due(S, it):
-            eval_ms += _rec_sequences(rec_eval, rec_dev, device)
+            for w in passes:
+                with _on_weights(rec_eval, w):
+                    eval_ms += _rec_sequences(rec_eval, rec_dev, device)
             lib.plot.flush(out_dir, os.path.join(out_dir, 'logfile.txt') if out_dir else None)
         lib.plot.tick()
         if out_dir and S.get('SAVE_EVERY') and (it + 1) % S['SAVE_EVERY'] == 0:
             checkpoint.save(os.path.join(out_dir, 'params_%d.npz' % (it + 1)), tr, data_source=source)
-            with torch.no_grad():
-                nets = tr.model.forward_nets(tr.feed)
-                # (the critic-free code-space modes never build Generator(p_z) in a step: samples are drawn here)
-                fx = nets['fake_x'] if 'fake_x' in nets else tr.model.Generator(nets['p_z'])
-            fx = fx.detach().float().cpu().numpy()
-            side = getattr(cfg, 'S', 64)
-            fx = fx.reshape(-1, getattr(cfg, 'C', 1), side, side)[:64]
-            lo = 0.0 if getattr(cfg, 'out_act', 'tanh') == 'sigmoid' else -1.0
-            lib.save_images.save_images(np.clip((fx - lo) / (1.0 - lo), 0, 1), os.path.join(out_dir, 'samples_%d.png' % (it + 1)))
+            _save_samples(tr, cfg, os.path.join(out_dir, 'samples_%d.png' % (it + 1)))
+            if tr.has_ema():       # the same noise through the averaged Generator, beside it
+                with tr.ema_weights():
+                    _save_samples(tr, cfg, os.path.join(out_dir, 'samples_%d_ema.png' % (it + 1)))
     tr.flush()
     torch.cuda.synchronize()
     return tr
+
+
+def _save_samples(tr, cfg, path):
+    """the sample grid run.train writes with every checkpoint: the Generator on the noise of the last step, still in the Trainer's feed"""
+    with torch.no_grad():
+        nets = tr.model.forward_nets(tr.feed)
+        # (the critic-free code-space modes never build Generator(p_z) in a step: samples are drawn here)
+        fx = nets['fake_x'] if 'fake_x' in nets else tr.model.Generator(nets['p_z'])
+    fx = fx.detach().float().cpu().numpy()
+    side = getattr(cfg, 'S', 64)
+    fx = fx.reshape(-1, getattr(cfg, 'C', 1), side, side)[:64]
+    lo = 0.0 if getattr(cfg, 'out_act', 'tanh') == 'sigmoid' else -1.0
+    lib.save_images.save_images(np.clip((fx - lo) / (1.0 - lo), 0, 1), path)
 
 
 def _evaluate(ev, due, dev, test, it, out_dir, device, tr=None):
@@ -517,10 +594,11 @@ def _evaluate(ev, due, dev, test, it, out_dir, device, tr=None):
         torch.cuda.synchronize(device)          # (the training work queued so far is not the passes' time)
     t0 = time.time()
     if 'DEV_EVERY' in due:
-        for k, v in ev.dev_costs(dev).items():
+        for k, v in ev.tag(ev.dev_costs(dev)).items():
             lib.plot.plot(k, v)
     if 'ACCURACY_EVERY' in due:
-        lib.plot.plot('testing accuracy', ev.cluster_accuracy(test))
+        for k, v in ev.tag({'testing accuracy': ev.cluster_accuracy(test)}).items():
+            lib.plot.plot(k, v)
     if 'SAMPLE_EVERY' in due and out_dir:
         if isinstance(ev, SequenceEvaluator):
             # generate_video(iteration, _data): the minibatch of the last critic step, still in the Trainer's feed buffer (read only)
@@ -549,7 +627,7 @@ def _set_scores(ev, dev, device, mmd, prdc, knn=False, parzen=False, rec=False):
     if device.type == 'cuda':
         torch.cuda.synchronize(device)
     t0 = time.time()
-    for k, v in ev.set_scores(dev, mmd=mmd, prdc=prdc, knn=knn, parzen=parzen, rec=rec).items():
+    for k, v in ev.tag(ev.set_scores(dev, mmd=mmd, prdc=prdc, knn=knn, parzen=parzen, rec=rec)).items():
         lib.plot.plot(k, v)
     if device.type == 'cuda':
         torch.cuda.synchronize(device)
@@ -561,7 +639,7 @@ def _rec_sequences(ev, dev, device):
     if device.type == 'cuda':
         torch.cuda.synchronize(device)
     t0 = time.time()
-    for k, v in ev.rec_scores(dev).items():
+    for k, v in ev.tag(ev.rec_scores(dev)).items():
         lib.plot.plot(k, v)
     if device.type == 'cuda':
         torch.cuda.synchronize(device)

@@ -657,6 +657,16 @@ int ggan_rmsprop_step(float* theta, const float* g, float* ms, size_t n, float l
  * ggan_pack_parts launch of the same optimizer step (its `bump` argument) -- no separate ggan_adam_advance launch. */
 int ggan_adam_step_counted(float* theta, const float* g, float* m, float* v, size_t n, const int32_t* step, float lr,
                            float beta1, float beta2, float eps, float grad_scale, ggan_stream_t stream);
+/* Exponential moving average of a flat weight buffer, for sampling and evaluation only.  NO call site in the reference (it
+ * keeps no average); the semantics are those TensorFlow 1 documents for tf.train.ExponentialMovingAverage(decay, num_updates):
+ *     d_t = min(decay, (1 + t) / (10 + t));   shadow -= (1 - d_t) * (shadow - theta)
+ * in fp32, in place.  t = step[0] is read on the device and must already hold the ordinal (1, 2, ...) of the update just applied:
+ * its state after ggan_adam_step_counted, after ggan_pack_adam, and after the pack launch of an RMSProp step.  theta is only
+ * read.  decay in [0, 1); shadow and theta are distinct 16-byte aligned buffers of n floats. */
+int ggan_ema_step(float* shadow, const float* theta, size_t n, const int32_t* step, float decay, ggan_stream_t stream);
+/* Exchanges the contents of two non-overlapping 16-byte aligned fp32 buffers in one pass (no scratch): how the averaged weights
+ * visit the live parameter storage for an evaluation and leave it again, bit for bit. */
+int ggan_swap(float* a, float* b, size_t n, ggan_stream_t stream);
 /* gather up to GGAN_PACK_MAX scattered tensors into one flat buffer (gradient bucket for RCCL). */
 #define GGAN_PACK_MAX 64
 int ggan_pack(const float* const* srcs, const size_t* sizes, const size_t* offsets, int count,

@@ -18,6 +18,7 @@ SETTINGS.update(run.prdc_settings(__file__))     # dev precision / recall / dens
 SETTINGS.update(run.knn_settings(__file__))      # dev knn accuracy z / x every $GGAN_KNN_EVERY iterations (off when unset; needs a labelled dev set)
 SETTINGS.update(run.parzen_settings(__file__))   # dev parzen ll / se / sigma x every $GGAN_PARZEN_EVERY iterations (off when unset)
 SETTINGS.update(run.rec_settings(__file__))      # dev rec mse / psnr / ssim / ssim se x every $GGAN_REC_EVERY iterations (off when unset)
+SETTINGS.update(run.ema_settings(__file__))      # $GGAN_EMA_DECAY: average the generator-side weights; $GGAN_EMA_EVAL = live | ema | both: which the passes score
 if len(sys.argv) > 1:
     SETTINGS['ITERS'] = int(sys.argv[1])
 globals().update(SETTINGS)          # BATCH_SIZE, DIM, DIM_LATENT, CRITIC_ITERS, ... as module constants, as in the reference
