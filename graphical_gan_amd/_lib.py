@@ -139,6 +139,7 @@ SIGNATURES = {
     'ggan_axpby': (_I, [_P, _P, _P, _Z, _F, _F, _F, _P]),
     'ggan_mix_mean': (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     'ggan_row_lerp': (_I, [_P, _P, _P, _P, _I, _I, _P]),
+    'ggan_head_seed_fwd': (_I, [_I, _I, _P, _P, _P, _F, _P, _P]),
     'ggan_bce_logits_fwd': (_I, [_P, _F, _F, _P, _I, _I, _P]),
     'ggan_bce_logits_bwd': (_I, [_P, _F, _F, _P, _P, _I, _P]),
     'ggan_bce_logits_multi_fwd': (_I, [C.POINTER(_P), C.POINTER(_F), C.POINTER(_F), C.POINTER(_I), _I, _P, _P]),

@@ -23,7 +23,7 @@ from .conv import (  # noqa: F401
     DEBUG_POISON_CHECK, PendingCast, ConvFwd, _fused_conv_backward, ConvDgrad, ConvDgradMasked, ConvWgrad, ChanSum, TALL_ROWS,
     ColSum)
 from .linear import (  # noqa: F401
-    Gemm, _fused_linear_backward, Gemm2, _CONSTS, cached_const, Gemm2Dgrad, _HEAD_HINT, head_bce_hint, CriticHead, DynScan,
+    Gemm, _fused_linear_backward, Gemm2, _CONSTS, cached_const, Gemm2Dgrad, HeadInputGrad, _HEAD_HINT, head_bce_hint, CriticHead, DynScan,
     gemm_colsum_, linear)
 from .norm import BatchNormTrain, BatchNormGroupedTrain, BatchNormBwd, LinearBatchNormRows, _all_gather_rows, SyncBatchNormTrain  # noqa: F401
 from .rows import (  # noqa: F401

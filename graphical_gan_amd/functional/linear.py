@@ -221,6 +221,69 @@ class Gemm2Dgrad(Function):
         return dg, dw, None
 
 
+@_skip_undefined
+class HeadInputGrad(Function):
+    """d_a1[M, K1] = d sum(D) / d a1 of the critic tail D = Linear(H -> 1)(lrelu(Linear([a1 | a2] -> H))): what the gradient-penalty
+    pass reads of the tail (its value on the interpolates is read by nobody), differentiable once more -- the penalty's gradient
+    reaches w and w_out through it.  Forward: the hidden layer by Gemm2's call, gpre = w_out[j] * lrelu'(h) in one pointwise launch
+    (ggan_head_seed_fwd: the plain composition forms it with a K = 1 product and an act_bwd pass, after a 1-wide product for the
+    logits), then Gemm2Dgrad's call -- the same kernels on the same operands, so the same bits as the composition.  Backward for an
+    incoming hh1: t = [hh1 | 0] @ w and d_w = [hh1 | 0]^T gpre by Gemm2Dgrad.backward's calls, d_wout = (t * lrelu'(h))^T ones by the
+    composition's act_bwd and N = 1 product -- every gradient keeps the composition's bits.  a1, a2 and b get no gradient
+    (LeakyReLU'' = 0).  Parameter operands are skipped under data_grad_only as in Gemm2 / Gemm2Dgrad.  No third derivative."""
+
+    @staticmethod
+    def forward(ctx, a1, a2, w, b, w_out, alpha):
+        a1, a2, w, w_out = _c(a1), _c(a2), _c(w), _c(w_out)
+        M, K1, K2 = a1.shape[0], a1.shape[1], a2.shape[1]
+        K, H = w.shape
+        assert K == K1 + K2 and a2.shape[0] == M and w_out.numel() == H, (a1.shape, a2.shape, w.shape, w_out.shape)
+        dev = a1.device
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        L, ws = _L(), workspace(dev)
+        h, gpre, d_a1, d_a2 = new(M, H), new(M, H), new(M, K1), new(M, K2)
+        check(L.ggan_gemm_split(0, 0, M, H, K, _p(a1), _p(a2), K1, _p(w), _p(_c(b)) if b is not None else _p(None), _p(h), _p(None), 0,
+                                _p(None), _lib.ACT_LRELU, float(alpha), _p(ws), ws.numel(), _stream()), 'ggan_gemm_split')
+        check(L.ggan_head_seed_fwd(M, H, _p(None), _p(h), _p(w_out), float(alpha), _p(gpre), _stream()), 'ggan_head_seed_fwd')
+        # (the a2 half of the product leaves into scratch, as in the composition: nothing of the penalty pass reads it)
+        check(L.ggan_gemm_split(0, 1, M, K, H, _p(gpre), _p(None), 0, _p(w), _p(None), _p(d_a1), _p(d_a2), K1, _p(None), ACT_NONE, 0.0,
+                                _p(ws), ws.numel(), _stream()), 'ggan_gemm_split')
+        ctx.alpha, ctx.K1 = float(alpha), K1
+        ctx.w_param, ctx.wout_param = _is_param(w), _is_param(w_out)
+        ctx.save_for_backward(h, gpre, w, w_out)
+        return d_a1
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, hh1):
+        h, gpre, w, w_out = ctx.saved_tensors
+        hh1 = _c(hh1)
+        M, H = h.shape
+        K, K1 = w.shape[0], ctx.K1
+        dev = h.device
+        zero = cached_const(0.0, (M, K - K1), dev)               # (the a2 half of d_a carried no gradient: a zero operand)
+        L, ws = _L(), workspace(dev)
+        d_w = d_wout = None
+        if ctx.needs_input_grad[4] and not (_DATA_ONLY[0] and ctx.wout_param):
+            t = torch.empty((M, H), dtype=torch.float32, device=dev)
+            check(L.ggan_gemm_split(0, 0, M, H, K, _p(hh1), _p(zero), K1, _p(w), _p(None), _p(t), _p(None), 0, _p(None), ACT_NONE, 0.0,
+                                    _p(ws), ws.numel(), _stream()), 'ggan_gemm_split')
+        if ctx.needs_input_grad[2] and not (_DATA_ONLY[0] and ctx.w_param):
+            d_w = torch.empty((K, H), dtype=torch.float32, device=dev)
+            check(L.ggan_gemm_split(1, 0, K, H, M, _p(hh1), _p(zero), K1, _p(gpre), _p(None), _p(d_w), _p(None), 0, _p(None), ACT_NONE, 0.0,
+                                    _p(ws), ws.numel(), _stream()), 'ggan_gemm_split')
+        if ctx.needs_input_grad[4] and not (_DATA_ONLY[0] and ctx.wout_param):
+            # d_wout = (t * lrelu'(h))^T ones by the composition's own two calls (ActBwd, then Gemm.backward's g^T a): the sum keeps its
+            # order and with it its bits -- a column sum in another order moves the weights of a long run (profiles/r07_notes.md)
+            mt = torch.empty_like(t)
+            check(L.ggan_act_bwd(_p(t), _p(h), _p(mt), t.numel(), _lib.ACT_LRELU, ctx.alpha, _stream()), 'ggan_act_bwd')
+            d_wout = torch.empty((H, 1), dtype=torch.float32, device=dev)
+            check(L.ggan_gemm(1, 0, H, 1, M, _p(mt), _p(cached_const(1.0, (M, 1), dev)), _p(None), _p(d_wout), ACT_NONE, 0.0, _p(ws),
+                              ws.numel(), _stream()), 'ggan_gemm')
+            d_wout = d_wout.view(w_out.shape)
+        return None, None, d_w, None, d_wout, None
+
+
 _HEAD_HINT = _threading.local()      # .terms: the cost hint in force on this thread (head_bce_hint)
 
 

@@ -298,6 +298,43 @@ class GraphicalGAN(object):
         """grad_rows: only the first grad_rows images of x carry a gradient (generator steps: [fake; real]); twice: the result
         will be differentiated twice (gradient-penalty pass): plain layer composition instead of the fused critic tail"""
         c = self.cfg
+        out, z_out = self._critic_stack(x, z, grad_rows, before_z, z_out)
+        if c.critic_deep:            # gan_inference_mnist.py:236-248: z1 -> '2' | concat -> zx1 -> zx2 -> Output
+            z_out = self._lin('Discriminator.2', 512, 512, z_out, LRELU)
+            out = self._lin('Discriminator.zx1', c.flat + 512, 512, (out, z_out), LRELU)
+            if c.fuse:
+                return lib.ops.linear.LinearLReLULinear('Discriminator.zx2', 512, 512, 'Discriminator.Output', out, differentiable=twice)
+            out = self._lin('Discriminator.zx2', 512, 512, out, LRELU)
+            return lib.ops.linear.Linear('Discriminator.Output', 512, 1, out).reshape(-1)
+        if c.fuse:
+            # Linear on concat([out, z_out], 1) + LeakyReLU + the 512 -> 1 Output layer as one op
+            return lib.ops.linear.LinearLReLULinear('Discriminator.zx1', c.flat + 512, 512, 'Discriminator.Output', (out, z_out),
+                                                    differentiable=twice)
+        out = self._lin('Discriminator.zx1', c.flat + 512, 512, (out, z_out), LRELU)     # Linear on concat([out, z_out], 1)
+        out = lib.ops.linear.Linear('Discriminator.Output', 512, 1, out)
+        return out.reshape(-1)
+
+    def penalty_seed_ok(self):
+        """the penalty pass may take DiscriminatorInputGrad: the joint critic's fused tail (not the MNIST critic's deeper one), whose conv
+        features split the hidden layer's operand on a tile boundary (functional.Gemm2.usable); GGAN_NO_PENALTY_SEED=1 keeps the plain
+        composition (the A/B switch, and the other side of the equivalence test)"""
+        c = self.cfg
+        return c.fuse and not c.critic_deep and c.flat % 64 == 0 and not os.environ.get('GGAN_NO_PENALTY_SEED')
+
+    def DiscriminatorInputGrad(self, x, z):
+        """Discriminator(x, z, twice=True) up to the conv features a1, and d sum(logits) / d a1 in its place (functional.HeadInputGrad: the
+        tail Linear -> LeakyReLU -> Linear differentiated w.r.t. its input in three launches): what the gradient-penalty pass needs of the
+        critic -- the logits themselves are read by nobody (gan_inference_cifar10.py:362).  Same conv and z1 launches in the same order as
+        Discriminator's; same registry keys and initial-value draws as the tail's two Linear calls.  Returns (a1, d_a1)."""
+        c = self.cfg
+        a1, z_out = self._critic_stack(x, z)
+        w, b = lib.ops.linear.linear_params('Discriminator.zx1', c.flat + 512, 512)
+        w_out, _ = lib.ops.linear.linear_params('Discriminator.Output', 512, 1)
+        return a1, F.HeadInputGrad.apply(a1, z_out, w, b, w_out, 0.2)
+
+    def _critic_stack(self, x, z, grad_rows=None, before_z=None, z_out=None):
+        """the critic's conv stack on x and its first layer on z: (features [rows, flat], z_out [rows, 512])"""
+        c = self.cfg
         out = x.reshape(-1, c.C, c.S, c.S)
         ch = c.C
         for i in range(c.nl):
@@ -318,20 +355,7 @@ class GraphicalGAN(object):
             before_z()               # (forward_nets: z's second half may still be in flight on the other stream)
         if z_out is None:            # (else: _critic already ran the z path on the second stream)
             z_out = self._lin('Discriminator.z1', c.dim_latent, 512, z, LRELU)
-        if c.critic_deep:            # gan_inference_mnist.py:236-248: z1 -> '2' | concat -> zx1 -> zx2 -> Output
-            z_out = self._lin('Discriminator.2', 512, 512, z_out, LRELU)
-            out = self._lin('Discriminator.zx1', c.flat + 512, 512, (out, z_out), LRELU)
-            if c.fuse:
-                return lib.ops.linear.LinearLReLULinear('Discriminator.zx2', 512, 512, 'Discriminator.Output', out, differentiable=twice)
-            out = self._lin('Discriminator.zx2', 512, 512, out, LRELU)
-            return lib.ops.linear.Linear('Discriminator.Output', 512, 1, out).reshape(-1)
-        if c.fuse:
-            # Linear on concat([out, z_out], 1) + LeakyReLU + the 512 -> 1 Output layer as one op
-            return lib.ops.linear.LinearLReLULinear('Discriminator.zx1', c.flat + 512, 512, 'Discriminator.Output', (out, z_out),
-                                                    differentiable=twice)
-        out = self._lin('Discriminator.zx1', c.flat + 512, 512, (out, z_out), LRELU)     # Linear on concat([out, z_out], 1)
-        out = lib.ops.linear.Linear('Discriminator.Output', 512, 1, out)
-        return out.reshape(-1)
+        return out, z_out
 
     def LatentDiscriminator(self, z, noise):
         """gan_inference_cifar10.py:192-222: the vegan critic on codes; Gaussian noise (std .3 on the input, .5 after the first
@@ -685,7 +709,8 @@ class GraphicalGAN(object):
         #  gradient contributions of every weight where it packs the bucket, not with an addition launch per weight)
         with (lib.second_leaf() if batched else lib.frozen()):
             return J.gradient_penalty(lambda xx, zz: self.Discriminator(xx, zz, twice=True), real_x, fake_x.detach() if batched else fake_x,
-                                      q_z.detach() if batched else q_z, p_z.detach() if batched else p_z, feed['alpha'])
+                                      q_z.detach() if batched else q_z, p_z.detach() if batched else p_z, feed['alpha'],
+                                      input_grad=self.DiscriminatorInputGrad if self.penalty_seed_ok() else None)
 
     def _critic(self, batched, real_x, q_z, p_z, fake_x, onehot, q_k, detach=True):
         """critic logits of the fake and the real pair.  batched: the critic is evaluated ONCE on [fake; real] (its rows

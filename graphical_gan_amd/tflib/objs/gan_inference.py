@@ -162,15 +162,22 @@ def wali_gp(disc_fake, disc_real, gradient_penalty, gen_params, disc_params, lr=
     return gen_cost, disc_cost, TrainOp(gen_opt, gen_cost), TrainOp(disc_opt, disc_cost)
 
 
-def gradient_penalty(critic, real_x, fake_x, q_z, p_z, alpha, lam=10.):
+def gradient_penalty(critic, real_x, fake_x, q_z, p_z, alpha, lam=10., input_grad=None):
     """The wali-gp construction of gan_inference_cifar10.py:353-364 (script-level code in the reference):
     interpolate, third critic pass, x-gradient only, lam*mean((||g||-1)^2).  create_graph=True keeps the
-    backward kernels on the tape so minimize() differentiates THROUGH g (double backward)."""
+    backward kernels on the tape so minimize() differentiates THROUGH g (double backward).
+    input_grad (optional): (x_hat, z_hat) -> (a1, d_a1), the critic up to its conv features a1 and d sum(critic) / d a1 (the model's
+    DiscriminatorInputGrad) -- the x-gradient then continues from there; nothing reads the critic's value on the interpolates."""
     import torch
     x_hat = F.RowLerp.apply(real_x, fake_x, alpha)
     z_hat = F.RowLerp.apply(q_z, p_z, alpha)
     if not x_hat.requires_grad:
         x_hat.requires_grad_(True)
+    if input_grad is not None:
+        a1, d_a1 = input_grad(x_hat, z_hat)
+        with F.data_grad_only():
+            (g,) = torch.autograd.grad(a1, [x_hat], grad_outputs=d_a1, create_graph=True)
+        return F.GradPenalty.apply(g.reshape(g.shape[0], -1), float(lam))
     d_hat = critic(x_hat, z_hat)
     ones = F.cached_const(1.0, d_hat.shape, d_hat.device)      # (persistent: no fill launch per critic step)
     with F.data_grad_only():             # only d/d x_hat is asked for: the layers skip their parameter gradients

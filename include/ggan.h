@@ -638,6 +638,13 @@ int ggan_gp_penalty_bwd(const float* g, const float* slopes, const float* gpen, 
  * zero before the first call, left zero (the last workgroup forms the penalty: fixed order, deterministic). */
 int ggan_gp_penalty_fwd_grad(const float* g, float* slopes, float* pen, float* gg_unit, int32_t* arrive, int B, int D, float lam,
                              ggan_stream_t stream);
+/* The critic tail Linear([a1 | a2] -> H) -> LeakyReLU(alpha) -> Linear(H -> 1) differentiated w.r.t. its input, as the penalty pass needs it
+ * (tf.gradients(Discriminator(x_hat, z_hat), [x_hat]), gan_inference_cifar10.py:362), between the two large products:
+ * gpre[n, j] = (u ? u[n] : 1) * w_out[j] * (h[n, j] > 0 ? 1 : alpha) -- u[M] the upstream gradient of the logits (NULL: ones), h[M, H]
+ * the hidden layer (pre- or post-activation: only its sign is read).  The bits of the K = 1 product u w_out^T followed by ggan_act_bwd.
+ * Any M, H >= 1; 16-byte accesses when H is a multiple of 4 and the buffers are 16-byte aligned. */
+int ggan_head_seed_fwd(int M, int H, const float* u /* may be NULL */, const float* h, const float* w_out, float alpha, float* gpre,
+                       ggan_stream_t stream);
 
 /* ---- optimiser --------------------------------------------------------------------------------
  * tf.train.AdamOptimizer step over a flat parameter buffer (tflib/objs/gan_inference.py:108-117;
