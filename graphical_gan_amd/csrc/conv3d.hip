@@ -378,6 +378,20 @@ __global__ __launch_bounds__(256) void conv3d_igemm_k(const IgParams P) {
     }
 }
 
+// FastDiv (conv.h) is exact for n * d < 2^32 only: true when the chain n / d0, (n / d0) / d1, (.. / d1) / d2 of ig_row / ig_col stays inside
+// that contract for every n < count + pad (a divisor of 1 passes its numerator through).  The pad is kept whole down the chain, so the
+// answer for a volume also holds for every residue class of its data gradient (fewer rows and taps along every axis, the same pad)
+constexpr size_t IG_ROW_PAD = 128, IG_COL_PAD = 64;       // rows / columns of the last tile and step past M / K (the largest tile side)
+bool fd_chain_ok(size_t count, size_t pad, int d0, int d1, int d2) {
+    const int d[3] = {d0, d1, d2};
+    for (int i = 0; i < 3; ++i) {
+        if (d[i] <= 1) continue;
+        if ((count + pad) * (size_t)d[i] >= (1ull << 32)) return false;
+        count = (count + d[i] - 1) / d[i];
+    }
+    return true;
+}
+
 // which products the implicit kernels cover (the rest stays on im2col / col2im + GEMM)
 bool ig_ok(const C3& g, int kind) {
     const size_t xb = (size_t)g.N * g.L * g.H * g.W * g.Ci * 4, yb = (size_t)g.N * g.Lo * g.Ho * g.Wo * g.Co * 4;
@@ -385,8 +399,13 @@ bool ig_ok(const C3& g, int kind) {
     const size_t K = (size_t)g.kl * g.k * g.k * g.Ci;
     if (xb >= 0x7FFFFFF0ull || yb >= 0x7FFFFFF0ull || K * g.Co * 4 >= 0x7FFFFFF0ull) return false;
     if (rows >= (1u << 24) || vox >= (1u << 24) || K >= (1u << 16) || (g.Co & 3)) return false;
-    if (kind == 2) return (g.Ci & 3) == 0 && g.sl <= 2 && g.s <= 2 && g.Ci >= 16;   // (thin inputs: a 32-wide tile would idle)
-    return true;
+    if (kind == 2) {
+        if ((g.Ci & 3) || g.sl > 2 || g.s > 2 || g.Ci < 16) return false;            // (thin inputs: a 32-wide tile would idle)
+        // every residue class has at most the rows and taps of class (0, 0, 0) along each axis: Lo x Ho x Wo rows, ceil(k / stride) taps
+        const int tl = cdiv(g.kl, g.sl), t = cdiv(g.k, g.s);
+        return fd_chain_ok(rows, IG_ROW_PAD, g.Wo, g.Ho, g.Lo) && fd_chain_ok((size_t)tl * t * t * g.Co, IG_COL_PAD, g.Co, t, t);
+    }
+    return fd_chain_ok(rows, IG_ROW_PAD, g.Wo, g.Ho, g.Lo) && fd_chain_ok(K, IG_COL_PAD, g.Ci, g.k, g.k);
 }
 
 void ig_common(IgParams& P, const C3& g) {
@@ -406,18 +425,27 @@ void ig_fwd_class(IgParams& P, const C3& g) {      // rows = output voxels, asce
     Q.d_TW = make_fastdiv(Q.TW); Q.d_TH = make_fastdiv(Q.TH);
 }
 
+// forward (wide: more than 32 result columns -> 64x64 tiles, else 128x32) and filter gradient (64x64 only); av4: Ci % 4 == 0
 template <int KIND>
 int ig_launch(const IgParams& P, dim3 grid, bool wide, bool av4, hipStream_t s, double fl) {
+    static_assert(KIND == 0 || KIND == 1, "the data gradient has ig_launch_dgrad");
     if constexpr (KIND == 1) {
         if (av4) { GGAN_LAUNCH("conv3d_igemm_k<1, 2, 2, true>", fl, 0, (conv3d_igemm_k<1, 2, 2, true>), grid, dim3(256), 0, s, P); }
         else { GGAN_LAUNCH("conv3d_igemm_k<1, 2, 2, false>", fl, 0, (conv3d_igemm_k<1, 2, 2, false>), grid, dim3(256), 0, s, P); }
     } else if (wide) {
-        if (av4) { GGAN_LAUNCH((KIND == 0 ? "conv3d_igemm_k<0, 2, 2, true>" : "conv3d_igemm_k<2, 2, 2, true>"), fl, 0, (conv3d_igemm_k<KIND, 2, 2, true>), grid, dim3(256), 0, s, P); }
-        else { GGAN_LAUNCH((KIND == 0 ? "conv3d_igemm_k<0, 2, 2, false>" : "conv3d_igemm_k<2, 2, 2, false>"), fl, 0, (conv3d_igemm_k<KIND, 2, 2, false>), grid, dim3(256), 0, s, P); }
+        if (av4) { GGAN_LAUNCH("conv3d_igemm_k<0, 2, 2, true>", fl, 0, (conv3d_igemm_k<0, 2, 2, true>), grid, dim3(256), 0, s, P); }
+        else { GGAN_LAUNCH("conv3d_igemm_k<0, 2, 2, false>", fl, 0, (conv3d_igemm_k<0, 2, 2, false>), grid, dim3(256), 0, s, P); }
     } else {
-        if (av4) { GGAN_LAUNCH((KIND == 0 ? "conv3d_igemm_k<0, 4, 1, true>" : "conv3d_igemm_k<2, 4, 1, true>"), fl, 0, (conv3d_igemm_k<KIND, 4, 1, true>), grid, dim3(256), 0, s, P); }
-        else { GGAN_LAUNCH((KIND == 0 ? "conv3d_igemm_k<0, 4, 1, false>" : "conv3d_igemm_k<2, 4, 1, false>"), fl, 0, (conv3d_igemm_k<KIND, 4, 1, false>), grid, dim3(256), 0, s, P); }
+        if (av4) { GGAN_LAUNCH("conv3d_igemm_k<0, 4, 1, true>", fl, 0, (conv3d_igemm_k<0, 4, 1, true>), grid, dim3(256), 0, s, P); }
+        else { GGAN_LAUNCH("conv3d_igemm_k<0, 4, 1, false>", fl, 0, (conv3d_igemm_k<0, 4, 1, false>), grid, dim3(256), 0, s, P); }
     }
+    return 0;
+}
+
+// data gradient: the gathered tensor is gy and ig_ok admits Co % 4 == 0 only, so its units are always 16 bytes (no AV4 = false instance)
+int ig_launch_dgrad(const IgParams& P, dim3 grid, bool wide, hipStream_t s, double fl) {
+    if (wide) { GGAN_LAUNCH("conv3d_igemm_k<2, 2, 2, true>", fl, 0, (conv3d_igemm_k<2, 2, 2, true>), grid, dim3(256), 0, s, P); }
+    else { GGAN_LAUNCH("conv3d_igemm_k<2, 4, 1, true>", fl, 0, (conv3d_igemm_k<2, 4, 1, true>), grid, dim3(256), 0, s, P); }
     return 0;
 }
 
@@ -452,10 +480,10 @@ int ggan_im2col3d(const int* dims10, const float* x, float* col, ggan_stream_t s
     const size_t n = (size_t)g.N * g.Lo * g.Ho * g.Wo * g.kl * g.k * g.k * g.Ci;
     const bool v4 = (g.Ci & 3) == 0 && (((uintptr_t)x | (uintptr_t)col) & 15) == 0, i32 = n < 0xF0000000ull;
     hipStream_t s = (hipStream_t)stream;
-    if (v4 && i32) { GGAN_LAUNCH("im2col3d", 0, 8.0 * n, (im2col3d_k<uint32_t, 4>), dim3(blocks(n / 4)), dim3(256), 0, s, g, x, col); }
-    else if (v4) { GGAN_LAUNCH("im2col3d", 0, 8.0 * n, (im2col3d_k<size_t, 4>), dim3(blocks(n / 4)), dim3(256), 0, s, g, x, col); }
-    else if (i32) { GGAN_LAUNCH("im2col3d", 0, 8.0 * n, (im2col3d_k<uint32_t, 1>), dim3(blocks(n)), dim3(256), 0, s, g, x, col); }
-    else { GGAN_LAUNCH("im2col3d", 0, 8.0 * n, (im2col3d_k<size_t, 1>), dim3(blocks(n)), dim3(256), 0, s, g, x, col); }
+    if (v4 && i32) { GGAN_LAUNCH("im2col3d_k<uint32_t, 4>", 0, 8.0 * n, (im2col3d_k<uint32_t, 4>), dim3(blocks(n / 4)), dim3(256), 0, s, g, x, col); }
+    else if (v4) { GGAN_LAUNCH("im2col3d_k<size_t, 4>", 0, 8.0 * n, (im2col3d_k<size_t, 4>), dim3(blocks(n / 4)), dim3(256), 0, s, g, x, col); }
+    else if (i32) { GGAN_LAUNCH("im2col3d_k<uint32_t, 1>", 0, 8.0 * n, (im2col3d_k<uint32_t, 1>), dim3(blocks(n)), dim3(256), 0, s, g, x, col); }
+    else { GGAN_LAUNCH("im2col3d_k<size_t, 1>", 0, 8.0 * n, (im2col3d_k<size_t, 1>), dim3(blocks(n)), dim3(256), 0, s, g, x, col); }
     return 0;
 }
 
@@ -573,7 +601,7 @@ int ggan_conv3d_dgrad(const int* dims10, const float* gy, const float* w, float*
     const bool wide = g.Ci > 32;
     const int BM = wide ? 64 : 128, BN = wide ? 64 : 32;
     P.kps = 1 << 30;
-    return ig_launch<2>(P, dim3(cdiv(max_m, BM), cdiv(g.Ci, BN), nc), wide, true, s, fl);
+    return ig_launch_dgrad(P, dim3(cdiv(max_m, BM), cdiv(g.Ci, BN), nc), wide, s, fl);
 }
 
 int ggan_col2im3d(const int* dims10, const float* col, float* gx, ggan_stream_t stream) {
@@ -583,10 +611,10 @@ int ggan_col2im3d(const int* dims10, const float* col, float* gx, ggan_stream_t 
     const double bytes = 4.0 * n * (1 + (g.kl / g.sl + 1) * (g.k / g.s + 1) * (g.k / g.s + 1));
     const bool v4 = (g.Ci & 3) == 0 && (((uintptr_t)gx | (uintptr_t)col) & 15) == 0, i32 = n < 0xF0000000ull;
     hipStream_t s = (hipStream_t)stream;
-    if (v4 && i32) { GGAN_LAUNCH("col2im3d", 0, bytes, (col2im3d_k<uint32_t, 4>), dim3(blocks(n / 4)), dim3(256), 0, s, g, col, gx); }
-    else if (v4) { GGAN_LAUNCH("col2im3d", 0, bytes, (col2im3d_k<size_t, 4>), dim3(blocks(n / 4)), dim3(256), 0, s, g, col, gx); }
-    else if (i32) { GGAN_LAUNCH("col2im3d", 0, bytes, (col2im3d_k<uint32_t, 1>), dim3(blocks(n)), dim3(256), 0, s, g, col, gx); }
-    else { GGAN_LAUNCH("col2im3d", 0, bytes, (col2im3d_k<size_t, 1>), dim3(blocks(n)), dim3(256), 0, s, g, col, gx); }
+    if (v4 && i32) { GGAN_LAUNCH("col2im3d_k<uint32_t, 4>", 0, bytes, (col2im3d_k<uint32_t, 4>), dim3(blocks(n / 4)), dim3(256), 0, s, g, col, gx); }
+    else if (v4) { GGAN_LAUNCH("col2im3d_k<size_t, 4>", 0, bytes, (col2im3d_k<size_t, 4>), dim3(blocks(n / 4)), dim3(256), 0, s, g, col, gx); }
+    else if (i32) { GGAN_LAUNCH("col2im3d_k<uint32_t, 1>", 0, bytes, (col2im3d_k<uint32_t, 1>), dim3(blocks(n)), dim3(256), 0, s, g, col, gx); }
+    else { GGAN_LAUNCH("col2im3d_k<size_t, 1>", 0, bytes, (col2im3d_k<size_t, 1>), dim3(blocks(n)), dim3(256), 0, s, g, col, gx); }
     return 0;
 }
 

@@ -386,7 +386,8 @@ int ggan_col2im3d(const int* dims10, const float* col, float* gx, ggan_stream_t 
  *   ggan_conv3d_wgrad  gw = d/dw  for an upstream gradient gy [N,Lo,Ho,Wo,Co] (already multiplied by act'(y))
  *   ggan_conv3d_dgrad  gx = d/dx  (one product per residue class of the input voxels, all classes in one launch)
  * ggan_conv3d_igemm_ok(dims10, kind) (kind 0 fwd, 1 filter grad, 2 data grad) returns 1 when the geometry is covered (Co % 4 == 0,
- * 32-bit sizes; data grad: Ci % 4 == 0, Ci >= 16, strides <= 2); the callers keep ggan_im2col3d / ggan_col2im3d + ggan_gemm for the
+ * 32-bit sizes, every (row or column index) x (extent it is divided by) below 2^32 -- a volume 4096 wide with more than 256 output
+ * rows of that width is not; data grad: Ci % 4 == 0, Ci >= 16, strides <= 2); the callers keep ggan_im2col3d / ggan_col2im3d + ggan_gemm for the
  * rest.  Operands 16-byte aligned; ws as for ggan_gemm (split of the reduction when the tile grid is small). */
 int ggan_conv3d_igemm_ok(const int* dims10, int kind);
 int ggan_conv3d_fwd(const int* dims10, const float* x, const float* w, const float* bias /* may be NULL */, float* y, int act,
