@@ -1835,6 +1835,8 @@ int ggan_pack_adam(const float* const* srcs, const size_t* sizes, const size_t* 
                    float grad_scale, ggan_stream_t stream) {
     GGAN_CHECK_ARG(srcs && sizes && offsets && flat && theta && m && v && step, "null pointer");
     GGAN_CHECK_ARG(count > 0 && count <= GGAN_PACK_MAX, "count out of range");
+    // (the kernel decides float4 or scalar from flat + off and the sources alone: theta, m and v must be congruent to flat)
+    GGAN_CHECK_ARG(aligned16(flat) && aligned16(theta) && aligned16(m) && aligned16(v), "buffers must be 16-byte aligned");
     PackTable t;
     size_t mx = 0, tot = 0, all = 0;
     for (int i = 0; i < count; ++i) {

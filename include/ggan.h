@@ -696,7 +696,10 @@ int ggan_pack_parts2(const float* const* srcs, const size_t* sizes, const size_t
  * workgroup uses step[0] + 1 as the update's ordinal and the last one to finish advances step[0]; `arrive` is
  * GGAN_PACK_ARRIVE_INTS int32 of device memory (arrival counters) that are zero before the call and are left zero.  Same
  * arithmetic, in the same order, as the two launches.  arrive == NULL: the launch applies PART of an update (a subset of the
- * tensors) and leaves step[0] alone -- the launch that completes the update, ordered behind it, passes the counters. */
+ * tensors) and leaves step[0] alone -- the launch that completes the update, ordered behind it, passes the counters.
+ * flat, theta, m and v must be 16-byte aligned (refused otherwise, as ggan_adam_step refuses them): the kernel picks its 16-byte
+ * accesses from flat + offset and the sources and applies them to theta, m and v at the same offset.  The project's own caller
+ * (optim.py: AdamOptimizer's g, theta, m, v) always passes whole, fresh torch allocations, which are aligned. */
 #define GGAN_PACK_ARRIVE_STRIDE 1024
 #define GGAN_PACK_ARRIVE_INTS (33 * GGAN_PACK_ARRIVE_STRIDE)
 int ggan_pack_adam(const float* const* srcs, const size_t* sizes, const size_t* offsets, const int* parts, const size_t* strides,
