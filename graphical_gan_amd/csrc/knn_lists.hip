@@ -3,15 +3,15 @@
 //                   goes to the lower candidate index --, d2[i, 0..k) their squared distances; skip_diag leaves out j == i by index;
 //   ggan_knn_vote   pred[i] = the label most frequent among labels_c[idx[i, :]] (a tied vote to the smallest label), the correct count
 //                   and the confusion matrix against labels_q.
-// The sweep is knn_sets.hip's: 128 x 128 Gram tiles (set_rows.h), the QUERY rows on the MFMA's N side, so that a lane owns one query per
-// 32-wide block column -- two per 64 x 64 wave tile -- for the whole sweep, grid (query blocks, S splits of the candidate blocks).  What a
-// lane keeps per owned query is a sorted list of K 64-bit KEYS
+// The sweep is knn_sets.hip's (sweep_tiles of set_rows.h: 128 x 128 Gram tiles), the QUERY rows on the MFMA's N side, so that a lane owns
+// one query per 32-wide block column -- two per 64 x 64 wave tile -- for the whole sweep, grid (query blocks, S splits of the candidate
+// blocks).  What a lane keeps per owned query is a sorted list of K 64-bit KEYS
 //   key = (bit pattern of D) << 32 | candidate index
 // D = max(n_i + n_j - 2 g_ij, 0) is a non-negative float (never -0: n_i + n_j >= +0 and an exact zero of a round-to-nearest sum is +0),
 // whose bit pattern orders like its value, so one unsigned 64-bit compare IS the pair order, and the insert / merge networks of
-// knn_sets.hip carry over with min / max on keys.  Keys of distinct candidates are distinct, so the K smallest of a set of keys do not
-// depend on the order they are met in: lane halves, wave pairs and split partials are merged by the same insert, and the result is the
-// same for every launch shape.  A candidate left out -- a ghost row of a ragged tile, j == i under skip_diag -- gets the key ~0, above
+// set_rows.h (list_insert, lists_store) carry over with min / max on keys.  Keys of distinct candidates are distinct, so the K smallest
+// of a set of keys do not depend on the order they are met in: lane halves, wave pairs and split partials are merged by the same
+// insert, and the result is the same for every launch shape.  A candidate left out -- a ghost row of a ragged tile, j == i under skip_diag -- gets the key ~0, above
 // every real one (a real key's upper word is at most the bit pattern of +inf); with k <= the number of real candidates it never reaches
 // an output.  No floating-point atomics: two calls give the same bits.
 #include "common.h"
@@ -20,107 +20,31 @@ using namespace ggan;
 
 namespace {
 
-typedef unsigned long long nkey;
 constexpr int kMaxK = 8;
-constexpr int kTargetWgs = 2048;
 constexpr int kMaxClasses = 1024;
-constexpr nkey kNoKey = ~(nkey)0;
 
-struct ListParams : RowSets {      // Z = [Q; C]: queries rows [0, nq), candidates rows [c0, c0 + nc)
-    nkey* pk;                     // partials [S][K][nq]
-    int nq, nc, c0;
-    int nbc, S;                    // candidate blocks, splits of them
+struct ListParams : SweepParams {  // (set_rows.h: Z = [Q; C], queries and candidates, the splits)
+    nkey* pk;                      // partials [S][K][nq]
     int skip;                      // leave out candidate j == query i (nq == nc)
 };
-
-__device__ __forceinline__ nkey kmin(nkey a, nkey b) { return a < b ? a : b; }
-__device__ __forceinline__ nkey kmax(nkey a, nkey b) { return a < b ? b : a; }
-
-// v into the ascending list L of the K smallest keys seen so far (knn_sets.hip's list_insert on keys)
-template <int K>
-__device__ __forceinline__ void key_insert(nkey (&L)[K], nkey v) {
-    if (v < L[K - 1]) {
-#pragma unroll
-        for (int q = K - 1; q > 0; --q) L[q] = kmax(L[q - 1], kmin(L[q], v));
-        L[0] = kmin(L[0], v);
-    }
-}
-
-__device__ __forceinline__ nkey key_shfl_xor(nkey v, int mask) {
-    const unsigned lo = __shfl_xor((unsigned)v, mask, 64), hi = __shfl_xor((unsigned)(v >> 32), mask, 64);
-    return ((nkey)hi << 32) | lo;
-}
 
 template <int K, bool VEC>
 __global__ __launch_bounds__(256, 2) void knn_lists_k(const ListParams P) {
     warm_kernarg(P);
-    __shared__ __attribute__((aligned(16))) float As[2][KS * LD];
-    __shared__ __attribute__((aligned(16))) float Bs[2][KS * LD];
-    __shared__ float nC[BT], nQ[BT];
-    __shared__ nkey mg[4][64][K];                       // the waves' lists, one per owned query
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave & 1, wn = wave >> 1, half = lane >> 5, l31 = lane & 31;
-    const int r0q = blockIdx.x * BT, s = blockIdx.y;
+    const int r0q = blockIdx.x * BT;
     nkey L[2][K];
-#pragma unroll
-    for (int bj = 0; bj < 2; ++bj)
-#pragma unroll
-        for (int q = 0; q < K; ++q) L[bj][q] = kNoKey;
-
-    float4 ra[2], rb[2];
-    if (s < P.nbc) load_step<VEC>(P, P.c0 + s * BT, r0q, 0, ra, rb);
-    for (int c = s; c < P.nbc; c += P.S) {
-        const int r0c = c * BT, cn = c + P.S;
-        if (tid < BT) nC[tid] = r0c + tid < P.nc ? P.norms[P.c0 + r0c + tid] : 0.f;
-        else nQ[tid - BT] = r0q + tid - BT < P.nq ? P.norms[r0q + tid - BT] : 0.f;
-        f32x16 acc[2][2];
-        gram_tile<VEC>(P, P.c0 + r0c, r0q, cn < P.nbc, P.c0 + cn * BT, r0q, As, Bs, ra, rb, acc);
-#pragma unroll
-        for (int bj = 0; bj < 2; ++bj) {
-            const int jl = wn * 64 + bj * 32 + l31;
+    list_clear(L[0]);
+    list_clear(L[1]);
+    sweep_tiles<VEC, 0>(P, nullptr, [&](int r0c, f32x16 (&acc)[2][2], const float (&ni)[2][16], const float (&nj)[2], const float (&)[1][BT]) {
+        for_each_acc([&](int il, int jl, int bi, int bj, int r) {
+            const int i = r0c + il;
             const int jskip = P.skip ? r0q + jl : -1;    // the candidate index this query leaves out
-            const float nj = nQ[jl];
-#pragma unroll
-            for (int bi = 0; bi < 2; ++bi) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int il = wm * 64 + bi * 32 + (r & 3) + 8 * (r >> 2) + 4 * half, i = r0c + il;
-                    const float dist = fmaxf(nC[il] + nj - 2.f * acc[bi][bj][r], 0.f);
-                    const nkey key = ((nkey)__float_as_uint(dist) << 32) | (unsigned)i;
-                    key_insert<K>(L[bj], (i < P.nc && i != jskip) ? key : kNoKey);
-                }
-            }
-        }
-        __syncthreads();                                   // nC / nQ are rewritten by the next tile
-    }
-
-    // lanes l and l ^ 32 own the same queries (other candidates): each takes the other's list
-#pragma unroll
-    for (int bj = 0; bj < 2; ++bj) {
-        nkey o[K];
-#pragma unroll
-        for (int q = 0; q < K; ++q) o[q] = key_shfl_xor(L[bj][q], 32);
-#pragma unroll
-        for (int q = 0; q < K; ++q) key_insert<K>(L[bj], o[q]);
-        if (half == 0) {
-#pragma unroll
-            for (int q = 0; q < K; ++q) mg[wave][bj * 32 + l31][q] = L[bj][q];
-        }
-    }
-    __syncthreads();
-    // waves (0, wn) and (1, wn) own the same 64 queries: thread ql < 128 merges the pair of query ql and writes the workgroup's list
-    if (tid < BT) {
-        const int w0 = 2 * (tid >> 6), ql = tid & 63, j = r0q + tid;
-        nkey a[K];
-#pragma unroll
-        for (int q = 0; q < K; ++q) a[q] = mg[w0][ql][q];
-#pragma unroll
-        for (int q = 0; q < K; ++q) key_insert<K>(a, mg[w0 + 1][ql][q]);
-        if (j < P.nq) {
-#pragma unroll
-            for (int q = 0; q < K; ++q) P.pk[((size_t)s * K + q) * P.nq + j] = a[q];
-        }
-    }
+            const float dist = gram_dist(ni[bi][r], nj[bj], acc[bi][bj][r]);
+            const nkey key = ((nkey)__float_as_uint(dist) << 32) | (unsigned)i;
+            list_insert<K>(L[bj], (i < P.nc && i != jskip) ? key : list_top<nkey>());
+        });
+    });
+    lists_store<K>(L, P.pk, P.nq);
 }
 
 // row j: the S partial lists merged, indices (and distances) out
@@ -130,12 +54,7 @@ __global__ __launch_bounds__(256) void knn_lists_final_k(const nkey* __restrict_
     const int j = blockIdx.x * 256 + threadIdx.x;
     if (j >= m) return;
     nkey L[K];
-#pragma unroll
-    for (int q = 0; q < K; ++q) L[q] = kNoKey;
-    for (int s = 0; s < S; ++s) {
-#pragma unroll
-        for (int q = 0; q < K; ++q) key_insert<K>(L, part[((size_t)s * K + q) * m + j]);
-    }
+    lists_merge_splits<K>(part, m, S, j, L);
 #pragma unroll
     for (int q = 0; q < K; ++q) {
         idx[(size_t)j * K + q] = (int)(unsigned)L[q];
@@ -174,15 +93,6 @@ __global__ __launch_bounds__(256) void knn_vote_k(const int* __restrict__ idx, c
     }
 }
 
-inline int blocks_of(int rows) { return (rows + BT - 1) / BT; }
-// splits of the candidate blocks: about kTargetWgs workgroups, so that a small query set still fills the chip (as knn_sets.hip)
-inline int splits_of(int nbq, int nbc) {
-    int S = (kTargetWgs + nbq - 1) / nbq;
-    if (S > nbc) S = nbc;
-    return S < 1 ? 1 : S;
-}
-inline bool rows_ok(int n) { return n >= 1 && n <= kMaxRows; }
-
 }  // namespace
 
 extern "C" {
@@ -203,33 +113,18 @@ int ggan_knn_lists(const float* Q, const float* C, int m, int n, int d, int k, i
     GGAN_CHECK_ARG(ws_bytes >= ggan_knn_lists_workspace(m, n, k), "workspace too small (ggan_knn_lists_workspace)");
     GGAN_CHECK_ARG(((uintptr_t)ws & 15) == 0, "workspace must be 16-byte aligned");
     ListParams P;
-    P.X = Q; P.Y = C; P.m = m; P.T = m + n; P.d = d;              // Z = [Q; C]: the queries first, the candidates behind them
-    P.vec = (d % 4 == 0) && ((uintptr_t)Q & 15) == 0 && ((uintptr_t)C & 15) == 0;
-    float* norms = (float*)ws;
-    P.norms = norms;
-    P.pk = (nkey*)((char*)ws + norms_bytes((long)m + n));
-    P.nq = m; P.nc = n; P.c0 = m;
-    P.nbc = blocks_of(n);
-    const int nbq = blocks_of(m);
-    P.S = splits_of(nbq, P.nbc);
-    P.skip = skip_diag ? 1 : 0;
+    SweepLaunch L;
     hipStream_t st = (hipStream_t)stream;
-    GGAN_LAUNCH("knn_lists_norms", 2.0 * P.T * d, 4.0 * P.T * d, set_norms_k, dim3(cdiv(P.T, 4)), dim3(256), 0, st, P, norms);
-    const double tiles = (double)nbq * P.nbc;
-    const double flops = tiles * 2.0 * BT * BT * d, bytes = tiles * 2.0 * BT * d * 4.0;
-    const dim3 grid(nbq, P.S);
-#define LISTS_CASE(K)                                                                                                                  \
-    case K:                                                                                                                            \
-        if (P.vec) { GGAN_LAUNCH("knn_lists", flops, bytes, (knn_lists_k<K, true>), grid, dim3(256), 0, st, P); }                      \
-        else { GGAN_LAUNCH("knn_lists", flops, bytes, (knn_lists_k<K, false>), grid, dim3(256), 0, st, P); }                           \
-        GGAN_LAUNCH("knn_lists_final", 0, 8.0 * P.S * K * m, knn_lists_final_k<K>, dim3(cdiv(m, 256)), dim3(256), 0, st,               \
-                    (const nkey*)P.pk, m, P.S, idx, d2);                                                                              \
-        break;
-    switch (k) {
-        LISTS_CASE(1) LISTS_CASE(2) LISTS_CASE(3) LISTS_CASE(4) LISTS_CASE(5) LISTS_CASE(6) LISTS_CASE(7) LISTS_CASE(8)
-    }
-#undef LISTS_CASE
-    return 0;
+    if (const int rc = sweep_setup(P, L, "knn_lists_norms", Q, C, m, n, d, ws, st)) return rc;
+    P.pk = (nkey*)L.part;
+    P.skip = skip_diag ? 1 : 0;
+    return dispatch_k_vec(k, P.vec, [&](auto K, auto VEC) {
+        constexpr int kk = decltype(K)::value;
+        GGAN_LAUNCH("knn_lists", L.flops, L.bytes, (knn_lists_k<kk, decltype(VEC)::value>), L.grid, dim3(256), 0, st, P);
+        GGAN_LAUNCH("knn_lists_final", 0, 8.0 * P.S * kk * m, knn_lists_final_k<kk>, dim3(cdiv(m, 256)), dim3(256), 0, st, (const nkey*)P.pk, m,
+                    P.S, idx, d2);
+        return 0;
+    });
 }
 
 int ggan_knn_vote(const int* idx, const int* labels_c, const int* labels_q, int m, int k, int classes, int* pred, int* correct,

@@ -26,7 +26,6 @@ using namespace ggan;
 namespace {
 
 constexpr int kMaxSigmas = 8;
-constexpr int kTargetWgs = 2048;
 
 struct SetParams : RowSets {       // (set_rows.h: the row list, its loads and the norm pre-pass)
     double* part;                  // [nb * S][3]
@@ -40,41 +39,21 @@ struct SetParams : RowSets {       // (set_rows.h: the row list, its loads and t
 __device__ __forceinline__ bool step_valid(int a, int t, int nb) { return 2 * t < nb || (2 * t == nb && 2 * a < nb) || t == 0; }
 
 // NS: the number of kernel widths (their constants then live in scalar registers for the whole epilogue; a run-time count made every
-// element's loop re-read them from the argument block).  VEC: see load4.
+// element's loop re-read them from the argument block).  VEC: see load4_raw.  Two workgroups per CU, as the sweeps of knn_sets.hip: without
+// the bound the allocator takes a whole SIMD's registers for NS >= 2 and one wave per SIMD is left.
 template <int NS, bool VEC>
-__global__ __launch_bounds__(256) void set_sums_k(const SetParams P) {
+__global__ __launch_bounds__(256, 2) void set_sums_k(const SetParams P) {
     warm_kernarg(P);
     __shared__ __attribute__((aligned(16))) float As[2][KS * LD];
     __shared__ __attribute__((aligned(16))) float Bs[2][KS * LD];
     __shared__ float nA[BT], nB[BT];
     __shared__ double red[4][3];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave & 1, wn = wave >> 1, half = lane >> 5, l31 = lane & 31;
     const int a = blockIdx.x, s = blockIdx.y;
     double dxx = 0.0, dyy = 0.0, dxy = 0.0;
     float g2[NS], wt[NS];
 #pragma unroll
     for (int q = 0; q < NS; ++q) { g2[q] = P.g2[q]; wt[q] = P.wt[q]; }
-
-    // staging: unit u of a thread is 4 consecutive k of one tile row; 4 lanes cover the 16 k of a row (64 contiguous bytes)
-    auto load_step = [&](int r0a, int r0b, int k0, float4 (&xa)[2], float4 (&xb)[2]) {
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const int unit = tid + 256 * u, row = unit >> 2, k = k0 + (unit & 3) * 4;
-            xa[u] = load4<VEC>(P, r0a + row, k);
-            xb[u] = load4<VEC>(P, r0b + row, k);
-        }
-    };
-    auto store_step = [&](int buf, const float4 (&xa)[2], const float4 (&xb)[2]) {
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const int unit = tid + 256 * u, row = unit >> 2, kq = unit & 3;
-            float* da = &As[buf][(kq * 4) * LD + row];
-            float* db = &Bs[buf][(kq * 4) * LD + row];
-            da[0] = xa[u].x; da[LD] = xa[u].y; da[2 * LD] = xa[u].z; da[3 * LD] = xa[u].w;
-            db[0] = xb[u].x; db[LD] = xb[u].y; db[2 * LD] = xb[u].z; db[3 * LD] = xb[u].w;
-        }
-    };
 
     // the steps of this workgroup: t = s, s + S, ... as far as they are tiles to compute (uniform over the workgroup)
     const int nt = P.nb / 2 + 1;
@@ -85,73 +64,30 @@ __global__ __launch_bounds__(256) void set_sums_k(const SetParams P) {
     const int r0a = a * BT;
     float4 ra[2], rb[2];
     int t = next_step(s);
-    if (t < nt) load_step(r0a, ((a + t) % P.nb) * BT, 0, ra, rb);
+    if (t < nt) load_step<VEC>(P, r0a, ((a + t) % P.nb) * BT, 0, ra, rb);
     while (t < nt) {
-        const int b = (a + t) % P.nb;
-        const int r0b = b * BT;
+        const int r0b = ((a + t) % P.nb) * BT;
         if (tid < BT) nA[tid] = r0a + tid < P.T ? P.norms[r0a + tid] : 0.f;
         else nB[tid - BT] = r0b + tid - BT < P.T ? P.norms[r0b + tid - BT] : 0.f;
-
-        f32x16 acc[2][2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-        store_step(0, ra, rb);                               // (the first step of a tile is loaded ahead: above, or behind the last tile's k loop)
-        __syncthreads();
-        int buf = 0;
-        for (int k0 = 0; k0 < P.d; k0 += KS) {
-            const bool more = k0 + KS < P.d;
-            if (more) load_step(r0a, r0b, k0 + KS, ra, rb);        // in flight while the MFMA block runs
-            const float* Ab = As[buf];
-            const float* Bb = Bs[buf];
-#pragma unroll
-            for (int kk = 0; kk < KS / 2; ++kk) {
-                const int k = 2 * kk + half;
-                const float a0 = Ab[k * LD + wm * 64 + l31], a1 = Ab[k * LD + wm * 64 + 32 + l31];
-                const float b0 = Bb[k * LD + wn * 64 + l31], b1 = Bb[k * LD + wn * 64 + 32 + l31];
-                acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-                acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-                acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-                acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-            }
-            if (more) store_step(buf ^ 1, ra, rb);
-            __syncthreads();
-            buf ^= 1;
-        }
-
         const int tn = next_step(t + P.S);
-        if (tn < nt) load_step(r0a, ((a + tn) % P.nb) * BT, 0, ra, rb);       // the next tile's first step, in flight during the epilogue
+        f32x16 acc[2][2];
+        gram_tile<VEC>(P, r0a, r0b, tn < nt, r0a, ((a + tn) % P.nb) * BT, As, Bs, ra, rb, acc);
 
-        // epilogue: accumulator register r of lane l is g[row (r & 3) + 8 (r >> 2) + 4 (l >> 5)][column l & 31] of its 32x32 block
         float fxx = 0.f, fyy = 0.f, fxy = 0.f;
         const bool diag = t == 0;
+        for_each_acc([&](int il, int jl, int bi, int bj, int r) {
+            const int i = r0a + il, j = r0b + jl;
+            const bool on = i < P.T && j < P.T && (!diag || i < j);
+            const float dist = gram_dist(nA[il], nB[jl], acc[bi][bj][r]);
+            float kv = 0.f;
 #pragma unroll
-        for (int bj = 0; bj < 2; ++bj) {
-            const int jl = wn * 64 + bj * 32 + l31, j = r0b + jl;
-            const float nj = nB[jl];
-            const bool jx = j < P.m;
-#pragma unroll
-            for (int bi = 0; bi < 2; ++bi) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int il = wm * 64 + bi * 32 + (r & 3) + 8 * (r >> 2) + 4 * half, i = r0a + il;
-                    const bool on = i < P.T && j < P.T && (!diag || i < j);
-                    const float dist = fmaxf(nA[il] + nj - 2.f * acc[bi][bj][r], 0.f);
-                    float kv = 0.f;
-                    #pragma unroll
-                    for (int q = 0; q < NS; ++q) kv = fmaf(wt[q], __builtin_amdgcn_exp2f(-g2[q] * dist), kv);
-                    kv = on ? kv : 0.f;
-                    const bool ix = i < P.m;
-                    fxx += (ix && jx) ? 2.f * kv : 0.f;
-                    fyy += (!ix && !jx) ? 2.f * kv : 0.f;
-                    fxy += (ix != jx) ? kv : 0.f;
-                }
-            }
-        }
+            for (int q = 0; q < NS; ++q) kv = fmaf(wt[q], __builtin_amdgcn_exp2f(-g2[q] * dist), kv);
+            kv = on ? kv : 0.f;
+            const bool ix = i < P.m, jx = j < P.m;
+            fxx += (ix && jx) ? 2.f * kv : 0.f;
+            fyy += (!ix && !jx) ? 2.f * kv : 0.f;
+            fxy += (ix != jx) ? kv : 0.f;
+        });
         dxx += (double)fxx; dyy += (double)fyy; dxy += (double)fxy;
         __syncthreads();                                   // nA / nB are rewritten by the next tile
         t = tn;
@@ -187,8 +123,8 @@ __global__ __launch_bounds__(256) void set_final_k(const double* __restrict__ pa
     }
 }
 
-inline int blocks_of(int m, int n) { return (int)(((long)m + n + BT - 1) / BT); }
-inline int splits_of(int nb) {
+// mmd's own splits, of the nt = nb / 2 + 1 steps of a block (the symmetric half: see the head of the file)
+inline int mmd_splits_of(int nb) {
     const int nt = nb / 2 + 1;
     int S = (kTargetWgs + nb - 1) / nb;
     if (S > nt) S = nt;
@@ -201,8 +137,8 @@ extern "C" {
 
 size_t ggan_mix_rbf_sums_workspace(int m, int n) {
     if (m < 1 || n < 1 || m > kMaxRows || n > kMaxRows) return 0;
-    const int nb = blocks_of(m, n);
-    return norms_bytes((long)m + n) + (size_t)nb * splits_of(nb) * 3 * sizeof(double);
+    const int nb = blocks_of((long)m + n);
+    return norms_bytes((long)m + n) + (size_t)nb * mmd_splits_of(nb) * 3 * sizeof(double);
 }
 
 int ggan_mix_rbf_sums(const float* X, const float* Y, int m, int n, int d, const float* sigmas, const float* wts, int ns,
@@ -215,31 +151,24 @@ int ggan_mix_rbf_sums(const float* X, const float* Y, int m, int n, int d, const
     GGAN_CHECK_ARG(((uintptr_t)ws & 15) == 0 && ((uintptr_t)sums3 & 7) == 0, "workspace must be 16-byte, sums3 8-byte aligned");
     for (int i = 0; i < ns; ++i) GGAN_CHECK_ARG(sigmas[i] > 0.f, "sigma <= 0");
     SetParams P;
-    P.X = X; P.Y = Y; P.m = m; P.T = m + n; P.d = d; P.ns = ns;
-    P.nb = blocks_of(m, n);
-    P.S = splits_of(P.nb);
-    P.vec = (d % 4 == 0) && ((uintptr_t)X & 15) == 0 && ((uintptr_t)Y & 15) == 0;
+    hipStream_t st = (hipStream_t)stream;
+    if (const int rc = rows_setup(P, "mmd_set_norms", X, Y, m, n, d, ws, st)) return rc;
+    P.ns = ns;
+    P.nb = blocks_of(P.T);
+    P.S = mmd_splits_of(P.nb);
     for (int i = 0; i < kMaxSigmas; ++i) {
         P.g2[i] = i < ns ? (float)(1.4426950408889634 / (2.0 * (double)sigmas[i] * (double)sigmas[i])) : 0.f;
         P.wt[i] = i < ns ? (wts ? wts[i] : 1.f) : 0.f;
     }
-    float* norms = (float*)ws;
-    P.norms = norms;
-    P.part = (double*)((char*)ws + norms_bytes((long)m + n));
-    hipStream_t st = (hipStream_t)stream;
-    GGAN_LAUNCH("mmd_set_norms", 2.0 * P.T * d, 4.0 * P.T * d, set_norms_k, dim3(cdiv(P.T, 4)), dim3(256), 0, st, P, norms);
+    P.part = (double*)((char*)ws + norms_bytes(P.T));
     // tiles computed: nb diagonal ones and nb (nb - 1) / 2 pairs
     const double tiles = 0.5 * (double)P.nb * (P.nb + 1);
-    const double flops = tiles * 2.0 * BT * BT * d, bytes = tiles * 2.0 * BT * d * 4.0;
-#define SUMS_CASE(NS)                                                                                                                  \
-    case NS:                                                                                                                           \
-        if (P.vec) { GGAN_LAUNCH("mmd_set_sums", flops, bytes, (set_sums_k<NS, true>), dim3(P.nb, P.S), dim3(256), 0, st, P); }        \
-        else { GGAN_LAUNCH("mmd_set_sums", flops, bytes, (set_sums_k<NS, false>), dim3(P.nb, P.S), dim3(256), 0, st, P); }             \
-        break;
-    switch (ns) {
-        SUMS_CASE(1) SUMS_CASE(2) SUMS_CASE(3) SUMS_CASE(4) SUMS_CASE(5) SUMS_CASE(6) SUMS_CASE(7) SUMS_CASE(8)
-    }
-#undef SUMS_CASE
+    if (const int rc = dispatch_k_vec(ns, P.vec, [&](auto NS, auto VEC) {
+            GGAN_LAUNCH("mmd_set_sums", tile_flops(tiles, d), tile_bytes(tiles, d), (set_sums_k<decltype(NS)::value, decltype(VEC)::value>),
+                        dim3(P.nb, P.S), dim3(256), 0, st, P);
+            return 0;
+        }))
+        return rc;
     GGAN_LAUNCH("mmd_set_final", 0, 24.0 * P.nb * P.S, set_final_k, dim3(1), dim3(256), 0, st, (const double*)P.part, P.nb * P.S, sums3);
     return 0;
 }

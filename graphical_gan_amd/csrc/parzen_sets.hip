@@ -22,12 +22,9 @@ using namespace ggan;
 namespace {
 
 constexpr int kMaxSigmas = 16;
-constexpr int kTargetWgs = 2048;
 
-struct ParzenParams : RowSets {    // Z = [Q; S]: queries rows [0, nq), candidates rows [c0, c0 + nc)
+struct ParzenParams : SweepParams {    // (set_rows.h: Z = [Q; S], queries and candidates, the splits)
     float* part;                   // partials [S][1 + ns][nq]: slot 0 the minimum distance, slot 1 + s the shifted sum of bandwidth s
-    int nq, nc, c0;
-    int nbc, S;                    // candidate blocks, splits of them
     int ns;
     float c2[kMaxSigmas];          // -log2(e) / (2 sigma_s^2): exp(-x / (2 sigma^2)) = exp2(c2 x)
 };
@@ -38,46 +35,28 @@ __device__ __forceinline__ float reshift(float c2, float from, float to) { retur
 template <bool VEC>
 __global__ __launch_bounds__(256, 2) void parzen_lse_k(const ParzenParams P) {
     warm_kernarg(P);
-    __shared__ __attribute__((aligned(16))) float As[2][KS * LD];
-    __shared__ __attribute__((aligned(16))) float Bs[2][KS * LD];
-    __shared__ float nC[BT], nQ[BT];
     // the running sums live in LDS, not in registers: 64 accumulators are live in the epilogue, and 2 x 16 sums on top of them spill.
     // Slot [g][bj][tid] belongs to thread tid alone during the sweep (consecutive lanes, consecutive banks), one read and one write per
     // tile, bandwidth and owned query -- against 2 d reads per tile of the main loop.
     __shared__ float Asum[kMaxSigmas][2][256];
     __shared__ float Msh[2][256];                          // the threads' minima, for the combination behind the sweep
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave & 1, wn = wave >> 1, half = lane >> 5, l31 = lane & 31;
-    const int r0q = blockIdx.x * BT, s = blockIdx.y;
+    const int tid = threadIdx.x, r0q = blockIdx.x * BT, s = blockIdx.y;
     float mn[2] = {INFINITY, INFINITY};
     for (int g = 0; g < P.ns; ++g) { Asum[g][0][tid] = 0.f; Asum[g][1][tid] = 0.f; }
 
-    float4 ra[2], rb[2];
-    if (s < P.nbc) load_step<VEC>(P, P.c0 + s * BT, r0q, 0, ra, rb);
-    for (int c = s; c < P.nbc; c += P.S) {
-        const int r0c = c * BT, cn = c + P.S;
-        if (tid < BT) nC[tid] = r0c + tid < P.nc ? P.norms[P.c0 + r0c + tid] : 0.f;
-        else nQ[tid - BT] = r0q + tid - BT < P.nq ? P.norms[r0q + tid - BT] : 0.f;
-        f32x16 acc[2][2];
-        gram_tile<VEC>(P, P.c0 + r0c, r0q, cn < P.nbc, P.c0 + cn * BT, r0q, As, Bs, ra, rb, acc);
+    sweep_tiles<VEC, 0>(P, nullptr, [&](int r0c, f32x16 (&acc)[2][2], const float (&ni)[2][16], const float (&nj)[2], const float (&)[1][BT]) {
         // accumulators -> distances in place, +inf for a ghost candidate; the tile's minimum per owned query
+        float t[2] = {INFINITY, INFINITY};
+        for_each_acc([&](int il, int jl, int bi, int bj, int r) {
+            const float dist = gram_dist(ni[bi][r], nj[bj], acc[bi][bj][r]);
+            acc[bi][bj][r] = r0c + il < P.nc ? dist : INFINITY;
+            t[bj] = fminf(t[bj], acc[bi][bj][r]);
+        });
         float old[2], sh[2];
 #pragma unroll
         for (int bj = 0; bj < 2; ++bj) {
-            const float nj = nQ[wn * 64 + bj * 32 + l31];
-            float t = INFINITY;
-#pragma unroll
-            for (int bi = 0; bi < 2; ++bi) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int il = wm * 64 + bi * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-                    const float dist = fmaxf(nC[il] + nj - 2.f * acc[bi][bj][r], 0.f);
-                    acc[bi][bj][r] = r0c + il < P.nc ? dist : INFINITY;
-                    t = fminf(t, acc[bi][bj][r]);
-                }
-            }
             old[bj] = mn[bj];
-            mn[bj] = fminf(mn[bj], t);
+            mn[bj] = fminf(mn[bj], t[bj]);
             sh[bj] = mn[bj] == INFINITY ? 0.f : mn[bj];    // only ghosts so far: every term below is exp2(-inf) = 0
         }
         for (int g = 0; g < P.ns; ++g) {
@@ -93,8 +72,7 @@ __global__ __launch_bounds__(256, 2) void parzen_lse_k(const ParzenParams P) {
                 Asum[g][bj][tid] = a;
             }
         }
-        __syncthreads();                                   // nC / nQ are rewritten by the next tile
-    }
+    });
     Msh[0][tid] = mn[0];
     Msh[1][tid] = mn[1];
     __syncthreads();
@@ -133,15 +111,6 @@ __global__ __launch_bounds__(256) void parzen_final_k(const ParzenParams P, floa
     }
 }
 
-inline int blocks_of(int rows) { return (rows + BT - 1) / BT; }
-// splits of the candidate blocks: about kTargetWgs workgroups, so that a small query set still fills the chip (as knn_sets.hip)
-inline int splits_of(int nbq, int nbc) {
-    int S = (kTargetWgs + nbq - 1) / nbq;
-    if (S > nbc) S = nbc;
-    return S < 1 ? 1 : S;
-}
-inline bool rows_ok(int n) { return n >= 1 && n <= kMaxRows; }
-
 }  // namespace
 
 extern "C" {
@@ -161,26 +130,20 @@ int ggan_parzen_lse(const float* Q, const float* S, int m, int n, int d, const f
     GGAN_CHECK_ARG(ws_bytes >= ggan_parzen_lse_workspace(m, n, ns), "workspace too small (ggan_parzen_lse_workspace)");
     GGAN_CHECK_ARG(((uintptr_t)ws & 15) == 0, "workspace must be 16-byte aligned");
     ParzenParams P;
-    P.X = Q; P.Y = S; P.m = m; P.T = m + n; P.d = d;              // Z = [Q; S]: the queries first, the candidates behind them
-    P.vec = (d % 4 == 0) && ((uintptr_t)Q & 15) == 0 && ((uintptr_t)S & 15) == 0;
-    float* norms = (float*)ws;
-    P.norms = norms;
-    P.part = (float*)((char*)ws + norms_bytes((long)m + n));
-    P.nq = m; P.nc = n; P.c0 = m;
-    P.nbc = blocks_of(n);
-    const int nbq = blocks_of(m);
-    P.S = splits_of(nbq, P.nbc);
+    SweepLaunch L;
+    hipStream_t st = (hipStream_t)stream;
+    if (const int rc = sweep_setup(P, L, "parzen_norms", Q, S, m, n, d, ws, st)) return rc;
+    P.part = (float*)L.part;
     P.ns = ns;
     for (int g = 0; g < kMaxSigmas; ++g) {
         const double sg = g < ns ? (double)sigmas[g] : 1.0;
         P.c2[g] = (float)(-1.4426950408889634 / (2.0 * sg * sg));
     }
-    hipStream_t st = (hipStream_t)stream;
-    GGAN_LAUNCH("parzen_norms", 2.0 * P.T * d, 4.0 * P.T * d, set_norms_k, dim3(cdiv(P.T, 4)), dim3(256), 0, st, P, norms);
-    const double tiles = (double)nbq * P.nbc;
-    const double flops = tiles * 2.0 * BT * BT * d, bytes = tiles * 2.0 * BT * d * 4.0;
-    if (P.vec) { GGAN_LAUNCH("parzen_lse", flops, bytes, parzen_lse_k<true>, dim3(nbq, P.S), dim3(256), 0, st, P); }
-    else { GGAN_LAUNCH("parzen_lse", flops, bytes, parzen_lse_k<false>, dim3(nbq, P.S), dim3(256), 0, st, P); }
+    if (const int rc = dispatch_vec(P.vec, [&](auto VEC) {
+            GGAN_LAUNCH("parzen_lse", L.flops, L.bytes, parzen_lse_k<decltype(VEC)::value>, L.grid, dim3(256), 0, st, P);
+            return 0;
+        }))
+        return rc;
     GGAN_LAUNCH("parzen_final", 0, 4.0 * P.S * (1 + ns) * m, parzen_final_k, dim3(cdiv(m, 256)), dim3(256), 0, st, P, lse);
     return 0;
 }

@@ -309,17 +309,13 @@ MMD_FUSED_MAX_ROWS = 512      # include/ggan.h: ggan_mix_rbf_mmd2_* take m + n <
 def mix_rbf_sums(x, y, sigmas, wts=None):
     """the three pairwise kernel sums of two row sets x [m, d], y [n, d] (ggan_mix_rbf_sums; x and y may be the same tensor) -> float64 device
     tensor [S_xx, S_yy, S_xy], the same-set sums over ordered pairs i != j.  Forward only: inputs that require grad are refused."""
-    if (torch.is_grad_enabled() and (x.requires_grad or y.requires_grad)):
-        raise _lib.GganError('mix_rbf_sums has no backward: detach the inputs (the differentiable op takes m + n <= %d rows)' % MMD_FUSED_MAX_ROWS)
-    x, y = _c(x), _c(y)
-    if x.dim() != 2 or y.dim() != 2 or x.shape[1] != y.shape[1]:
-        raise ValueError('mix_rbf_sums: two [rows, d] sets of one width expected, got %s and %s' % (tuple(x.shape), tuple(y.shape)))
+    _no_grad('mix_rbf_sums', [x, y], ' (the differentiable op takes m + n <= %d rows)' % MMD_FUSED_MAX_ROWS)
+    x, y = _row_shapes('mix_rbf_sums', [_c(x), _c(y)])
     (m, d), n = x.shape, y.shape[0]
     ns = len(sigmas)
     sg = (C.c_float * ns)(*[float(v) for v in sigmas])
     wt = (C.c_float * ns)(*[float(v) for v in wts]) if wts is not None else None
-    nbytes = int(_L().ggan_mix_rbf_sums_workspace(m, n))
-    ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=x.device)
+    ws, nbytes = _workspace(_L().ggan_mix_rbf_sums_workspace(m, n), x.device)
     out = torch.empty((3,), dtype=torch.float64, device=x.device)
     check(_L().ggan_mix_rbf_sums(_p(x), _p(y), m, n, d, sg, wt, ns, _p(out), _p(ws), nbytes, _stream()), 'ggan_mix_rbf_sums')
     return out
@@ -336,18 +332,35 @@ def mmd2_from_sums(sums3, m, n, wt_sum, biased):
 PRDC_MAX_K = 8                # include/ggan.h: ggan_knn_radii keeps 1 <= k <= 8 neighbours per row
 
 
+def _workspace(nbytes, device):
+    """(an op's scratch buffer, the size to tell the op): what its *_workspace entry asks for (0: shapes the entry itself refuses)"""
+    nbytes = int(nbytes)
+    return torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=device), nbytes
+
+
+def _row_shapes(name, sets):
+    """[rows, d] sets of one width (ValueError otherwise) -> the sets"""
+    if any(t.dim() != 2 for t in sets) or len(set(t.shape[1] for t in sets)) != 1:
+        raise ValueError('%s: [rows, d] sets of one width expected, got %s' % (name, ', '.join(str(tuple(t.shape)) for t in sets)))
+    return sets
+
+
+def _no_grad(name, sets, hint=''):
+    """the set-level ops are forward only: inputs that require grad are refused"""
+    if torch.is_grad_enabled() and any(t.requires_grad for t in sets):
+        raise _lib.GganError('%s has no backward: detach the inputs%s' % (name, hint))
+
+
 def _row_sets(name, sets, k=None, radii=None):
     """the checks the k-NN ball ops share, in this order: [rows, d] sets of one width, 1 <= k <= min(8, fewest rows - 1), one radius per row of
     the last set (ValueError, before anything else); no gradient; fp32 on the device -> the sets, contiguous"""
-    if any(t.dim() != 2 for t in sets) or len(set(t.shape[1] for t in sets)) != 1:
-        raise ValueError('%s: [rows, d] sets of one width expected, got %s' % (name, ', '.join(str(tuple(t.shape)) for t in sets)))
+    _row_shapes(name, sets)
     rows = min(t.shape[0] for t in sets)
     if k is not None and (not 1 <= int(k) <= PRDC_MAX_K or int(k) > rows - 1):
         raise ValueError('%s: 1 <= k <= min(%d, rows - 1) expected, got k = %s with %d rows' % (name, PRDC_MAX_K, k, rows))
     if radii is not None and (radii.dim() != 1 or radii.shape[0] != sets[-1].shape[0]):
         raise ValueError('%s: one radius per row of the second set expected, got %s for %d rows' % (name, tuple(radii.shape), sets[-1].shape[0]))
-    if torch.is_grad_enabled() and any(t.requires_grad for t in sets):
-        raise _lib.GganError('%s has no backward: detach the inputs' % name)
+    _no_grad(name, sets)
     return [_c(t) for t in sets]
 
 
@@ -356,8 +369,7 @@ def knn_radii(z, k):
     count) -> float32 [n] device tensor.  Forward only."""
     (z,), k = _row_sets('knn_radii', [z], k=k), int(k)
     n, d = z.shape
-    nbytes = int(_L().ggan_knn_radii_workspace(n, k))
-    ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=z.device)
+    ws, nbytes = _workspace(_L().ggan_knn_radii_workspace(n, k), z.device)
     r2 = torch.empty((n,), dtype=torch.float32, device=z.device)
     check(_L().ggan_knn_radii(_p(z), n, d, k, _p(r2), _p(ws), nbytes, _stream()), 'ggan_knn_radii')
     return r2
@@ -368,8 +380,7 @@ def ball_counts(a, b, r2_b):
     row of b (ggan_ball_counts) -> (int32 [m], float32 [m]) device tensors.  Forward only."""
     (a, b), r2_b = _row_sets('ball_counts', [a, b], radii=r2_b), _c(r2_b)
     (m, d), n = a.shape, b.shape[0]
-    nbytes = int(_L().ggan_ball_counts_workspace(m, n))
-    ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=a.device)
+    ws, nbytes = _workspace(_L().ggan_ball_counts_workspace(m, n), a.device)
     cnt = torch.empty((m,), dtype=torch.int32, device=a.device)
     mn = torch.empty((m,), dtype=torch.float32, device=a.device)
     check(_L().ggan_ball_counts(_p(a), _p(b), m, n, d, _p(r2_b), _p(cnt), _p(mn), _p(ws), nbytes, _stream()), 'ggan_ball_counts')
@@ -402,19 +413,16 @@ def knn_lists(q, c, k, skip_diag=False, return_d2=False):
     in distance goes to the lower index (ggan_knn_lists) -> int32 [m, k] device tensor, with return_d2 also the float32 [m, k] squared
     distances.  skip_diag (m == n): candidate i is left out for query i, by index.  Forward only."""
     name = 'knn_lists'
-    if q.dim() != 2 or c.dim() != 2 or q.shape[1] != c.shape[1]:
-        raise ValueError('%s: [rows, d] sets of one width expected, got %s, %s' % (name, tuple(q.shape), tuple(c.shape)))
+    _row_shapes(name, [q, c])
     (m, d), n, k, skip = q.shape, c.shape[0], int(k), bool(skip_diag)
     if skip and m != n:
         raise ValueError('%s: skip_diag needs as many candidates as queries, got %d and %d' % (name, n, m))
     if not 1 <= k <= KNN_MAX_K or k > n - (1 if skip else 0):
         raise ValueError('%s: 1 <= k <= min(%d, candidates%s) expected, got k = %s with %d candidates'
                          % (name, KNN_MAX_K, ' - 1' if skip else '', k, n))
-    if torch.is_grad_enabled() and (q.requires_grad or c.requires_grad):
-        raise _lib.GganError('%s has no backward: detach the inputs' % name)
+    _no_grad(name, [q, c])
     q, c = _c(q), _c(c)
-    nbytes = int(_L().ggan_knn_lists_workspace(m, n, k))
-    ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=q.device)
+    ws, nbytes = _workspace(_L().ggan_knn_lists_workspace(m, n, k), q.device)
     idx = torch.empty((m, k), dtype=torch.int32, device=q.device)
     d2 = torch.empty((m, k), dtype=torch.float32, device=q.device) if return_d2 else None
     check(_L().ggan_knn_lists(_p(q), _p(c), m, n, d, k, 1 if skip else 0, _p(idx), _p(d2), _p(ws), nbytes, _stream()), 'ggan_knn_lists')
@@ -490,16 +498,12 @@ def parzen_lse(q, s, sigmas):
     """lse[g, i] = log sum_j exp(-D(q_i, s_j) / (2 sigmas[g]^2)) over the rows of s [n, d], per row of q [m, d] and per bandwidth (at most
     16 host numbers), D the squared distance of knn_lists; the sums are carried shifted by the row's minimum distance, so the result is
     finite where a plain sum of kernel values is log 0 (ggan_parzen_lse) -> float32 [ns, m] device tensor.  Forward only."""
-    name = 'parzen_lse'
-    if q.dim() != 2 or s.dim() != 2 or q.shape[1] != s.shape[1]:
-        raise ValueError('%s: [rows, d] sets of one width expected, got %s, %s' % (name, tuple(q.shape), tuple(s.shape)))
-    sig = _sigmas(name, sigmas)
-    if torch.is_grad_enabled() and (q.requires_grad or s.requires_grad):
-        raise _lib.GganError('%s has no backward: detach the inputs' % name)
+    _row_shapes('parzen_lse', [q, s])
+    sig = _sigmas('parzen_lse', sigmas)
+    _no_grad('parzen_lse', [q, s])
     q, s = _c(q), _c(s)
     (m, d), n, ns = q.shape, s.shape[0], len(sig)
-    nbytes = int(_L().ggan_parzen_lse_workspace(m, n, ns))
-    ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=q.device)
+    ws, nbytes = _workspace(_L().ggan_parzen_lse_workspace(m, n, ns), q.device)
     lse = torch.empty((ns, m), dtype=torch.float32, device=q.device)
     host = (C.c_float * ns)(*sig)
     check(_L().ggan_parzen_lse(_p(q), _p(s), m, n, d, C.cast(host, C.c_void_p), ns, _p(lse), _p(ws), nbytes, _stream()), 'ggan_parzen_lse')
@@ -562,8 +566,7 @@ def ssim_pairs(a, b, shape, map_a=(1., 0.), map_b=None):
     same = a is b
     a = _c(a)
     b = a if same else _c(b)
-    nbytes = int(_L().ggan_ssim_pairs_workspace(n, c, h, w))
-    ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=a.device)
+    ws, nbytes = _workspace(_L().ggan_ssim_pairs_workspace(n, c, h, w), a.device)
     mse = torch.empty((n,), dtype=torch.float32, device=a.device)
     ssim = torch.empty((n,), dtype=torch.float32, device=a.device)
     check(_L().ggan_ssim_pairs(_p(a), _p(b), n, c, h, w, sa, ha, sb, hb, _p(mse), _p(ssim), _p(ws), nbytes, _stream()), 'ggan_ssim_pairs')

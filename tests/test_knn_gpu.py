@@ -64,7 +64,8 @@ def test_lists_against_float64(gpu, m, n, d, skip, ks):
 
 
 # ---- 2. the integer lattice: exact, ties included -----------------------------------------------------------------------------------------
-@pytest.mark.parametrize('m,n,d', [(130, 67, 33), (257, 300, 16), (192, 160, 3072)])
+@pytest.mark.parametrize('m,n,d', [(130, 67, 33), (257, 300, 16), (192, 160, 3072),
+                                   (5800, 5800, 16)])           # 46 blocks each way in 45 splits: split 0 walks a second, ragged tile
 def test_integer_lattice_is_exact_lower_index_at_a_tie(gpu, m, n, d):
     """integer entries: every product and sum is exact in float32, so indices and distances must EQUAL the reference's -- and the
     reference sees distance ties at the k-th place, so it is the lower-index rule that decides"""

@@ -81,12 +81,18 @@ def test_sums_and_both_estimators_against_float64(gpu, m, n, d):
 
 
 # ---- 2. exact coverage -----------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize('m,n,d', [(130, 67, 33), (257, 300, 131), (1, 1, 5)])
+@pytest.mark.parametrize('m,n,d', [(130, 67, 33), (257, 300, 131), (1, 1, 5),
+                                   (4100, 4000, 33)])          # 64 blocks, 33 steps in 32 splits: split 0 also takes the half step t = 32
 def test_every_pair_counted_exactly_once(gpu, m, n, d):
     """sigma = 1e6 makes every kernel value exactly sum(wts) = 7: the sums are then pair counts"""
     from graphical_gan_amd import functional as F
-    x, y, _ = _case(130, 67, 33) if d == 33 else (_case(257, 300, 131) if d == 131 else
-                                                 (np.ones((1, 5), np.float32), np.full((1, 5), 2.0, np.float32), None))
+    if d == 5:
+        x, y = np.ones((1, 5), np.float32), np.full((1, 5), 2.0, np.float32)
+    elif m > 1000:                   # (rows alone: the counts are closed-form, the float64 sums of _case are not needed)
+        rng = np.random.default_rng(1000 * m + 10 * n + d)
+        x, y = rng.standard_normal((m, d)).astype(np.float32), rng.standard_normal((n, d)).astype(np.float32)
+    else:
+        x, y, _ = _case(m, n, d)
     got = F.mix_rbf_sums(_t(x, gpu), _t(y, gpu), (1e6,) * 3, (1., 2., 4.)).cpu().numpy()
     assert got.tolist() == [7.0 * m * (m - 1), 7.0 * n * (n - 1), 7.0 * m * n], got
 

@@ -49,9 +49,9 @@ def test_values_against_float64(gpu, m, n, d):
 
 
 # ---- 2. limits --------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize('m,n,d', [(130, 67, 33), (1, 1, 5)])
+@pytest.mark.parametrize('m,n,d', [(130, 67, 33), (1, 1, 5), (5800, 5800, 16)])          # (the last: 46 blocks in 45 splits, two tiles in split 0)
 def test_a_huge_bandwidth_counts_the_candidates(gpu, m, n, d):
-    Q, S = R.lattice(130, 67, 33)[:2] if d == 33 else (np.ones((1, 5), np.float32), np.full((1, 5), 2.0, np.float32))
+    Q, S = R.lattice(m, n, d)[:2] if d != 5 else (np.ones((1, 5), np.float32), np.full((1, 5), 2.0, np.float32))
     got = _lse(Q, S, [1e6], gpu)
     assert np.all(np.abs(got - np.log(n)) <= 1e-6), np.abs(got - np.log(n)).max()
 

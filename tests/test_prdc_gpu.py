@@ -80,7 +80,8 @@ def test_self_left_out_by_index_duplicates_count(gpu):
 
 
 # ---- 3. exactness on a lattice --------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize('m,n,d', [(130, 67, 33), (257, 300, 16)])
+@pytest.mark.parametrize('m,n,d', [(130, 67, 33), (257, 300, 16),
+                                   (5800, 5800, 16)])           # 46 blocks each way in 45 splits: split 0 walks a second, ragged tile
 def test_integer_lattice_is_exact_ties_included(gpu, m, n, d):
     """integer entries: every product and sum is exact in float32, so everything must EQUAL the reference -- the test of `<=` at a tie and
     of the multiset rule (equal distances are plentiful)"""
@@ -103,7 +104,7 @@ def test_integer_lattice_is_exact_ties_included(gpu, m, n, d):
 
 
 # ---- 4. every pair seen exactly once ----------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize('m,n,d', [(130, 67, 33), (257, 300, 131), (1, 1, 5)])
+@pytest.mark.parametrize('m,n,d', [(130, 67, 33), (257, 300, 131), (1, 1, 5), (5800, 5800, 16)])          # (the last: two tiles per workgroup)
 def test_every_pair_seen_exactly_once(gpu, m, n, d):
     import torch
     from graphical_gan_amd import functional as F
