@@ -56,6 +56,7 @@ ema_decay; no part of the reference): an evaluator with `weights = 'ema'` runs i
 give the names (' ema') and files ('_ema') of what it then reports, and `... CKPT --ema` scores the `ema/gen/` keys of a checkpoint.
 The critic has no average: `dev gen cost ema` sets the averaged Generator / Extractor against the live critic."""
 import argparse
+import collections
 import contextlib
 import os
 import time
@@ -142,6 +143,101 @@ def _rec_stats(mse, ssim):
     psnr, s = F.psnr_from_mse(mse), ssim.double()
     count = torch.full((), float(s.shape[0]), dtype=torch.float64, device=s.device)
     return torch.stack([mse.double().mean(), psnr.mean(), s.mean(), s.std(unbiased=False) / torch.sqrt(count)]), psnr
+
+
+# ---- the set-level dev scores: one row each, in the order Evaluator.set_scores computes and logs them ---------------------------------
+class SetScore(collections.namedtuple('SetScore', 'name needs title sequences help check score')):
+    """name: the keyword of set_scores / evaluate_once, the flag --<name>, the settings key <NAME>_EVERY, $GGAN_<NAME>_EVERY and the row cap
+    <NAME>_MAX_ROWS (default: the module constant of that name); needs: the sets _score_sets builds for it, of 'generated', 'labels', 'rec';
+    title: what the 'skipped' messages call it; sequences: True where the state-space scripts have the score too, else why they have not;
+    help: of the flag; check(ev, batches, cap): what is refused before any device work, or None; score(ev, sets, rows) -> (names, device
+    tensors) from the leading `rows` rows, inside set_scores' guard"""
+    __slots__ = ()
+    every = property(lambda self: self.name.upper() + '_EVERY')
+
+    def cap(self, S):
+        key = self.name.upper() + '_MAX_ROWS'
+        return int(S.get(key, globals()[key]))
+
+
+_SPACES = (('z', 'z', 'pz'), ('x', 'x', 'gx'))         # (space, real set, generated set) of the two-sample scores
+
+
+def _mmd_score(ev, sets, rows):
+    if rows < 2:
+        raise ValueError('the unbiased MMD needs at least 2 rows per set')
+    return (['dev mmd ' + space for space, _, _ in _SPACES],
+            [lib.objs.mmd.mix_rbf_mmd2(sets[a][:rows], sets[b][:rows], biased=False).double().reshape(1) for _, a, b in _SPACES])
+
+
+def _prdc_score(ev, sets, rows):
+    k = int(ev.S.get('PRDC_K', PRDC_K))
+    if k > rows - 1:
+        raise ValueError('PRDC_K = %d needs more than %d rows per set' % (k, rows))
+    return (['dev %s %s' % (what, space) for space, _, _ in _SPACES for what in ('precision', 'recall', 'density', 'coverage')],
+            [F.prdc(sets[a][:rows], sets[b][:rows], k) for _, a, b in _SPACES])
+
+
+def _knn_check(ev, batches, cap):
+    k = int(ev.S.get('KNN_K', KNN_K))
+    if not 1 <= k <= F.KNN_MAX_K:
+        raise ValueError('KNN_K = %d: 1 <= KNN_K <= %d expected' % (k, F.KNN_MAX_K))
+
+
+def _knn_score(ev, sets, rows):
+    k = int(ev.S.get('KNN_K', KNN_K))
+    if k > rows - 1:
+        raise ValueError('KNN_K = %d needs more than %d rows' % (k, rows))
+    return (['dev knn accuracy ' + space for space in ('z', 'x')],
+            [F.knn_accuracy(sets[space][:rows], sets['y'][:rows], k) for space in ('z', 'x')])
+
+
+def _parzen_sigmas(S):
+    return [float(v) for v in np.asarray(S.get('PARZEN_SIGMAS', PARZEN_SIGMAS), dtype=np.float64).reshape(-1)]
+
+
+def _parzen_check(ev, batches, cap):
+    B, sigmas = ev.cfg.B, _parzen_sigmas(ev.S)
+    if not 1 <= len(sigmas) <= F.PARZEN_MAX_SIGMAS:
+        raise ValueError('PARZEN_SIGMAS: 1 .. %d bandwidths expected, got %d' % (F.PARZEN_MAX_SIGMAS, len(sigmas)))
+    full = sum(1 for b in batches if _split(b)[0].shape[0] == B)
+    if min(full, max(1, cap // B)) < 2:
+        raise ValueError('the Parzen pass needs at least 2 full minibatches of %d rows within PARZEN_MAX_ROWS = %d: one to '
+                         'choose the bandwidth on, one to score' % (B, cap))
+
+
+def _parzen_score(ev, sets, rows):
+    return ['dev parzen ll x', 'dev parzen se x', 'dev parzen sigma x'], [ev._parzen(sets['x'][:rows], sets['gx'][:rows], _parzen_sigmas(ev.S))]
+
+
+def _rec_score(ev, sets, rows):
+    return list(REC_KEYS), [ev._rec(sets['x'][:rows], sets['rx'][:rows])]
+
+
+_NO_CODE, _NO_IMAGES = 'the state-space scripts have no single code to compare', 'the state-space scripts have no single set of images to compare'
+SET_SCORES = (
+    SetScore('mmd', ('generated',), 'dev mmd', _NO_CODE,
+             'also score the dev set by the unbiased MMD^2 of codes and of images (dev mmd z / dev mmd x; image scripts)', None, _mmd_score),
+    SetScore('prdc', ('generated',), 'dev precision / recall / density / coverage', _NO_CODE,
+             'also score the dev set by k-NN-ball precision / recall / density / coverage of codes and of images (eight dev rows; image scripts)',
+             None, _prdc_score),
+    SetScore('knn', ('labels',), 'dev knn accuracy', _NO_CODE,
+             'also score the labelled dev set by the leave-one-out k-NN accuracy of codes and of images (dev knn accuracy z / x; image scripts)',
+             _knn_check, _knn_score),
+    SetScore('parzen', ('generated',), 'dev parzen ll', _NO_IMAGES,
+             'also score the dev set by the Gaussian Parzen-window log-likelihood of held-out images under generated ones (dev parzen ll / se / '
+             'sigma x; image scripts)', _parzen_check, _parzen_score),
+    SetScore('rec', ('rec',), 'dev rec mse / psnr / ssim', True,
+             'also score how well Generator(Extractor(x)) gives the dev set back: per-image (state-space scripts: per-frame) mse / PSNR / SSIM in '
+             'the unit pixel range (dev rec mse / psnr / ssim / ssim se x; every script)', None, _rec_score),
+)
+
+
+def _known(where, scores):
+    """the keywords of `scores` must be rows of SET_SCORES"""
+    unknown = sorted(set(scores) - set(r.name for r in SET_SCORES))
+    if unknown:
+        raise TypeError('%s: no set-level score %s (known: %s)' % (where, ', '.join(unknown), ', '.join(r.name for r in SET_SCORES)))
 
 
 class _Passes(object):
@@ -362,62 +458,32 @@ class Evaluator(_Passes):
             sets['gx'][rows].copy_(self.model.Generator(sets['pz'][rows]).float())
         return sets
 
-    def set_scores(self, batches, mmd=False, prdc=False, knn=False, return_sets=False, parzen=False, rec=False):
-        """the set-level scores asked for, from ONE build of the sets (_score_sets: one stream of noise draws, whichever scores are on) and
-        ONE host synchronisation: mmd -> the two values of mmd_scores, prdc -> the eight of prdc_scores, knn -> the two of knn_scores,
-        parzen -> the three of parzen_scores, rec -> the four of rec_scores, in that order.  With several on, each scores the leading rows its own row cap allows.  knn
-        needs labelled minibatches (the labels come from the sets' own _stage call); with knn alone the generated sets are not built.
-        parzen needs at least two full minibatches within its row cap (one to choose the bandwidth on, one to score) and at most
-        functional.PARZEN_MAX_SIGMAS bandwidths.  rec adds the set rx = Generator(q_z) and compares it with x image by image (its per-image
-        rows stay in self.rec_rows); with knn and rec alone the generated sets are not built.  return_sets: (values, {z, pz, x, gx}), with
-        knn also y, with rec also rx, with knn alone {z, x, y}."""
-        B = self.cfg.B
-        cap = {'mmd': int(self.S.get('MMD_MAX_ROWS', MMD_MAX_ROWS)), 'prdc': int(self.S.get('PRDC_MAX_ROWS', PRDC_MAX_ROWS)),
-               'knn': int(self.S.get('KNN_MAX_ROWS', KNN_MAX_ROWS)), 'parzen': int(self.S.get('PARZEN_MAX_ROWS', PARZEN_MAX_ROWS)),
-               'rec': int(self.S.get('REC_MAX_ROWS', REC_MAX_ROWS))}
-        on = [name for name, flag in (('mmd', mmd), ('prdc', prdc), ('knn', knn), ('parzen', parzen), ('rec', rec)) if flag]
+    def set_scores(self, batches, return_sets=False, **on):
+        """the set-level scores asked for by keyword (the names of SET_SCORES: mmd=True, ...), from ONE build of the sets (_score_sets: one
+        stream of noise draws, whichever scores are on) and ONE host synchronisation: mmd -> the two values of mmd_scores, prdc -> the eight
+        of prdc_scores, knn -> the two of knn_scores, parzen -> the three of parzen_scores, rec -> the four of rec_scores, in the table's
+        order.  With several on, each scores the leading rows its own row cap allows.  knn needs labelled minibatches (the labels come
+        from the sets' own _stage call); parzen needs at least two full minibatches within its row cap (one to choose the bandwidth on, one
+        to score) and at most functional.PARZEN_MAX_SIGMAS bandwidths; rec adds the set rx = Generator(q_z) and compares it with x image by
+        image (its per-image rows stay in self.rec_rows).  The generated sets are built only where a score that is on needs them.
+        return_sets: (values, {z, pz, x, gx}), with knn also y, with rec also rx, with knn alone {z, x, y}."""
+        _known('set_scores', on)
+        on = [r for r in SET_SCORES if on.get(r.name)]
         if not on:
             raise ValueError('set_scores: no score was asked for')
-        k = int(self.S.get('PRDC_K', PRDC_K))
-        knn_k = int(self.S.get('KNN_K', KNN_K))
-        if knn and not 1 <= knn_k <= F.KNN_MAX_K:
-            raise ValueError('KNN_K = %d: 1 <= KNN_K <= %d expected' % (knn_k, F.KNN_MAX_K))
-        if parzen:
-            sigmas = [float(v) for v in np.asarray(self.S.get('PARZEN_SIGMAS', PARZEN_SIGMAS), dtype=np.float64).reshape(-1)]
-            if not 1 <= len(sigmas) <= F.PARZEN_MAX_SIGMAS:
-                raise ValueError('PARZEN_SIGMAS: 1 .. %d bandwidths expected, got %d' % (F.PARZEN_MAX_SIGMAS, len(sigmas)))
-            full = sum(1 for b in batches if _split(b)[0].shape[0] == B)
-            if min(full, max(1, cap['parzen'] // B)) < 2:
-                raise ValueError('the Parzen pass needs at least 2 full minibatches of %d rows within PARZEN_MAX_ROWS = %d: one to '
-                                 'choose the bandwidth on, one to score' % (B, cap['parzen']))
+        B = self.cfg.B
+        cap = {r.name: r.cap(self.S) for r in on}
+        for r in on:
+            if r.check:
+                r.check(self, batches, cap[r.name])
+        needs = set(n for r in on for n in r.needs)
         with self._guard():
-            sets = self._score_sets(batches, max(cap[name] for name in on), generated=bool(mmd or prdc or parzen), labels=bool(knn), rec=bool(rec))
-            rows = {name: min(sets['z'].shape[0], max(1, cap[name] // B) * B) for name in on}
+            sets = self._score_sets(batches, max(cap.values()), generated='generated' in needs, labels='labels' in needs, rec='rec' in needs)
             names, vals = [], []
-            if mmd:
-                if rows['mmd'] < 2:
-                    raise ValueError('the unbiased MMD needs at least 2 rows per set')
-                for space, a, b in (('z', 'z', 'pz'), ('x', 'x', 'gx')):
-                    names.append('dev mmd ' + space)
-                    vals.append(lib.objs.mmd.mix_rbf_mmd2(sets[a][:rows['mmd']], sets[b][:rows['mmd']], biased=False).double().reshape(1))
-            if prdc:
-                if k > rows['prdc'] - 1:
-                    raise ValueError('PRDC_K = %d needs more than %d rows per set' % (k, rows['prdc']))
-                for space, a, b in (('z', 'z', 'pz'), ('x', 'x', 'gx')):
-                    names += ['dev %s %s' % (what, space) for what in ('precision', 'recall', 'density', 'coverage')]
-                    vals.append(F.prdc(sets[a][:rows['prdc']], sets[b][:rows['prdc']], k))
-            if knn:
-                if knn_k > rows['knn'] - 1:
-                    raise ValueError('KNN_K = %d needs more than %d rows' % (knn_k, rows['knn']))
-                for space in ('z', 'x'):
-                    names.append('dev knn accuracy ' + space)
-                    vals.append(F.knn_accuracy(sets[space][:rows['knn']], sets['y'][:rows['knn']], knn_k))
-            if parzen:
-                names += ['dev parzen ll x', 'dev parzen se x', 'dev parzen sigma x']
-                vals.append(self._parzen(sets['x'][:rows['parzen']], sets['gx'][:rows['parzen']], sigmas))
-            if rec:
-                names += list(REC_KEYS)
-                vals.append(self._rec(sets['x'][:rows['rec']], sets['rx'][:rows['rec']]))
+            for r in on:
+                n, v = r.score(self, sets, min(sets['z'].shape[0], max(1, cap[r.name] // B) * B))
+                names += n
+                vals += v
             vals = torch.cat(vals).cpu().numpy()
         res = {name: float(v) for name, v in zip(names, vals)}
         return (res, sets) if return_sets else res
@@ -782,11 +848,8 @@ def main(argv=None):
     ap.add_argument('--mode', default=None, help="the script's MODE (default: the script's own)")
     ap.add_argument('--out-dir', default=None, help='also write the sample grid and the reconstructions here (the state-space scripts: the video files, required)')
     ap.add_argument('--manifold', action='store_true', help='also write the latent-space t-SNE pictures of the MNIST scripts to --out-dir')
-    ap.add_argument('--mmd', action='store_true', help='also score the dev set by the unbiased MMD^2 of codes and of images (dev mmd z / dev mmd x; image scripts)')
-    ap.add_argument('--prdc', action='store_true', help='also score the dev set by k-NN-ball precision / recall / density / coverage of codes and of images (eight dev rows; image scripts)')
-    ap.add_argument('--knn', action='store_true', help='also score the labelled dev set by the leave-one-out k-NN accuracy of codes and of images (dev knn accuracy z / x; image scripts)')
-    ap.add_argument('--parzen', action='store_true', help='also score the dev set by the Gaussian Parzen-window log-likelihood of held-out images under generated ones (dev parzen ll / se / sigma x; image scripts)')
-    ap.add_argument('--rec', action='store_true', help='also score how well Generator(Extractor(x)) gives the dev set back: per-image (state-space scripts: per-frame) mse / PSNR / SSIM in the unit pixel range (dev rec mse / psnr / ssim / ssim se x; every script)')
+    for row in SET_SCORES:
+        ap.add_argument('--' + row.name, action='store_true', help=row.help)
     ap.add_argument('--ema', action='store_true', help="score the averaged generator-side weights the checkpoint holds (its ema/gen/ keys, written by a run with $GGAN_EMA_DECAY) instead of the last iterate: every name gets the suffix ' ema', every file '_ema'; the critic of 'dev gen cost ema' is the live one")
     ap.add_argument('--set', action='append', default=[], metavar='KEY=VALUE', help='override an UPPERCASE setting (int / float / str)')
     a = ap.parse_args(argv)
@@ -802,14 +865,10 @@ def main(argv=None):
         over[k] = v
     if a.mode:
         over['MODE'] = a.mode
-    if a.mmd and os.path.splitext(os.path.basename(a.script))[0] in run._SEQUENCE_SCRIPTS:
-        ap.error('--mmd: the state-space scripts have no single code to compare')
-    if a.prdc and os.path.splitext(os.path.basename(a.script))[0] in run._SEQUENCE_SCRIPTS:
-        ap.error('--prdc: the state-space scripts have no single code to compare')
-    if a.knn and os.path.splitext(os.path.basename(a.script))[0] in run._SEQUENCE_SCRIPTS:
-        ap.error('--knn: the state-space scripts have no single code to compare')
-    if a.parzen and os.path.splitext(os.path.basename(a.script))[0] in run._SEQUENCE_SCRIPTS:
-        ap.error('--parzen: the state-space scripts have no single set of images to compare')
+    if os.path.splitext(os.path.basename(a.script))[0] in run._SEQUENCE_SCRIPTS:
+        for row in SET_SCORES:
+            if getattr(a, row.name) and row.sequences is not True:
+                ap.error('--%s: %s' % (row.name, row.sequences))
     if a.manifold:          # (checked before anything is built)
         name = os.path.splitext(os.path.basename(a.script))[0]
         if name not in MANIFOLD_SCRIPTS:
@@ -821,7 +880,7 @@ def main(argv=None):
     cfg, model = run.config(S), None
     if S['DATASET'] in run.SEQUENCE_DATASETS:
         from .models_ssgan import StateSpaceGAN
-        if not a.out_dir and not a.rec:
+        if not a.out_dir and not any(getattr(a, row.name) for row in SET_SCORES):
             ap.error('--out-dir is required for %s: its passes are files' % a.script)
         model = StateSpaceGAN(cfg)
     ema = None
@@ -837,18 +896,19 @@ def main(argv=None):
         # the checkpoint's live ones), and the evaluators only name what they write
         tr.load_params(ema)
         tr.ema_loaded = True
-    res = evaluate_once(tr, S, out_dir=a.out_dir, manifold=a.manifold, mmd=a.mmd, prdc=a.prdc, knn=a.knn, parzen=a.parzen, rec=a.rec)
+    res = evaluate_once(tr, S, out_dir=a.out_dir, manifold=a.manifold, **{row.name: getattr(a, row.name) for row in SET_SCORES})
     for k in sorted(res):
         print('%s\t%s' % (k, res[k]))
     return res
 
 
-def evaluate_once(tr, S, out_dir=None, frame='eval', manifold=False, mmd=False, prdc=False, knn=False, parzen=False, rec=False):
+def evaluate_once(tr, S, out_dir=None, frame='eval', manifold=False, **scores):
     """every pass the script's data allow, once -> {name: value}; manifold: the latent-space pictures too (labelled dev data only);
-    mmd: the two dev-set MMD^2 scores too; prdc: the eight precision / recall / density / coverage scores too; knn: the two k-NN
-    accuracies too (labelled dev data only); a trainer whose weights are averaged ones loaded from a checkpoint (tr.ema_loaded, main --ema):
-    names and files carry the suffixes; parzen: the three Parzen-window values too; rec: the four reconstruction values too -- one build of the sets for the five.  The
-    state-space scripts: the video files (with out_dir) and, with rec, the four reconstruction values of the dev sequences' frames"""
+    scores: the set-level scores of SET_SCORES to add, by name (mmd=True, ...: Evaluator.set_scores' keywords, one build of the sets for all
+    of them; a score that needs labels is skipped on unlabelled dev data); a trainer whose weights are averaged ones loaded from a
+    checkpoint (tr.ema_loaded, main --ema): names and files carry the suffixes.  The state-space scripts: the video files (with out_dir)
+    and, with rec, the four reconstruction values of the dev sequences' frames"""
+    _known('evaluate_once', scores)
     from . import run
     ema_names = bool(getattr(tr, 'ema_loaded', False))
     if S['DATASET'] in run.SEQUENCE_DATASETS:       # the video passes: files only (train_data: the first dev minibatch)
@@ -856,7 +916,7 @@ def evaluate_once(tr, S, out_dir=None, frame='eval', manifold=False, mmd=False, 
         ev.weights = 'ema' if ema_names else 'live'
         dev, _ = run.eval_sets(S, tr.model, tr.device)
         res = {}
-        if rec:
+        if scores.get('rec'):
             res.update(ev.tag(ev.rec_scores(run.rec_sequences(S, tr.model, tr.device))))
         if out_dir:
             ev.set_fixed_data(dev[0])
@@ -869,11 +929,12 @@ def evaluate_once(tr, S, out_dir=None, frame='eval', manifold=False, mmd=False, 
     res = dict(ev.tag(ev.dev_costs(dev)))
     if tr.cfg.K and test is not None:
         res.update(ev.tag({'testing accuracy': ev.cluster_accuracy(test)}))
-    if knn and not run.labelled(dev):
-        print('[evaluate] dev knn accuracy skipped: no labelled dev set')
-        knn = False
-    if mmd or prdc or knn or parzen or rec:
-        res.update(ev.tag(ev.set_scores(dev, mmd=mmd, prdc=prdc, knn=knn, parzen=parzen, rec=rec)))
+    for row in SET_SCORES:
+        if scores.get(row.name) and 'labels' in row.needs and not run.labelled(dev):
+            print('[evaluate] %s skipped: no labelled dev set' % row.title)
+            scores[row.name] = False
+    if any(scores.values()):
+        res.update(ev.tag(ev.set_scores(dev, **scores)))
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
         ev.set_fixed_data(dev[0])

@@ -3,6 +3,7 @@ reference's gan_inference_* / gmgan_inference_* / ssgan_inference_* scripts; the
 gmgan_inference_cifar10.py:470-549: alternate one generator step and CRITIC_ITERS critic steps on fresh minibatches, log the
 costs through tflib.plot, dump sample grids and a checkpoint every so often)."""
 import contextlib
+import functools
 import itertools
 import os
 import time
@@ -14,6 +15,8 @@ from . import checkpoint
 from . import tflib as lib
 from .data import DevicePrefetcher
 from .engine import Trainer
+from .evaluate import SET_SCORES, Evaluator, SequenceEvaluator
+from .models_ssgan import StateSpaceGAN
 
 
 def _batches(S, model, device):
@@ -126,93 +129,25 @@ def manifold_due(plan, it, iters):
     return bool((n and it % n == n - 1) or (plan.get('MANIFOLD_AT_END') and it == iters - 1))
 
 
-# the dev-set MMD^2 scores (evaluate.Evaluator.mmd_scores) are no pass of the reference's loops: off unless asked for, a cadence of their
-# own outside EVAL_KEYS
-def mmd_settings(script):
-    """{'MMD_EVERY': N} for the eight image scripts when $GGAN_MMD_EVERY = N is set, {} otherwise -- and always {} for the two state-space
-    scripts, which have no single code to compare"""
+# the set-level dev scores (the rows of evaluate.SET_SCORES: dev mmd, dev precision / recall / density / coverage, dev knn accuracy, dev
+# parzen ll, dev rec mse / psnr / ssim) are no pass of the reference's loops: each is off unless asked for, with a switch and a cadence of
+# its own outside EVAL_KEYS
+def score_settings(script):
+    """{'<NAME>_EVERY': N} for every row of evaluate.SET_SCORES whose $GGAN_<NAME>_EVERY = N is set and which the script has: the eight
+    image scripts have every row, the two state-space scripts those with `sequences` (dev rec alone: they have no single code or set of
+    images to compare), any other name none"""
     name = os.path.splitext(os.path.basename(script))[0]
-    every = os.environ.get('GGAN_MMD_EVERY')
-    if name not in _IMAGE_SCRIPTS or not every:
+    if name not in _IMAGE_SCRIPTS and name not in _SEQUENCE_SCRIPTS:
         return {}
-    return {'MMD_EVERY': int(every)}
+    rows = [r for r in SET_SCORES if name in _IMAGE_SCRIPTS or r.sequences is True]
+    return {r.every: int(os.environ['GGAN_' + r.every]) for r in rows if os.environ.get('GGAN_' + r.every)}
 
 
-def mmd_due(S, it):
-    """does the pass fire after iteration `it`: it % N == N - 1, the cadence of the other passes"""
-    n = int(S.get('MMD_EVERY') or 0)
-    return bool(n and it % n == n - 1)
-
-
-# the dev-set precision / recall / density / coverage scores (evaluate.Evaluator.prdc_scores): as the MMD scores, off unless asked for, a
-# switch and a cadence of their own
-def prdc_settings(script):
-    """{'PRDC_EVERY': N} for the eight image scripts when $GGAN_PRDC_EVERY = N is set, {} otherwise -- and always {} for the two state-space
-    scripts, which have no single code to compare"""
-    name = os.path.splitext(os.path.basename(script))[0]
-    every = os.environ.get('GGAN_PRDC_EVERY')
-    if name not in _IMAGE_SCRIPTS or not every:
-        return {}
-    return {'PRDC_EVERY': int(every)}
-
-
-def prdc_due(S, it):
-    """does the pass fire after iteration `it`: it % N == N - 1, the cadence of the other passes"""
-    n = int(S.get('PRDC_EVERY') or 0)
-    return bool(n and it % n == n - 1)
-
-
-# the dev-set k-NN accuracy of codes and of images (evaluate.Evaluator.knn_scores): as the two passes above, off unless asked for, a switch
-# and a cadence of their own; it needs a labelled dev set
-def knn_settings(script):
-    """{'KNN_EVERY': N} for the eight image scripts when $GGAN_KNN_EVERY = N is set, {} otherwise -- and always {} for the two state-space
-    scripts, which have no single code to compare"""
-    name = os.path.splitext(os.path.basename(script))[0]
-    every = os.environ.get('GGAN_KNN_EVERY')
-    if name not in _IMAGE_SCRIPTS or not every:
-        return {}
-    return {'KNN_EVERY': int(every)}
-
-
-def knn_due(S, it):
-    """does the pass fire after iteration `it`: it % N == N - 1, the cadence of the other passes"""
-    n = int(S.get('KNN_EVERY') or 0)
-    return bool(n and it % n == n - 1)
-
-
-# the Parzen-window log-likelihood of held-out dev images under generated ones (evaluate.Evaluator.parzen_scores): as the three passes
-# above, off unless asked for, a switch and a cadence of their own
-def parzen_settings(script):
-    """{'PARZEN_EVERY': N} for the eight image scripts when $GGAN_PARZEN_EVERY = N is set, {} otherwise -- and always {} for the two
-    state-space scripts, which have no single set of images to compare"""
-    name = os.path.splitext(os.path.basename(script))[0]
-    every = os.environ.get('GGAN_PARZEN_EVERY')
-    if name not in _IMAGE_SCRIPTS or not every:
-        return {}
-    return {'PARZEN_EVERY': int(every)}
-
-
-def parzen_due(S, it):
-    """does the pass fire after iteration `it`: it % N == N - 1, the cadence of the other passes"""
-    n = int(S.get('PARZEN_EVERY') or 0)
-    return bool(n and it % n == n - 1)
-
-
-# the reconstruction fidelity of the dev set (evaluate.Evaluator.rec_scores, evaluate.SequenceEvaluator.rec_scores): as the four passes
-# above, off unless asked for, a switch and a cadence of their own -- and the one set-level pass the two state-space scripts have too
-def rec_settings(script):
-    """{'REC_EVERY': N} for the ten scripts when $GGAN_REC_EVERY = N is set, {} otherwise"""
-    name = os.path.splitext(os.path.basename(script))[0]
-    every = os.environ.get('GGAN_REC_EVERY')
-    if (name not in _IMAGE_SCRIPTS and name not in _SEQUENCE_SCRIPTS) or not every:
-        return {}
-    return {'REC_EVERY': int(every)}
-
-
-def rec_due(S, it):
-    """does the pass fire after iteration `it`: it % N == N - 1, the cadence of the other passes"""
-    n = int(S.get('REC_EVERY') or 0)
-    return bool(n and it % n == n - 1)
+def scores_due(S, it):
+    """the names of the rows of evaluate.SET_SCORES that fire after iteration `it`, in the table's order: it % N == N - 1, the cadence of the
+    other passes"""
+    every = ((r.name, int(S.get(r.every) or 0)) for r in SET_SCORES)
+    return tuple(name for name, n in every if n and it % n == n - 1)
 
 
 # an exponential moving average of the generator-side weights (engine.Trainer's ema_decay), kept on the device inside the steps and used by
@@ -467,61 +402,52 @@ def train(S, cfg, model=None, out_dir=None):
     if timed:
         ev0 = torch.cuda.Event(enable_timing=True)
         ev0.record(torch.cuda.current_stream(device))
-    plan = eval_plan(S)
-    evaluator = None
-    if plan and (tr.world == 1 or torch.distributed.get_rank() == 0):     # (replicas: rank 0 evaluates and logs)
-        from .evaluate import Evaluator, SequenceEvaluator
-        from .models_ssgan import StateSpaceGAN
-        sequences = isinstance(tr.model, StateSpaceGAN)
-        if sequences and not out_dir:
-            print('[run] video passes skipped: no OUT_DIR to write them to')
-            plan = None
-    if plan and (tr.world == 1 or torch.distributed.get_rank() == 0):
-        evaluator = (SequenceEvaluator if sequences else Evaluator)(tr, S)
-        ev_dev, ev_test = eval_sets(S, tr.model, device)
-        evaluator.set_fixed_data(ev_dev[0])
-        if 'ACCURACY_EVERY' in plan and (ev_test is None or not tr.cfg.K):
+    lead = tr.world == 1 or torch.distributed.get_rank() == 0          # (replicas: rank 0 evaluates and logs)
+    sequences = isinstance(tr.model, StateSpaceGAN)
+    # the reference's passes, the latent-space pictures and the set-level scores share ONE evaluator and ONE eval_sets call per run, each
+    # made when the first pass that is on needs it
+    the_eval = functools.lru_cache(None)(lambda: (SequenceEvaluator if sequences else Evaluator)(tr, S))
+    the_sets = functools.lru_cache(None)(lambda: eval_sets(S, tr.model, device))
+    plan = eval_plan(S) if lead else None
+    if plan and sequences and not out_dir:
+        print('[run] video passes skipped: no OUT_DIR to write them to')
+        plan = None
+    if plan:
+        the_eval().set_fixed_data(the_sets()[0][0])
+        if 'ACCURACY_EVERY' in plan and (the_sets()[1] is None or not tr.cfg.K):
             print('[run] testing accuracy skipped: %s' % ('no mixture prior (N_COMS)' if not tr.cfg.K else 'no labelled test set (%s data)' % source))
             plan.pop('ACCURACY_EVERY')
-    manifold = manifold_plan(S) if (tr.world == 1 or torch.distributed.get_rank() == 0) else None
+    manifold = manifold_plan(S) if lead else None
     if manifold:
-        from .evaluate import Evaluator
-        from .models_ssgan import StateSpaceGAN
-        m_dev = None
-        if isinstance(tr.model, StateSpaceGAN) or tr.cfg.dataset != 'mnist':
+        if sequences or tr.cfg.dataset != 'mnist':
             why = 'a pass of the MNIST scripts only'
         elif not out_dir:
             why = 'no OUT_DIR to write the pictures to'
         else:
-            m_dev = ev_dev if evaluator is not None else eval_sets(S, tr.model, device)[0]
-            why = None if labelled(m_dev) else 'no labelled dev set (%s data)' % source
+            why = None if labelled(the_sets()[0]) else 'no labelled dev set (%s data)' % source
         if why:
             print('[run] latent-space t-SNE skipped: %s' % why)
             manifold = None
-        else:
-            m_eval = evaluator if evaluator is not None else Evaluator(tr, S)
-    # the evaluator of the set-level scores: dev mmd (MMD_EVERY), dev precision / ... / coverage (PRDC_EVERY), dev knn accuracy (KNN_EVERY),
-    # dev parzen ll / se / sigma (PARZEN_EVERY), dev rec mse / psnr / ssim / ssim se (REC_EVERY: the state-space scripts too, through
-    # their own evaluator and on dev minibatches of their own)
-    mmd_eval, knn_on, rec_eval = None, False, None
-    if (S.get('MMD_EVERY') or S.get('PRDC_EVERY') or S.get('KNN_EVERY') or S.get('PARZEN_EVERY') or S.get('REC_EVERY')) and (tr.world == 1 or torch.distributed.get_rank() == 0):
-        from .evaluate import Evaluator, SequenceEvaluator
-        from .models_ssgan import StateSpaceGAN
-        if isinstance(tr.model, StateSpaceGAN) and S.get('REC_EVERY'):
-            rec_eval = evaluator if evaluator is not None else SequenceEvaluator(tr, S)
+    # the set-level scores that are on (the rows of evaluate.SET_SCORES with an <NAME>_EVERY).  The state-space scripts have dev rec alone,
+    # through their own evaluator and on dev minibatches of their own
+    on = set(r.name for r in SET_SCORES if S.get(r.every)) if lead else set()
+    if on and sequences:
+        if 'rec' in on:
+            the_eval()
             rec_dev = rec_sequences(S, tr.model, device)
-        if isinstance(tr.model, StateSpaceGAN):
-            if S.get('MMD_EVERY') or S.get('PRDC_EVERY') or S.get('KNN_EVERY') or S.get('PARZEN_EVERY'):
-                print('[run] %s skipped: the state-space models have no single code to compare'
-                      % ' and '.join(n for n, key in (('dev mmd', 'MMD_EVERY'), ('dev precision / recall / density / coverage', 'PRDC_EVERY'),
-                                                        ('dev knn accuracy', 'KNN_EVERY'), ('dev parzen ll', 'PARZEN_EVERY')) if S.get(key)))
-        else:
-            mmd_eval = evaluator if evaluator is not None else (m_eval if manifold else Evaluator(tr, S))
-            mmd_dev = ev_dev if evaluator is not None else (m_dev if manifold else eval_sets(S, tr.model, device)[0])
-            knn_on = bool(S.get('KNN_EVERY'))
-            if knn_on and not labelled(mmd_dev):
-                print('[run] dev knn accuracy skipped: no labelled dev set (%s data)' % source)
-                knn_on = False
+        skipped = [r.title for r in SET_SCORES if r.name in on and r.sequences is not True]
+        if skipped:
+            print('[run] %s skipped: the state-space models have no single code to compare' % ' and '.join(skipped))
+        on &= {'rec'}
+    elif on:
+        the_eval()
+        for r in SET_SCORES:
+            if r.name in on and 'labels' in r.needs and not labelled(the_sets()[0]):
+                print('[run] %s skipped: no labelled dev set (%s data)' % (r.title, source))
+                on.discard(r.name)
+    ev = the_eval() if plan or manifold or on else None
+    ev_dev, ev_test = the_sets() if plan or manifold or (on and not sequences) else (None, None)
+    flush = lambda: lib.plot.flush(out_dir, os.path.join(out_dir, 'logfile.txt') if out_dir else None)
     eval_ms = 0.0            # wall time of the evaluation passes (kept out of `time`)
     for it in range(S['ITERS']):
         if (it == 2 and isinstance(batches, DevicePrefetcher) and S.get('RING_FEED', True) and tr.graph_enabled
@@ -534,34 +460,29 @@ def train(S, cfg, model=None, out_dir=None):
             for k, v in res.items():
                 lib.plot.plot(k.replace('_', ' '), float(v))
             if timed:
-                ev = torch.cuda.Event(enable_timing=True)
-                ev.record(torch.cuda.current_stream(device))
-                ev.synchronize()
-                lib.plot.plot('time', (ev0.elapsed_time(ev) - eval_ms) * 1e-3 / (it + 1))
+                ev1 = torch.cuda.Event(enable_timing=True)
+                ev1.record(torch.cuda.current_stream(device))
+                ev1.synchronize()
+                lib.plot.plot('time', (ev0.elapsed_time(ev1) - eval_ms) * 1e-3 / (it + 1))
             else:
                 lib.plot.plot('time', (time.time() - t0 - eval_ms * 1e-3) / (it + 1))
-            lib.plot.flush(out_dir, os.path.join(out_dir, 'logfile.txt') if out_dir else None)
-        due = eval_due(plan, it) if evaluator is not None else ()
+            flush()
+        due = eval_due(plan, it)
         if due:
             for w in passes:
-                with _on_weights(evaluator, w):
-                    eval_ms += _evaluate(evaluator, due, ev_dev, ev_test, it, out_dir, device, tr)
-            lib.plot.flush(out_dir, os.path.join(out_dir, 'logfile.txt') if out_dir else None)
+                with _on_weights(ev, w):
+                    eval_ms += _timed(device, lambda: _evaluate(ev, due, ev_dev, ev_test, it, out_dir, tr))
+            flush()
         if manifold_due(manifold, it, S['ITERS']):
             for w in passes:
-                with _on_weights(m_eval, w):
-                    eval_ms += _manifold(m_eval, m_dev, it, out_dir, device)
-        if mmd_eval is not None and (mmd_due(S, it) or prdc_due(S, it) or (knn_on and knn_due(S, it)) or parzen_due(S, it) or rec_due(S, it)):
+                with _on_weights(ev, w):
+                    eval_ms += _timed(device, lambda: ev.manifold(ev_dev, out_dir, it))
+        scores = dict.fromkeys((name for name in scores_due(S, it) if name in on), True)
+        if scores:          # (one build of the sets for the image scores that are due; the sequences' frames for dev rec)
             for w in passes:
-                with _on_weights(mmd_eval, w):
-                    eval_ms += _set_scores(mmd_eval, mmd_dev, device, mmd_due(S, it), prdc_due(S, it), knn_on and knn_due(S, it),
-                                           parzen_due(S, it), rec_due(S, it))
-            lib.plot.flush(out_dir, os.path.join(out_dir, 'logfile.txt') if out_dir else None)
-        if rec_eval is not None and rec_due(S, it):
-            for w in passes:
-                with _on_weights(rec_eval, w):
-                    eval_ms += _rec_sequences(rec_eval, rec_dev, device)
-            lib.plot.flush(out_dir, os.path.join(out_dir, 'logfile.txt') if out_dir else None)
+                with _on_weights(ev, w):
+                    eval_ms += _timed(device, lambda: _plot(ev.tag(ev.rec_scores(rec_dev) if sequences else ev.set_scores(ev_dev, **scores))))
+            flush()
         lib.plot.tick()
         if out_dir and S.get('SAVE_EVERY') and (it + 1) % S['SAVE_EVERY'] == 0:
             checkpoint.save(os.path.join(out_dir, 'params_%d.npz' % (it + 1)), tr, data_source=source)
@@ -587,60 +508,32 @@ def _save_samples(tr, cfg, path):
     lib.save_images.save_images(np.clip((fx - lo) / (1.0 - lo), 0, 1), path)
 
 
-def _evaluate(ev, due, dev, test, it, out_dir, device, tr=None):
-    """the passes due after iteration `it`, logged through lib.plot under the reference's names -> milliseconds they took"""
-    from .evaluate import SequenceEvaluator
+def _timed(device, fn):
+    """fn() between two synchronisations of the device (the training work queued so far is not its time) -> milliseconds it took"""
     if device.type == 'cuda':
-        torch.cuda.synchronize(device)          # (the training work queued so far is not the passes' time)
+        torch.cuda.synchronize(device)
     t0 = time.time()
+    fn()
+    if device.type == 'cuda':
+        torch.cuda.synchronize(device)
+    return (time.time() - t0) * 1e3
+
+
+def _plot(values):
+    """a pass's {name: value} through lib.plot, in the pass's order"""
+    for k, v in values.items():
+        lib.plot.plot(k, v)
+
+
+def _evaluate(ev, due, dev, test, it, out_dir, tr=None):
+    """the passes due after iteration `it`, logged through lib.plot under the reference's names"""
     if 'DEV_EVERY' in due:
-        for k, v in ev.tag(ev.dev_costs(dev)).items():
-            lib.plot.plot(k, v)
+        _plot(ev.tag(ev.dev_costs(dev)))
     if 'ACCURACY_EVERY' in due:
-        for k, v in ev.tag({'testing accuracy': ev.cluster_accuracy(test)}).items():
-            lib.plot.plot(k, v)
+        _plot(ev.tag({'testing accuracy': ev.cluster_accuracy(test)}))
     if 'SAMPLE_EVERY' in due and out_dir:
         if isinstance(ev, SequenceEvaluator):
             # generate_video(iteration, _data): the minibatch of the last critic step, still in the Trainer's feed buffer (read only)
             ev.save_videos(out_dir, it, train_data=tr.feed['real_x_unit'])
         else:
             ev.save_images(out_dir, it)
-    if device.type == 'cuda':
-        torch.cuda.synchronize(device)
-    return (time.time() - t0) * 1e3
-
-
-def _manifold(ev, dev, it, out_dir, device):
-    """the latent-space pictures after iteration `it` -> milliseconds they took"""
-    if device.type == 'cuda':
-        torch.cuda.synchronize(device)
-    t0 = time.time()
-    ev.manifold(dev, out_dir, it)
-    if device.type == 'cuda':
-        torch.cuda.synchronize(device)
-    return (time.time() - t0) * 1e3
-
-
-def _set_scores(ev, dev, device, mmd, prdc, knn=False, parzen=False, rec=False):
-    """the dev-set MMD^2, precision / recall / density / coverage, k-NN accuracy, Parzen-window and reconstruction scores that are due, from
-    one build of the sets, logged through lib.plot -> milliseconds they took"""
-    if device.type == 'cuda':
-        torch.cuda.synchronize(device)
-    t0 = time.time()
-    for k, v in ev.tag(ev.set_scores(dev, mmd=mmd, prdc=prdc, knn=knn, parzen=parzen, rec=rec)).items():
-        lib.plot.plot(k, v)
-    if device.type == 'cuda':
-        torch.cuda.synchronize(device)
-    return (time.time() - t0) * 1e3
-
-
-def _rec_sequences(ev, dev, device):
-    """the state-space scripts' reconstruction scores of the dev sequences' frames, logged through lib.plot -> milliseconds they took"""
-    if device.type == 'cuda':
-        torch.cuda.synchronize(device)
-    t0 = time.time()
-    for k, v in ev.tag(ev.rec_scores(dev)).items():
-        lib.plot.plot(k, v)
-    if device.type == 'cuda':
-        torch.cuda.synchronize(device)
-    return (time.time() - t0) * 1e3

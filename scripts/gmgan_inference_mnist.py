@@ -14,11 +14,7 @@ SETTINGS = run.reference_block(__file__, MODE=MODE, MODE_K=MODE_K)
 SETTINGS.update(DATA_DIR=os.environ.get('GGAN_DATA_DIR', ''), OUT_DIR=os.environ.get('GGAN_OUT_DIR', ''), SAVE_EVERY=10000, LOG_EVERY=100)
 SETTINGS.update(run.eval_settings(__file__))     # dev costs / samples / reconstructions (/ testing accuracy) at the reference's cadence
 SETTINGS.update(run.manifold_settings(__file__)) # the latent-space t-SNE pictures: once, after the last iteration
-SETTINGS.update(run.mmd_settings(__file__))      # dev mmd z / dev mmd x every $GGAN_MMD_EVERY iterations (off when unset)
-SETTINGS.update(run.prdc_settings(__file__))     # dev precision / recall / density / coverage z / x every $GGAN_PRDC_EVERY iterations (off when unset)
-SETTINGS.update(run.knn_settings(__file__))      # dev knn accuracy z / x every $GGAN_KNN_EVERY iterations (off when unset; needs a labelled dev set)
-SETTINGS.update(run.parzen_settings(__file__))   # dev parzen ll / se / sigma x every $GGAN_PARZEN_EVERY iterations (off when unset)
-SETTINGS.update(run.rec_settings(__file__))      # dev rec mse / psnr / ssim / ssim se x every $GGAN_REC_EVERY iterations (off when unset)
+SETTINGS.update(run.score_settings(__file__))   # the set-level dev scores, off when unset: every $GGAN_MMD_EVERY / $GGAN_PRDC_EVERY / $GGAN_KNN_EVERY / $GGAN_PARZEN_EVERY / $GGAN_REC_EVERY iterations
 SETTINGS.update(run.ema_settings(__file__))      # $GGAN_EMA_DECAY: average the generator-side weights; $GGAN_EMA_EVAL = live | ema | both: which the passes score
 if len(sys.argv) > 1:
     SETTINGS['ITERS'] = int(sys.argv[1])

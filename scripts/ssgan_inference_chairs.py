@@ -12,7 +12,7 @@ BN_FLAG = False  # BatchNorm in the frame generator, extractors and critics (BN_
 SETTINGS = run.reference_block(__file__, MODE=MODE, BN_FLAG=BN_FLAG)
 # edit the block here, e.g. SETTINGS['N_COMS'] = 10 -- or pass it to reference_block, which then derives N_VIS etc. from it
 SETTINGS.update(run.eval_settings(__file__))  # the video passes every 5000 iterations: samples / train_data / reconstruction / disentangle
-SETTINGS.update(run.rec_settings(__file__))      # dev rec mse / psnr / ssim / ssim se x every $GGAN_REC_EVERY iterations (off when unset)
+SETTINGS.update(run.score_settings(__file__))   # the set-level dev scores, off when unset: dev rec mse / psnr / ssim / ssim se x every $GGAN_REC_EVERY iterations (the other four are the image scripts')
 SETTINGS.update(run.ema_settings(__file__))      # $GGAN_EMA_DECAY: average the generator-side weights; $GGAN_EMA_EVAL = live | ema | both: which the passes score
 SETTINGS.update(DATA_DIR=os.environ.get('GGAN_DATA_DIR', ''), OUT_DIR=os.environ.get('GGAN_OUT_DIR', ''), SAVE_EVERY=10000, LOG_EVERY=100)
 if len(sys.argv) > 1:

@@ -535,6 +535,8 @@ def test_environment_switches_match_the_integration_table():
                 if fn.endswith(('.py', '.hip', '.h')):
                     with open(os.path.join(d, fn)) as f:
                         used.update(re.findall(r'''['"](GGAN_[A-Z0-9_]+)['"]''', f.read()))
+    from graphical_gan_amd import evaluate
+    used.update('GGAN_%s_EVERY' % r.name.upper() for r in evaluate.SET_SCORES)         # (run.score_settings spells these from the table's names)
     with open(os.path.join(root, 'INTEGRATION.md')) as f:
         text = f.read()
     section = text[text.index('## 6. '):]

@@ -1,9 +1,8 @@
 """not-gpu: the labelled neighbour-list ops' ABI (header, binding, built library, argument errors without a GPU), what the Python ops
-refuse, the cadence settings of the dev-set k-NN accuracy pass, the scripts' new line, and the float64 restatement tests/_knn_ref.py: its
+refuse, the cadence settings of the dev-set k-NN accuracy pass, and the float64 restatement tests/_knn_ref.py: its
 known answers on a hand-made case and the conditions on the inputs under which the GPU tests' closed-row rule can hide little."""
 import contextlib
 import ctypes as C
-import glob
 import os
 import re
 import sys
@@ -19,6 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ('ggan_knn_lists_workspace', 'ggan_knn_lists', 'ggan_knn_vote')
 IMAGE_SCRIPTS = ['%s_inference_%s' % (f, d) for f in ('gan', 'gmgan') for d in ('cifar10', 'svhn', 'mnist', 'face')]
 SEQUENCE_SCRIPTS = ['ssgan_inference_moving_mnist', 'ssgan_inference_chairs']
+SCORE_VARS = ['GGAN_%s_EVERY' % n for n in ('MMD', 'PRDC', 'KNN', 'PARZEN', 'REC')]
 
 
 # ---- the restatement -------------------------------------------------------------------------------------------------------------------
@@ -171,44 +171,33 @@ def test_python_ops_refuse_what_they_cannot_do(lib_built):
 def test_knn_settings_and_cadence(monkeypatch):
     from graphical_gan_amd import run
     every = IMAGE_SCRIPTS + SEQUENCE_SCRIPTS
-    for v in ('GGAN_KNN_EVERY', 'GGAN_PRDC_EVERY', 'GGAN_MMD_EVERY'):
+    for v in SCORE_VARS:
         monkeypatch.delenv(v, raising=False)
-    base = {s: (run.eval_settings(s), run.manifold_settings(s), run.mmd_settings(s), run.prdc_settings(s)) for s in every}
+    base = {s: (run.eval_settings(s), run.manifold_settings(s)) for s in every}
     for s in every:
-        assert run.knn_settings(s) == {} and run.knn_settings('/somewhere/%s.py' % s) == {}
+        assert run.score_settings(s) == {} and run.score_settings('/somewhere/%s.py' % s) == {}
     monkeypatch.setenv('GGAN_KNN_EVERY', '20')
-    for s in IMAGE_SCRIPTS:
-        assert run.knn_settings(s) == {'KNN_EVERY': 20} and run.knn_settings('/somewhere/%s.py' % s) == {'KNN_EVERY': 20}
+    for s in IMAGE_SCRIPTS:                    # (exactly the one key: no other score learns the variable)
+        assert run.score_settings(s) == {'KNN_EVERY': 20} and run.score_settings('/somewhere/%s.py' % s) == {'KNN_EVERY': 20}
     for s in SEQUENCE_SCRIPTS:
-        assert run.knn_settings(s) == {}
+        assert run.score_settings(s) == {}
     for s in every:                 # the other settings functions do not learn the variable, and the key is in no *_KEYS
-        assert (run.eval_settings(s), run.manifold_settings(s), run.mmd_settings(s), run.prdc_settings(s)) == base[s]
+        assert (run.eval_settings(s), run.manifold_settings(s)) == base[s]
     assert 'KNN_EVERY' not in run.EVAL_KEYS and 'KNN_EVERY' not in run.MANIFOLD_KEYS
-    S = dict(run.reference_block('gan_inference_cifar10'), **run.knn_settings('gan_inference_cifar10'))
+    S = dict(run.reference_block('gan_inference_cifar10'), **run.score_settings('gan_inference_cifar10'))
     assert run.eval_plan(S) is None and run.manifold_plan(S) is None
-    assert [it for it in range(60) if run.knn_due(S, it)] == [19, 39, 59]
-    assert not any(run.mmd_due(S, it) or run.prdc_due(S, it) for it in range(60))
-    assert not any(run.knn_due(run.reference_block('gan_inference_cifar10'), it) for it in range(60))
+    assert [it for it in range(60) if 'knn' in run.scores_due(S, it)] == [19, 39, 59]
+    assert not any('mmd' in run.scores_due(S, it) or 'prdc' in run.scores_due(S, it) for it in range(60))
+    assert all(run.scores_due(S, it) in ((), ('knn',)) for it in range(60))              # no other score fires
+    assert not any(run.scores_due(run.reference_block('gan_inference_cifar10'), it) for it in range(60))
     monkeypatch.delenv('GGAN_KNN_EVERY')
     monkeypatch.setenv('GGAN_PRDC_EVERY', '20')
     for s in every:
-        assert run.knn_settings(s) == {}
-
-
-def test_the_eight_image_scripts_carry_the_line():
-    line = 'SETTINGS.update(run.knn_settings(__file__))'
-    seen = {}
-    for path in glob.glob(os.path.join(ROOT, 'scripts', '*_inference_*.py')):
-        seen[os.path.splitext(os.path.basename(path))[0]] = open(path).read().count(line)
-    assert sorted(seen) == sorted(IMAGE_SCRIPTS + SEQUENCE_SCRIPTS)
-    assert all(seen[s] == 1 for s in IMAGE_SCRIPTS) and all(seen[s] == 0 for s in SEQUENCE_SCRIPTS)
+        assert 'KNN_EVERY' not in run.score_settings(s)
 
 
 def test_evaluate_once_and_cli_default_to_no_knn():
-    import inspect
     from graphical_gan_amd import evaluate
-    assert inspect.signature(evaluate.evaluate_once).parameters['knn'].default is False
-    assert inspect.signature(evaluate.Evaluator.set_scores).parameters['knn'].default is False
     assert evaluate.KNN_MAX_ROWS == 10000 and evaluate.KNN_K == 5
     with pytest.raises(SystemExit):            # refused before anything is built
         evaluate.main(['nowhere.npz', '--script', 'ssgan_inference_chairs', '--out-dir', 'x', '--knn'])

@@ -1,5 +1,6 @@
 """not-gpu: the set-level MMD op's ABI (header, binding, built library, argument errors without a GPU), the cadence settings of the
-dev-set MMD pass, the scripts' new line, and the float64 restatement tests/_mmd_ref.py against the oracle and the reference's formula."""
+dev-set MMD pass and of the five set-level scores together, their table, the scripts' one line for them, and the float64 restatement tests/_mmd_ref.py against the oracle and the reference's formula."""
+import argparse
 import ctypes as C
 import glob
 import os
@@ -89,46 +90,95 @@ def test_python_ops_refuse_what_they_cannot_do(lib_built):
         lib.objs.mmd.mix_rbf_mmd2(torch.zeros(400, 3, requires_grad=True), torch.zeros(200, 3))
 
 
+SCORE_VARS = ['GGAN_%s_EVERY' % n for n in ('MMD', 'PRDC', 'KNN', 'PARZEN', 'REC')]
+
+
 def test_mmd_settings_and_cadence(monkeypatch):
     from graphical_gan_amd import run
-    monkeypatch.delenv('GGAN_MMD_EVERY', raising=False)
+    for v in SCORE_VARS:
+        monkeypatch.delenv(v, raising=False)
     base_eval = {s: run.eval_settings(s) for s in IMAGE_SCRIPTS + SEQUENCE_SCRIPTS}
     base_man = {s: run.manifold_settings(s) for s in IMAGE_SCRIPTS + SEQUENCE_SCRIPTS}
     for s in IMAGE_SCRIPTS + SEQUENCE_SCRIPTS:
-        assert run.mmd_settings(s) == {} and run.mmd_settings('/somewhere/%s.py' % s) == {}
+        assert run.score_settings(s) == {} and run.score_settings('/somewhere/%s.py' % s) == {}
     monkeypatch.setenv('GGAN_MMD_EVERY', '20')
     for s in IMAGE_SCRIPTS:
-        assert run.mmd_settings(s) == {'MMD_EVERY': 20} and run.mmd_settings('/somewhere/%s.py' % s) == {'MMD_EVERY': 20}
+        assert run.score_settings(s) == {'MMD_EVERY': 20} and run.score_settings('/somewhere/%s.py' % s) == {'MMD_EVERY': 20}
     for s in SEQUENCE_SCRIPTS:
-        assert run.mmd_settings(s) == {}
+        assert run.score_settings(s) == {}
     # the other settings functions do not learn the variable, and the key is no EVAL_KEY
     for s in IMAGE_SCRIPTS + SEQUENCE_SCRIPTS:
         assert run.eval_settings(s) == base_eval[s] and run.manifold_settings(s) == base_man[s]
         assert 'MMD_EVERY' not in run.eval_settings(s)
     assert 'MMD_EVERY' not in run.EVAL_KEYS and 'MMD_EVERY' not in run.MANIFOLD_KEYS
-    S = dict(run.reference_block('gan_inference_cifar10'), **run.mmd_settings('gan_inference_cifar10'))
+    S = dict(run.reference_block('gan_inference_cifar10'), **run.score_settings('gan_inference_cifar10'))
     assert run.eval_plan(S) is None and run.manifold_plan(S) is None
-    assert [it for it in range(60) if run.mmd_due(S, it)] == [19, 39, 59]
-    assert not any(run.mmd_due(run.reference_block('gan_inference_cifar10'), it) for it in range(60))
+    assert [it for it in range(60) if 'mmd' in run.scores_due(S, it)] == [19, 39, 59]
+    assert all(run.scores_due(S, it) in ((), ('mmd',)) for it in range(60))              # no other score fires
+    assert not any(run.scores_due(run.reference_block('gan_inference_cifar10'), it) for it in range(60))
 
 
-def test_the_eight_image_scripts_carry_the_line():
-    line = 'SETTINGS.update(run.mmd_settings(__file__))'
+def test_all_five_switches_at_once(monkeypatch):
+    """distinct values: an image script gets the five keys with their own values, a state-space script REC_EVERY alone, and where several
+    cadences coincide scores_due names them in the table's order"""
+    from graphical_gan_amd import run
+    for v, n in zip(SCORE_VARS, (2, 3, 4, 6, 12)):
+        monkeypatch.setenv(v, str(n))
+    want = dict(MMD_EVERY=2, PRDC_EVERY=3, KNN_EVERY=4, PARZEN_EVERY=6, REC_EVERY=12)
+    for s in IMAGE_SCRIPTS:
+        assert run.score_settings(s) == want and list(run.score_settings(s)) == list(want)
+    for s in SEQUENCE_SCRIPTS:
+        assert run.score_settings(s) == {'REC_EVERY': 12}
+    assert run.score_settings('no_such_script') == {}
+    assert run.scores_due(want, 11) == ('mmd', 'prdc', 'knn', 'parzen', 'rec')
+    assert run.scores_due(want, 5) == ('mmd', 'prdc', 'parzen') and run.scores_due(want, 3) == ('mmd', 'knn')
+    assert run.scores_due(want, 1) == ('mmd',) and run.scores_due(want, 0) == () and run.scores_due(want, 2) == ('prdc',)
+    assert run.scores_due(dict(reversed(list(want.items()))), 11) == ('mmd', 'prdc', 'knn', 'parzen', 'rec')      # (the table's order, not the block's)
+
+
+def test_the_ten_scripts_carry_the_line():
+    """each script carries the score_settings line exactly once and names no per-score settings function (which script gets which score:
+    the score_settings tests)"""
+    line = 'SETTINGS.update(run.score_settings(__file__))'
     seen = {}
     for path in glob.glob(os.path.join(ROOT, 'scripts', '*_inference_*.py')):
-        seen[os.path.splitext(os.path.basename(path))[0]] = open(path).read().count(line)
+        text = open(path).read()
+        seen[os.path.splitext(os.path.basename(path))[0]] = text.count(line)
+        assert not re.search(r'(mmd|prdc|knn|parzen|rec)_(settings|due)', text), path
     assert sorted(seen) == sorted(IMAGE_SCRIPTS + SEQUENCE_SCRIPTS)
-    for s in IMAGE_SCRIPTS:
-        assert seen[s] == 1, s
-    for s in SEQUENCE_SCRIPTS:
-        assert seen[s] == 0, s
+    assert all(n == 1 for n in seen.values()), seen
+
+
+def test_the_table_and_its_keywords(monkeypatch):
+    """the five scores are rows of one table, in the logged order; each is off unless asked for, by flag or by keyword, and a keyword that
+    is no row is refused"""
+    from graphical_gan_amd import evaluate
+    assert [r.name for r in evaluate.SET_SCORES] == ['mmd', 'prdc', 'knn', 'parzen', 'rec']
+    parsed, real = [], argparse.ArgumentParser.parse_args
+
+    def parse(self, argv=None):                # (main's own parser, stopped once it has read the command line)
+        parsed.append(real(self, argv))
+        raise SystemExit(0)
+    monkeypatch.setattr(argparse.ArgumentParser, 'parse_args', parse)
+    for flags in ([], ['--knn']):
+        with pytest.raises(SystemExit):
+            evaluate.main(['nowhere.npz', '--script', 'gan_inference_mnist'] + flags)
+    for r in evaluate.SET_SCORES:
+        assert getattr(parsed[0], r.name) is False and getattr(parsed[1], r.name) is (r.name == 'knn'), r.name
+    xs = [np.zeros((4, 6), np.float32)]
+    ev = object.__new__(evaluate.Evaluator)
+    with pytest.raises(ValueError, match='no score was asked for'):
+        ev.set_scores(xs)
+    with pytest.raises(ValueError, match='no score was asked for'):
+        ev.set_scores(xs, mmd=False, rec=False)
+    with pytest.raises(TypeError, match='mmd, prdc, knn, parzen, rec'):
+        ev.set_scores(xs, fid=True)
+    with pytest.raises(TypeError, match='mmd, prdc, knn, parzen, rec'):
+        evaluate.evaluate_once(None, {}, fid=True)
 
 
 def test_evaluate_once_and_cli_default_to_no_mmd():
-    import inspect
     from graphical_gan_amd import evaluate
-    sig = inspect.signature(evaluate.evaluate_once)
-    assert sig.parameters['mmd'].default is False
     assert hasattr(evaluate.Evaluator, 'mmd_scores') and evaluate.MMD_MAX_ROWS == 10000
     with pytest.raises(SystemExit):            # refused before anything is built
         evaluate.main(['nowhere.npz', '--script', 'ssgan_inference_chairs', '--out-dir', 'x', '--mmd'])

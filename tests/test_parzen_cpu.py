@@ -1,10 +1,9 @@
 """not-gpu: the Parzen-window op's ABI (header, binding, built library, argument errors without a GPU), what the Python ops refuse, the
-cadence settings of the dev-set Parzen pass, the scripts' new line, what the pass refuses before any device work, and the float64
+cadence settings of the dev-set Parzen pass, what the pass refuses before any device work, and the float64
 restatement tests/_parzen_ref.py: its known answers by hand and the conditions on the shared cases under which the GPU tests test
 something (a dropped candidate shows; an unshifted sum is log 0)."""
 import contextlib
 import ctypes as C
-import glob
 import os
 import re
 import sys
@@ -20,6 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ('ggan_parzen_lse_workspace', 'ggan_parzen_lse')
 IMAGE_SCRIPTS = ['%s_inference_%s' % (f, d) for f in ('gan', 'gmgan') for d in ('cifar10', 'svhn', 'mnist', 'face')]
 SEQUENCE_SCRIPTS = ['ssgan_inference_moving_mnist', 'ssgan_inference_chairs']
+SCORE_VARS = ['GGAN_%s_EVERY' % n for n in ('MMD', 'PRDC', 'KNN', 'PARZEN', 'REC')]
 
 
 # ---- the restatement -------------------------------------------------------------------------------------------------------------------
@@ -149,46 +149,34 @@ def test_python_ops_refuse_what_they_cannot_do(lib_built):
 def test_parzen_settings_and_cadence(monkeypatch):
     from graphical_gan_amd import run
     every = IMAGE_SCRIPTS + SEQUENCE_SCRIPTS
-    for v in ('GGAN_PARZEN_EVERY', 'GGAN_KNN_EVERY', 'GGAN_PRDC_EVERY', 'GGAN_MMD_EVERY'):
+    for v in SCORE_VARS:
         monkeypatch.delenv(v, raising=False)
-    others = lambda s: (run.eval_settings(s), run.manifold_settings(s), run.mmd_settings(s), run.prdc_settings(s), run.knn_settings(s))
+    others = lambda s: (run.eval_settings(s), run.manifold_settings(s))
     base = {s: others(s) for s in every}
     for s in every:
-        assert run.parzen_settings(s) == {} and run.parzen_settings('/somewhere/%s.py' % s) == {}
+        assert run.score_settings(s) == {} and run.score_settings('/somewhere/%s.py' % s) == {}
     monkeypatch.setenv('GGAN_PARZEN_EVERY', '20')
-    for s in IMAGE_SCRIPTS:
-        assert run.parzen_settings(s) == {'PARZEN_EVERY': 20} and run.parzen_settings('/somewhere/%s.py' % s) == {'PARZEN_EVERY': 20}
+    for s in IMAGE_SCRIPTS:                    # (exactly the one key: no other score learns the variable)
+        assert run.score_settings(s) == {'PARZEN_EVERY': 20} and run.score_settings('/somewhere/%s.py' % s) == {'PARZEN_EVERY': 20}
     for s in SEQUENCE_SCRIPTS:
-        assert run.parzen_settings(s) == {}
+        assert run.score_settings(s) == {}
     for s in every:                 # the other settings functions do not learn the variable, and the key is in no *_KEYS
         assert others(s) == base[s]
     assert 'PARZEN_EVERY' not in run.EVAL_KEYS and 'PARZEN_EVERY' not in run.MANIFOLD_KEYS
-    S = dict(run.reference_block('gan_inference_mnist'), **run.parzen_settings('gan_inference_mnist'))
+    S = dict(run.reference_block('gan_inference_mnist'), **run.score_settings('gan_inference_mnist'))
     assert run.eval_plan(S) is None and run.manifold_plan(S) is None
-    assert [it for it in range(60) if run.parzen_due(S, it)] == [19, 39, 59]
-    assert not any(run.mmd_due(S, it) or run.prdc_due(S, it) or run.knn_due(S, it) for it in range(60))
-    assert not any(run.parzen_due(run.reference_block('gan_inference_mnist'), it) for it in range(60))
+    assert [it for it in range(60) if 'parzen' in run.scores_due(S, it)] == [19, 39, 59]
+    assert not any(set(run.scores_due(S, it)) & {'mmd', 'prdc', 'knn'} for it in range(60))
+    assert all(run.scores_due(S, it) in ((), ('parzen',)) for it in range(60))           # no other score fires
+    assert not any(run.scores_due(run.reference_block('gan_inference_mnist'), it) for it in range(60))
     monkeypatch.delenv('GGAN_PARZEN_EVERY')
     monkeypatch.setenv('GGAN_KNN_EVERY', '20')
     for s in every:
-        assert run.parzen_settings(s) == {}
-
-
-def test_the_eight_image_scripts_carry_the_line():
-    line = 'SETTINGS.update(run.parzen_settings(__file__))'
-    seen = {}
-    for path in glob.glob(os.path.join(ROOT, 'scripts', '*_inference_*.py')):
-        seen[os.path.splitext(os.path.basename(path))[0]] = open(path).read().count(line)
-    assert sorted(seen) == sorted(IMAGE_SCRIPTS + SEQUENCE_SCRIPTS)
-    assert all(seen[s] == 1 for s in IMAGE_SCRIPTS) and all(seen[s] == 0 for s in SEQUENCE_SCRIPTS)
+        assert 'PARZEN_EVERY' not in run.score_settings(s)
 
 
 def test_evaluate_once_and_cli_default_to_no_parzen():
-    import inspect
-    from graphical_gan_amd import evaluate, run
-    assert inspect.signature(evaluate.evaluate_once).parameters['parzen'].default is False
-    assert inspect.signature(evaluate.Evaluator.set_scores).parameters['parzen'].default is False
-    assert inspect.signature(run._set_scores).parameters['parzen'].default is False
+    from graphical_gan_amd import evaluate
     assert evaluate.PARZEN_MAX_ROWS == 10000 and evaluate.PARZEN_VALID_ROWS == 1000
     assert np.array_equal(evaluate.PARZEN_SIGMAS, np.logspace(-1, 0, 10)) and np.array_equal(evaluate.PARZEN_SIGMAS, R.SIGMAS)
     with pytest.raises(SystemExit):            # refused before anything is built

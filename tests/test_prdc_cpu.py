@@ -1,8 +1,7 @@
 """not-gpu: the k-NN-ball ops' ABI (header, binding, built library, argument errors without a GPU), what the Python ops refuse, the
-cadence settings of the dev-set precision / recall / density / coverage pass, the scripts' new line, and the float64 restatement
+cadence settings of the dev-set precision / recall / density / coverage pass, and the float64 restatement
 tests/_prdc_ref.py: its known answers, its limiting cases, and the conditions under which the GPU tests' brackets can hide nothing."""
 import ctypes as C
-import glob
 import os
 import re
 import sys
@@ -17,6 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ('ggan_knn_radii_workspace', 'ggan_knn_radii', 'ggan_ball_counts_workspace', 'ggan_ball_counts')
 IMAGE_SCRIPTS = ['%s_inference_%s' % (f, d) for f in ('gan', 'gmgan') for d in ('cifar10', 'svhn', 'mnist', 'face')]
 SEQUENCE_SCRIPTS = ['ssgan_inference_moving_mnist', 'ssgan_inference_chairs']
+SCORE_VARS = ['GGAN_%s_EVERY' % n for n in ('MMD', 'PRDC', 'KNN', 'PARZEN', 'REC')]
 
 
 def test_header_binding_and_library_agree(lib_built):
@@ -98,51 +98,37 @@ def test_python_ops_refuse_what_they_cannot_do(lib_built):
 def test_prdc_settings_and_cadence(monkeypatch):
     from graphical_gan_amd import run
     every = IMAGE_SCRIPTS + SEQUENCE_SCRIPTS
-    monkeypatch.delenv('GGAN_PRDC_EVERY', raising=False)
-    monkeypatch.delenv('GGAN_MMD_EVERY', raising=False)
-    base = {s: (run.eval_settings(s), run.manifold_settings(s), run.mmd_settings(s)) for s in every}
+    for v in SCORE_VARS:
+        monkeypatch.delenv(v, raising=False)
+    base = {s: (run.eval_settings(s), run.manifold_settings(s)) for s in every}
     for s in every:
-        assert run.prdc_settings(s) == {} and run.prdc_settings('/somewhere/%s.py' % s) == {}
+        assert run.score_settings(s) == {} and run.score_settings('/somewhere/%s.py' % s) == {}
     monkeypatch.setenv('GGAN_PRDC_EVERY', '20')
-    for s in IMAGE_SCRIPTS:
-        assert run.prdc_settings(s) == {'PRDC_EVERY': 20} and run.prdc_settings('/somewhere/%s.py' % s) == {'PRDC_EVERY': 20}
+    for s in IMAGE_SCRIPTS:                    # (exactly the one key: no other score learns the variable)
+        assert run.score_settings(s) == {'PRDC_EVERY': 20} and run.score_settings('/somewhere/%s.py' % s) == {'PRDC_EVERY': 20}
     for s in SEQUENCE_SCRIPTS:
-        assert run.prdc_settings(s) == {}
-    # the other settings functions do not learn the variable (mmd_settings among them), and the key is in no *_KEYS
+        assert run.score_settings(s) == {}
+    # the other settings functions do not learn the variable, and the key is in no *_KEYS
     for s in every:
-        assert (run.eval_settings(s), run.manifold_settings(s), run.mmd_settings(s)) == base[s]
-        assert run.mmd_settings(s) == {} and 'PRDC_EVERY' not in run.eval_settings(s)
+        assert (run.eval_settings(s), run.manifold_settings(s)) == base[s]
+        assert 'PRDC_EVERY' not in run.eval_settings(s)
     assert 'PRDC_EVERY' not in run.EVAL_KEYS and 'PRDC_EVERY' not in run.MANIFOLD_KEYS
-    S = dict(run.reference_block('gan_inference_cifar10'), **run.prdc_settings('gan_inference_cifar10'))
+    S = dict(run.reference_block('gan_inference_cifar10'), **run.score_settings('gan_inference_cifar10'))
     assert run.eval_plan(S) is None and run.manifold_plan(S) is None
-    assert [it for it in range(60) if run.prdc_due(S, it)] == [19, 39, 59]
-    assert not any(run.mmd_due(S, it) for it in range(60))
-    assert not any(run.prdc_due(run.reference_block('gan_inference_cifar10'), it) for it in range(60))
+    assert [it for it in range(60) if 'prdc' in run.scores_due(S, it)] == [19, 39, 59]
+    assert not any('mmd' in run.scores_due(S, it) for it in range(60))
+    assert all(run.scores_due(S, it) in ((), ('prdc',)) for it in range(60))             # no other score fires
+    assert not any(run.scores_due(run.reference_block('gan_inference_cifar10'), it) for it in range(60))
     # ... and the other way round
     monkeypatch.delenv('GGAN_PRDC_EVERY')
     monkeypatch.setenv('GGAN_MMD_EVERY', '20')
     for s in every:
-        assert run.prdc_settings(s) == {}
-    assert run.mmd_settings('gan_inference_cifar10') == {'MMD_EVERY': 20}
-
-
-def test_the_eight_image_scripts_carry_the_line():
-    line = 'SETTINGS.update(run.prdc_settings(__file__))'
-    seen = {}
-    for path in glob.glob(os.path.join(ROOT, 'scripts', '*_inference_*.py')):
-        seen[os.path.splitext(os.path.basename(path))[0]] = open(path).read().count(line)
-    assert sorted(seen) == sorted(IMAGE_SCRIPTS + SEQUENCE_SCRIPTS)
-    for s in IMAGE_SCRIPTS:
-        assert seen[s] == 1, s
-    for s in SEQUENCE_SCRIPTS:
-        assert seen[s] == 0, s
+        assert 'PRDC_EVERY' not in run.score_settings(s)
+    assert run.score_settings('gan_inference_cifar10') == {'MMD_EVERY': 20}
 
 
 def test_evaluate_once_and_cli_default_to_no_prdc():
-    import inspect
     from graphical_gan_amd import evaluate
-    sig = inspect.signature(evaluate.evaluate_once)
-    assert sig.parameters['prdc'].default is False and sig.parameters['mmd'].default is False
     assert hasattr(evaluate.Evaluator, 'prdc_scores') and evaluate.PRDC_MAX_ROWS == 10000 and evaluate.PRDC_K == 5
     with pytest.raises(SystemExit):            # refused before anything is built
         evaluate.main(['nowhere.npz', '--script', 'ssgan_inference_chairs', '--out-dir', 'x', '--prdc'])

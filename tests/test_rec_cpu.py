@@ -1,10 +1,9 @@
 """not-gpu: the reconstruction-fidelity op's ABI (header, binding, built library, argument errors without a GPU), what the Python ops
-refuse, the cadence settings of the dev-set reconstruction pass for all ten scripts, the scripts' new line, what the CLI refuses before a
+refuse, the cadence settings of the dev-set reconstruction pass for all ten scripts, what the CLI refuses before a
 checkpoint is read, and the float64 restatement tests/_ssim_ref.py: its closed forms by hand, its agreement with scipy's Gaussian filter,
 and the condition on the shared cases under which the GPU tests test something (raw one-pass moments in float32 miss the gate on the bright
 flat planes; centred ones do not)."""
 import ctypes as C
-import glob
 import inspect
 import os
 import re
@@ -20,6 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ('ggan_ssim_pairs_workspace', 'ggan_ssim_pairs')
 IMAGE_SCRIPTS = ['%s_inference_%s' % (f, d) for f in ('gan', 'gmgan') for d in ('cifar10', 'svhn', 'mnist', 'face')]
 SEQUENCE_SCRIPTS = ['ssgan_inference_moving_mnist', 'ssgan_inference_chairs']
+SCORE_VARS = ['GGAN_%s_EVERY' % n for n in ('MMD', 'PRDC', 'KNN', 'PARZEN', 'REC')]
 KEYS = ['dev rec mse x', 'dev rec psnr x', 'dev rec ssim x', 'dev rec ssim se x']
 
 
@@ -216,47 +216,33 @@ def test_psnr_from_mse_caps_at_100_db():
 def test_rec_settings_and_cadence(monkeypatch):
     from graphical_gan_amd import run
     every = IMAGE_SCRIPTS + SEQUENCE_SCRIPTS
-    for v in ('GGAN_REC_EVERY', 'GGAN_PARZEN_EVERY', 'GGAN_KNN_EVERY', 'GGAN_PRDC_EVERY', 'GGAN_MMD_EVERY'):
+    for v in SCORE_VARS:
         monkeypatch.delenv(v, raising=False)
-    others = lambda s: (run.eval_settings(s), run.manifold_settings(s), run.mmd_settings(s), run.prdc_settings(s), run.knn_settings(s),
-                        run.parzen_settings(s))
+    others = lambda s: (run.eval_settings(s), run.manifold_settings(s))
     base = {s: others(s) for s in every}
     for s in every:                                # the default is off
-        assert run.rec_settings(s) == {} and run.rec_settings('/somewhere/%s.py' % s) == {}
+        assert run.score_settings(s) == {} and run.score_settings('/somewhere/%s.py' % s) == {}
     monkeypatch.setenv('GGAN_REC_EVERY', '20')
-    for s in every:                                # all ten scripts, the state-space ones included
-        assert run.rec_settings(s) == {'REC_EVERY': 20} and run.rec_settings('/somewhere/%s.py' % s) == {'REC_EVERY': 20}
-    assert run.rec_settings('no_such_script') == {}
+    for s in every:                                # all ten scripts, the state-space ones included (exactly the one key)
+        assert run.score_settings(s) == {'REC_EVERY': 20} and run.score_settings('/somewhere/%s.py' % s) == {'REC_EVERY': 20}
+    assert run.score_settings('no_such_script') == {}
     for s in every:                 # the other settings functions do not learn the variable, and the key is in no *_KEYS
         assert others(s) == base[s]
     assert 'REC_EVERY' not in run.EVAL_KEYS and 'REC_EVERY' not in run.MANIFOLD_KEYS
     for script in ('gan_inference_mnist', 'ssgan_inference_chairs'):
-        S = dict(run.reference_block(script), **run.rec_settings(script))
+        S = dict(run.reference_block(script), **run.score_settings(script))
         assert run.eval_plan(S) is None and run.manifold_plan(S) is None
-        assert [it for it in range(60) if run.rec_due(S, it)] == [19, 39, 59]
-        assert not any(run.mmd_due(S, it) or run.prdc_due(S, it) or run.knn_due(S, it) or run.parzen_due(S, it) for it in range(60))
-        assert not any(run.rec_due(run.reference_block(script), it) for it in range(60))
+        assert [it for it in range(60) if 'rec' in run.scores_due(S, it)] == [19, 39, 59]
+        assert not any(set(run.scores_due(S, it)) & {'mmd', 'prdc', 'knn', 'parzen'} for it in range(60))
+        assert not any(run.scores_due(run.reference_block(script), it) for it in range(60))
     monkeypatch.delenv('GGAN_REC_EVERY')
     monkeypatch.setenv('GGAN_PARZEN_EVERY', '20')
     for s in every:
-        assert run.rec_settings(s) == {}
+        assert 'REC_EVERY' not in run.score_settings(s)
 
 
-def test_the_ten_scripts_carry_the_line():
-    line = 'SETTINGS.update(run.rec_settings(__file__))'
-    seen = {}
-    for path in glob.glob(os.path.join(ROOT, 'scripts', '*_inference_*.py')):
-        seen[os.path.splitext(os.path.basename(path))[0]] = open(path).read().count(line)
-    assert sorted(seen) == sorted(IMAGE_SCRIPTS + SEQUENCE_SCRIPTS)
-    assert all(seen[s] == 1 for s in seen), seen
-
-
-def test_new_keywords_stand_at_the_end_and_default_to_off():
-    from graphical_gan_amd import evaluate, run
-    for fn in (evaluate.evaluate_once, evaluate.Evaluator.set_scores, run._set_scores):
-        params = list(inspect.signature(fn).parameters.values())
-        assert params[-1].name == 'rec' and params[-1].default is False, fn
-        assert params[-2].name == 'parzen'
+def test_rec_constants_and_signatures():
+    from graphical_gan_amd import evaluate
     assert evaluate.REC_MAX_ROWS == 10000 and list(evaluate.REC_KEYS) == KEYS
     assert list(inspect.signature(evaluate.Evaluator.rec_scores).parameters) == ['self', 'batches', 'return_rows']
     assert list(inspect.signature(evaluate.SequenceEvaluator.rec_scores).parameters) == ['self', 'batches', 'return_rows', 'per_frame']
