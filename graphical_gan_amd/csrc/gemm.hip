@@ -9,6 +9,7 @@
 // deterministic split-K (partial slabs + launch_splitk_reduce, no atomics).
 #include "common.h"
 #include "conv.h"
+#include "cost_head.h"
 #include <stdlib.h>
 using namespace ggan;
 
@@ -415,9 +416,9 @@ __global__ __launch_bounds__(512) void gemm_kernel8(const GemmParams P) {
 struct HeadTerms { int count, kind; int rows[4]; float z[4]; float w[4]; const float* ext[4]; };
 
 // What the cost and the head's own parameters need from ALL rows, as extra workgroups of the products' launch (or head_tail_k):
-// workgroup 0: the cost -- bce_multi_fwd_k's loop and summation order on 256 threads (pointwise.hip);  workgroups 1..: 16 columns of
-// d_wout = h^T g each, the first of them d_bout too -- head_out_bwd_k's loop and combination order without the gh store.  Threads
-// beyond 256 (eight-wave launches) only keep the barriers company: their partial sums are exact zeros.
+// workgroup 0: the cost, term by term (cost_add_term on 256 threads: bce_multi_fwd_k's values and summation order);  workgroups 1..:
+// 16 columns of d_wout = h^T g each, the first of them d_bout too (head_columns without the gh store: head_out_bwd_k's sums).
+// Threads beyond 256 (eight-wave launches) only keep the barriers company: their partial sums are exact zeros.
 struct HeadTail {
     const float* logits; const float* g; const float* h;
     float* d_wout; float* d_bout; float* loss;
@@ -429,51 +430,20 @@ __device__ __forceinline__ void head_tail_wg(const HeadTail& T, const int local,
     const int tid = threadIdx.x;
     const bool on = tid < 256;
     if (local == 0) {
-        float* sm = lds;
         float tot = 0.f;
         int r0 = 0;
         for (int k = 0; k < T.terms.count; ++k) {
             const float z = T.terms.z[k];
             const int n = T.terms.rows[k];
             const float* x = T.terms.ext[k] ? T.terms.ext[k] : T.logits + r0;
-            float s = 0.f;
-            if (on)
-                for (int i = tid; i < n; i += 256) {
-                    const float v = x[i];
-                    s += T.terms.kind == 1 ? v : fmaxf(v, 0.f) - v * z + log1pf(expf(-fabsf(v)));
-                }
-            s = block_sum(s, sm);
-            const float r = T.terms.w[k] * (s / (float)n);
-            tot = k ? tot + r : r;
+            tot = cost_add_term(tot, k, T.terms.kind == 1, x, n, z, T.terms.w[k], nullptr, 256, on, lds);
             if (!T.terms.ext[k]) r0 += n;
         }
         if (tid == 0 && T.loss) T.loss[0] = tot;
         return;
     }
-    float (*red)[16] = reinterpret_cast<float (*)[16]>(lds);
-    const int cl = tid & 15, rg = (tid >> 4) & 15;
-    const int c = (local - 1) * 16 + cl;
-    float acc = 0.f, gs = 0.f;
-    if (on && c < T.H) {
-#pragma unroll 8
-        for (int r = rg; r < T.M; r += 16) {
-            const float gr = T.g[r], hv = T.h[(size_t)r * T.H + c];
-            acc = fmaf(gr, hv, acc);
-            gs += gr;
-        }
-    }
-    if (on) red[rg][cl] = acc;
-    __syncthreads();
-    if (on && rg == 0 && c < T.H && T.d_wout)
-        T.d_wout[c] = (((red[0][cl] + red[1][cl]) + (red[2][cl] + red[3][cl])) + ((red[4][cl] + red[5][cl]) + (red[6][cl] + red[7][cl]))) +
-                      (((red[8][cl] + red[9][cl]) + (red[10][cl] + red[11][cl])) + ((red[12][cl] + red[13][cl]) + (red[14][cl] + red[15][cl])));
-    if (local == 1 && T.d_bout) {
-        __syncthreads();
-        if (on && cl == 0) red[rg][0] = gs;
-        __syncthreads();
-        if (tid == 0) T.d_bout[0] = (((red[0][0] + red[1][0]) + (red[2][0] + red[3][0])) + ((red[4][0] + red[5][0]) + (red[6][0] + red[7][0]))) +
-                                    (((red[8][0] + red[9][0]) + (red[10][0] + red[11][0])) + ((red[12][0] + red[13][0]) + (red[14][0] + red[15][0])));
-    }
+    head_columns<false>(T.g, T.h, nullptr, 0.f, nullptr, T.d_wout, T.d_bout, local == 1, T.M, T.H, (local - 1) * 16 + (tid & 15), tid, (tid >> 4) & 15, on,
+                        reinterpret_cast<float (*)[16]>(lds));
 }
 
 __global__ __launch_bounds__(256) void head_tail_k(const HeadTail T) {
@@ -523,23 +493,8 @@ __global__ __launch_bounds__(256) void head_out_fwd_k(const float* __restrict__ 
     const int row = blockIdx.x * 2 + rl;
     float dot = 0.f;
     if (row < M) {
-        for (int c = t * 4; c < H; c += 512) {
-            const size_t o = (size_t)row * H + c;
-            float4 v = *reinterpret_cast<const float4*>(part + o);
-            // (slab order: deterministic.  Unrolled: the slab loads are independent, only the adds are ordered -- rolled, the 16
-            //  slabs of the K = 4608 tail were 16 serial L2 round trips, most of this kernel's 8 us)
-#pragma unroll 8
-            for (int s = 1; s < SK; ++s) {
-                const float4 u = *reinterpret_cast<const float4*>(part + (size_t)s * slab + o);
-                v.x += u.x; v.y += u.y; v.z += u.z; v.w += u.w;
-            }
-            const float4 bb = *reinterpret_cast<const float4*>(b + c);
-            const float4 ww = *reinterpret_cast<const float4*>(w_out + c);
-            v.x = fmaxf(alpha * (v.x + bb.x), v.x + bb.x); v.y = fmaxf(alpha * (v.y + bb.y), v.y + bb.y);
-            v.z = fmaxf(alpha * (v.z + bb.z), v.z + bb.z); v.w = fmaxf(alpha * (v.w + bb.w), v.w + bb.w);
-            *reinterpret_cast<float4*>(h + o) = v;
-            dot = fmaf(v.x, ww.x, fmaf(v.y, ww.y, fmaf(v.z, ww.z, fmaf(v.w, ww.w, dot))));
-        }
+        float4 v, ww;
+        for (int c = t * 4; c < H; c += 512) dot = head_fwd_unit(part, SK, slab, (size_t)row * H + c, b, w_out, c, alpha, h, dot, v, ww);
     }
     dot = wave_sum(dot);
     if ((tid & 63) == 0) red[tid >> 6] = dot;
@@ -547,7 +502,7 @@ __global__ __launch_bounds__(256) void head_out_fwd_k(const float* __restrict__ 
     if (t == 0 && row < M) logits[row] = (red[2 * rl] + red[2 * rl + 1]) + b_out[0];
 }
 
-// head_out_fwd_k + g[r] + gh[r,:] (H <= 2048: the row's h values stay in registers).  Same expressions as bce_multi_fwd_k / head_out_bwd_k.
+// head_out_fwd_k + g[r] + gh[r,:] (H <= 2048: the row's h values stay in registers); g as unit_seed / bce_grad form it (cost_head.h).
 __global__ __launch_bounds__(256) void head_out_fwd_bce_k(const float* __restrict__ part, int SK, size_t slab, const float* __restrict__ b,
                                                           const float* __restrict__ w_out, const float* __restrict__ b_out, float alpha,
                                                           float* __restrict__ h, float* __restrict__ logits, int M, int H,
@@ -560,22 +515,7 @@ __global__ __launch_bounds__(256) void head_out_fwd_bce_k(const float* __restric
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
         const int c = t * 4 + it * 512;
-        if (row < M && c < H) {
-            const size_t o = (size_t)row * H + c;
-            float4 v = *reinterpret_cast<const float4*>(part + o);
-#pragma unroll 8
-            for (int s = 1; s < SK; ++s) {
-                const float4 u = *reinterpret_cast<const float4*>(part + (size_t)s * slab + o);
-                v.x += u.x; v.y += u.y; v.z += u.z; v.w += u.w;
-            }
-            const float4 bb = *reinterpret_cast<const float4*>(b + c);
-            const float4 ww = *reinterpret_cast<const float4*>(w_out + c);
-            v.x = fmaxf(alpha * (v.x + bb.x), v.x + bb.x); v.y = fmaxf(alpha * (v.y + bb.y), v.y + bb.y);
-            v.z = fmaxf(alpha * (v.z + bb.z), v.z + bb.z); v.w = fmaxf(alpha * (v.w + bb.w), v.w + bb.w);
-            *reinterpret_cast<float4*>(h + o) = v;
-            dot = fmaf(v.x, ww.x, fmaf(v.y, ww.y, fmaf(v.z, ww.z, fmaf(v.w, ww.w, dot))));
-            hv[it] = v; wv[it] = ww;
-        }
+        if (row < M && c < H) dot = head_fwd_unit(part, SK, slab, (size_t)row * H + c, b, w_out, c, alpha, h, dot, hv[it], wv[it]);
     }
     dot = wave_sum(dot);
     if ((tid & 63) == 0) red[tid >> 6] = dot;
@@ -588,11 +528,11 @@ __global__ __launch_bounds__(256) void head_out_fwd_bce_k(const float* __restric
         int r0 = 0;
         for (int k = 0; k < T.count; ++k) {
             if (T.ext[k]) continue;
-            if (row >= r0 && row < r0 + T.rows[k]) { z = T.z[k]; sc = 1.f * T.w[k] / (float)T.rows[k]; }
+            if (row >= r0 && row < r0 + T.rows[k]) { z = T.z[k]; sc = unit_seed(T.w[k], T.rows[k]); }
             r0 += T.rows[k];
         }
     }
-    const float gr = T.kind == 1 ? sc : sc * (1.f / (1.f + expf(-lg)) - z);
+    const float gr = T.kind == 1 ? sc : bce_grad(sc, lg, z);
     if (t == 0) g_out[row] = gr;
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
@@ -607,39 +547,13 @@ __global__ __launch_bounds__(256) void head_out_fwd_bce_k(const float* __restric
 }
 
 // backward head: gh[r,c] = g[r] * w_out[c] * lrelu'(h[r,c]);  d_wout[c] = sum_r g[r] h[r,c];  d_bout = sum_r g[r].
-// One workgroup per 16 columns, 16 row groups (measured against 64 x 4 and 32 x 8: the launch is a chain of L2 round trips per
-// thread, not bandwidth -- 8 rows per thread at 128 rows, all of their loads in flight at once); the row groups are combined in a
-// fixed order (deterministic).  bce_head_bwd_k (pointwise.hip) is the same loop with g
-// formed from the logits.
+// One workgroup per 16 columns: head_columns (cost_head.h), which bce_head_bwd_k (losses.hip) runs with g formed from the logits.
 __global__ __launch_bounds__(256) void head_out_bwd_k(const float* __restrict__ g, const float* __restrict__ h,
                                                       const float* __restrict__ w_out, float alpha, float* __restrict__ gh,
                                                       float* __restrict__ d_wout, float* __restrict__ d_bout, int M, int H) {
     __shared__ float red[16][16];
-    const int tid = threadIdx.x, cl = tid & 15, rg = tid >> 4;
-    const int c = blockIdx.x * 16 + cl;
-    float acc = 0.f, gs = 0.f;
-    if (c < H) {
-        const float w = w_out[c];
-#pragma unroll 8
-        for (int r = rg; r < M; r += 16) {
-            const float gr = g[r], hv = h[(size_t)r * H + c];
-            gh[(size_t)r * H + c] = gr * w * (hv > 0.f ? 1.f : alpha);
-            acc = fmaf(gr, hv, acc);
-            gs += gr;
-        }
-    }
-    red[rg][cl] = acc;
-    __syncthreads();
-    if (rg == 0 && c < H && d_wout)
-        d_wout[c] = (((red[0][cl] + red[1][cl]) + (red[2][cl] + red[3][cl])) + ((red[4][cl] + red[5][cl]) + (red[6][cl] + red[7][cl]))) +
-                    (((red[8][cl] + red[9][cl]) + (red[10][cl] + red[11][cl])) + ((red[12][cl] + red[13][cl]) + (red[14][cl] + red[15][cl])));
-    if (blockIdx.x == 0 && d_bout) {
-        __syncthreads();
-        if (cl == 0) red[rg][0] = gs;
-        __syncthreads();
-        if (tid == 0) d_bout[0] = (((red[0][0] + red[1][0]) + (red[2][0] + red[3][0])) + ((red[4][0] + red[5][0]) + (red[6][0] + red[7][0]))) +
-                                (((red[8][0] + red[9][0]) + (red[10][0] + red[11][0])) + ((red[12][0] + red[13][0]) + (red[14][0] + red[15][0])));
-    }
+    const int tid = threadIdx.x;
+    head_columns<true>(g, h, w_out, alpha, gh, d_wout, d_bout, blockIdx.x == 0, M, H, blockIdx.x * 16 + (tid & 15), tid, tid >> 4, true, red);
 }
 
 // N == 1 (the critics' Output layers, 512 -> 1): a matrix-vector product -- one wave per row, no tiles, no split-K, no reduce

@@ -1,6 +1,6 @@
 // Set-level mixture-of-RBF kernel sums between two row sets (tflib/objs/mmd.py:20-67 at dev-set sizes): for X[m,d], Y[n,d]
 //   S_xx = sum_{i != j} k(x_i, x_j),  S_yy likewise,  S_xy = sum_{i,j} k(x_i, y_j),  k(a,b) = sum_s wt_s exp(-||a-b||^2 / (2 sigma_s^2))
-// from which both MMD^2 estimators follow (include/ggan.h).  ggan_mix_rbf_mmd2_fwd (pointwise.hip) forms direct differences on one
+// from which both MMD^2 estimators follow (include/ggan.h).  ggan_mix_rbf_mmd2_fwd (losses.hip) forms direct differences on one
 // scalar workgroup per row and stops at m + n = 512; here the Gram product runs on v_mfma_f32_32x32x2_f32 and nothing of size
 // (m+n)^2 ever reaches memory.
 //

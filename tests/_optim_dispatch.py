@@ -1,4 +1,4 @@
-"""Which path of the optimizer tail (csrc/pointwise.hip: pack_k, pack_adam_k, adam_k<PRE>, rmsprop_k) each dispatch test runs: one row
+"""Which path of the optimizer tail (csrc/optim.hip: pack_k, pack_adam_k, adam_k<PRE>, rmsprop_k) each dispatch test runs: one row
 per entry point and edge (plain data), the rows' inputs, the float64 restatements they are measured against, the derived bounds, and
 `planned()`, a transcription of the host dispatch and of the in-kernel path predicate.
 
@@ -36,7 +36,7 @@ m at the gradient's scale); nothing below 1e-15, so no denormal appears anywhere
 
 Stages and bounds (u = 2^-24, half an ulp relative; no stage carries another's error):
   flat    bitwise the float32 sum in slab order, src slabs then src2 slabs (0 for a missing source).
-  m       against float64 from the float32 inputs: M_ROUNDINGS * u * (|b1 m| + |(1 - b1) gg|).  ADAM1 under -ffp-contract=on rounds
+  m       against float64 from the float32 inputs: M_ROUNDINGS * u * (|b1 m| + |(1 - b1) gg|).  adam1 (csrc/optim.hip) under -ffp-contract=on rounds
           1 - b1, b1 * m, (1 - b1) * gg and the sum: 4 (a contraction removes one).  First order the error is at most
           u (2 |b1 m| + 3 |(1 - b1) gg|): what the count leaves over covers the second-order terms.
   v       likewise, V_ROUNDINGS = 5: 1 - b2, b2 * v, (1 - b2) * gg, (..) * gg, the sum; u (2 |b2 v| + 4 |(1 - b2) gg^2|) first order.
@@ -525,7 +525,7 @@ MUTANTS = ADAM_MUTANTS + PACK_MUTANTS + RMS_MUTANTS
 
 
 def f32_kernel(g32, th0, m0, v0, t, hyper, gscale):
-    """ADAM1 as written, in float32 numpy without contraction (numpy's float32 power for powf) -> (theta, m, v): the CPU stand-in for the
+    """adam1 as written, in float32 numpy without contraction (numpy's float32 power for powf) -> (theta, m, v): the CPU stand-in for the
     right kernel"""
     f = np.float32
     lr, b1, b2, eps = (f(h) for h in hyper)

@@ -11,7 +11,7 @@ from _conv_dispatch import ROWS, row_id
 
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'graphical_gan_amd', 'csrc')
 FAMILY = ('conv_corr.hip', 'conv_wgrad.hip', 'conv_thin.hip', 'conv_naive.hip')
-HELPERS = ('conv_api.hip', 'pointwise.hip')          # pad_width_k, pack, chansum: only ever in a row's `also`
+HELPERS = ('conv_api.hip', 'optim.hip', 'pointwise.hip')          # pad_width_k, pack, chansum: only ever in a row's `also`
 
 _LAUNCH = re.compile(r'GGAN_LAUNCH\(\s*(\(\s*MODE == 0 \? "([^"]+)" : "([^"]+)"\s*\)|"([^"]+)")\s*,')
 

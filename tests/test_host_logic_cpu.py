@@ -545,3 +545,21 @@ def test_environment_switches_match_the_integration_table():
     documented = {n for ln in rows for n in re.findall(r'GGAN_[A-Z0-9_]+', ln.split('|')[1]) if not n.startswith('GGAN_BENCH_')}
     assert used - documented == set(), 'read by the code but not in INTEGRATION.md section 6'
     assert documented - used == set(), 'in INTEGRATION.md section 6 but read nowhere'
+
+
+def test_cost_and_optimizer_arithmetic_is_written_once():
+    """the expressions several kernels must agree on to the last bit have one home each: the BCE value in csrc/cost_head.h, the Adam
+    element update as a function (no per-kernel macro), the bias-corrected step size in adam_lr_t; and every .hip is built"""
+    import os
+    import re
+    from graphical_gan_amd import build
+    csrc = build.CSRC
+    texts = {fn: open(os.path.join(csrc, fn)).read() for fn in sorted(os.listdir(csrc)) if fn.endswith(('.hip', '.h'))}
+    assert {fn: t.count('log1pf(') for fn, t in texts.items() if 'log1pf(' in t} == {'cost_head.h': 1}
+    assert not [fn for fn, t in texts.items() if '#define ADAM1' in t]
+    uses = {fn: t.count('powf(') for fn, t in texts.items() if 'powf(' in t}
+    assert list(uses) == ['optim.hip'], uses
+    m = re.search(r'float adam_lr_t\([^)]*\) \{\n(.*?)\n\}\n', texts['optim.hip'], flags=re.S)
+    assert m and m.group(1).count('powf(') == uses['optim.hip'] == 2 and texts['optim.hip'].count('float adam_lr_t(') == 1
+    assert sorted(fn for fn in texts if fn.endswith('.hip')) == sorted(build.SOURCES)
+    assert len(set(build.SOURCES)) == len(build.SOURCES)

@@ -1,4 +1,4 @@
-"""The coverage table tests/_optim_dispatch.py against csrc/pointwise.hip, without a GPU: the GGAN_LAUNCH sites of the five optimizer
+"""The coverage table tests/_optim_dispatch.py against csrc/optim.hip, without a GPU: the GGAN_LAUNCH sites of the five optimizer
 entry points have rows and the rows name no other label; the constants planned() copies are the source's; every row's launches follow
 from planned(); the table reaches every (path, chunk, tail) combination and every arrival-group case; the float64 restatement agrees
 with oracle.ops.adam_update; a float32 restatement of the kernels passes every bound while each of sixteen wrong kernels misses one by
@@ -19,8 +19,11 @@ SMALL = 100000                  # rows with more elements are left to the GPU mo
 
 
 def _source():
-    with open(os.path.join(ROOT, 'graphical_gan_amd', 'csrc', 'pointwise.hip')) as f:
-        return f.read()
+    text = ''
+    for name in ('optim.hip', 'pointwise.h'):           # the optimizer's unit, then kBlock and grid_for, which it shares
+        with open(os.path.join(ROOT, 'graphical_gan_amd', 'csrc', name)) as f:
+            text += f.read()
+    return text
 
 
 def _elements(row):
@@ -243,7 +246,7 @@ def test_restatement_agrees_with_the_oracle():
 
 
 def test_a_float32_restatement_of_the_kernels_passes_every_bound():
-    """the bounds are not so tight that the arithmetic as written misses them: ADAM1 and rmsprop_k in float32 numpy, without contraction
+    """the bounds are not so tight that the arithmetic as written misses them: adam1 and rmsprop_k in float32 numpy, without contraction
     and with numpy's own float32 power, stay inside on every row's inputs"""
     worst = {}
     for idx, r in enumerate(ROWS):

@@ -1,4 +1,4 @@
-"""-m gpu: every path of the optimizer tail (csrc/pointwise.hip: pack_k, pack_adam_k, adam_k<false>, adam_k<true>, rmsprop_k), row by
+"""-m gpu: every path of the optimizer tail (csrc/optim.hip: pack_k, pack_adam_k, adam_k<false>, adam_k<true>, rmsprop_k), row by
 row of tests/_optim_dispatch.py.  The row's entry point runs through the C ABI between ggan_prof_reset / ggan_prof_enable; the profiler
 must have seen exactly the row's launches, each with the work-item count of the row's grid and block (a record holds that product, not
 the grid's shape); the pointers handed over must have exactly the alignment the row states

@@ -1,4 +1,4 @@
-"""Cost of the evaluation-only weight average (csrc/pointwise.hip: ema_k, swap_k) on an MI355X, for docs/KERNELS.md.
+"""Cost of the evaluation-only weight average (csrc/optim.hip: ema_k, swap_k) on an MI355X, for docs/KERNELS.md.
 
   python tools/ema_time.py [--decay 0.999 | --decay off] [--steps 200] [--warmup 20] [--repeats 5] [--no-kernels]
 
