@@ -365,7 +365,7 @@ __global__ __launch_bounds__(256) void cluster_accuracy_k(const int32_t* __restr
 struct NoiseTable {
     float* dst[GGAN_NOISE_MAX];
     unsigned n[GGAN_NOISE_MAX];
-    int kind[GGAN_NOISE_MAX];      // 0 normal(a, b) = a + b*N(0,1); 1 uniform [a, b); 2 one-hot rows of width K (n = rows * K)
+    int kind[GGAN_NOISE_MAX];      // 0 normal(a, b) = a + b*N(0,1); 1 uniform (a, b) for a = 0, else [a, b]; 2 one-hot rows of width K (n = rows * K)
     float a[GGAN_NOISE_MAX], b[GGAN_NOISE_MAX];
     int K[GGAN_NOISE_MAX];
     int slot[GGAN_NOISE_MAX];      // the tensor's ordinal within the step's draw (part of the counter): its index
@@ -385,7 +385,9 @@ __device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned
     out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
 }
 
-__device__ __forceinline__ float u01(unsigned x) { return ((float)(x >> 8) + 0.5f) * (1.0f / 16777216.0f); }   // (0, 1)
+// (0, 1): 2^-25 .. 1 - 2^-24.  16777215 + 0.5 is no float32 and rounds to 2^24, so the top word would give exactly 1; the fminf moves
+// that one value and no other.
+__device__ __forceinline__ float u01(unsigned x) { return fminf(((float)(x >> 8) + 0.5f) * (1.0f / 16777216.0f), 0.99999994f); }
 
 __global__ __launch_bounds__(256) void noise_fill_k(const NoiseTable t, unsigned long long* __restrict__ state) {
     const int tb = blockIdx.y, ti = t.slot[tb];

@@ -116,7 +116,8 @@ def decode_cluster_accuracy(assign, labels, colbest):
     assign, labels = np.asarray(assign, np.int64), np.asarray(labels, np.int64)
     rows = 0xFFFFFFFF - (np.asarray(colbest).astype(np.uint64) & np.uint64(0xFFFFFFFF)).astype(np.int64)
     label_of = np.where(rows < len(labels), labels[np.minimum(rows, len(labels) - 1)], np.iinfo(np.int64).min)
-    return int(np.sum(label_of[assign] == labels))
+    ok = (assign >= 0) & (assign < len(label_of))                    # (the kernel counts no match for an assignment outside [0, K))
+    return int(np.sum(ok & (label_of[np.clip(assign, 0, len(label_of) - 1)] == labels)))
 
 
 def column_keys(P):

@@ -59,7 +59,7 @@ def noise_state(device, seed=None):
 
 def noise_fill_(state, specs):
     """One launch for all the noise of a step.  specs: list of (tensor, kind, a, b) -- NOISE_NORMAL: a + b*N(0,1); NOISE_UNIFORM:
-    [a, b); NOISE_ONEHOT: rows of the 2-D tensor become one-hot with a uniformly drawn index.  In place; graph-capturable (the
+    (a, b) for a = 0, [a, b] otherwise (rounding may reach an end when a != 0); NOISE_ONEHOT: rows of the 2-D tensor become one-hot with a uniformly drawn index.  In place; graph-capturable (the
     draw number advances on the device)."""
     assert state.dtype == torch.int64 and state.numel() == 3 and state.is_cuda
     n = len(specs)

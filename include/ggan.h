@@ -521,7 +521,8 @@ int ggan_agg_div_bwd(int kind, const float* mu, const float* sd, const float* k_
                      ggan_stream_t stream);
 
 /* All the noise of one session.run in one launch: up to GGAN_NOISE_MAX device tensors, each filled with kind 0 = a + b*N(0,1),
- * 1 = uniform [a, b), 2 = one-hot rows of width `widths[i]` with a uniformly drawn index (the prior's k ~ Cat(1/K)).  Replaces
+ * 1 = uniform on (a, b) for a = 0 and on [a, b] otherwise (the draw u lies in [2^-25, 1 - 2^-24]; a + (b - a) u may round onto an end when
+ * a != 0), 2 = one-hot rows of width `widths[i]` with a uniformly drawn index (the prior's k ~ Cat(1/K)).  Replaces
  * tf.random_normal / tf.random_uniform / Categorical.sample + one_hot of the scripts (gmgan_inference_cifar10.py:115-120,344-346;
  * gan_inference_cifar10.py:353-357).  state = {seed, draw number, arrival counter} (3 x uint64 in DEVICE memory, arrival counter
  * zero): Philox4x32-10 keyed by the seed; the draw number is advanced on the device, so a captured HIP graph yields new noise on
