@@ -28,6 +28,11 @@
                      images back -- per-image mean squared error, PSNR and SSIM (Wang et al. 2004) in the unit pixel range, ggan_ssim_pairs.
                      The one pass that measures the round trip x -> q(z | x) -> Generator(z), and the one all ten scripts have:
                      SequenceEvaluator.rec_scores scores the state-space scripts' reconstructed sequences frame by frame.
+  probe_scores       `dev probe accuracy z` / `fit probe accuracy z` / `dev probe accuracy xr`: a least-squares linear probe -- the closed-form
+                     ridge classifier of functional.lsq_probe_fit on standardised columns -- fitted on q_z of labelled TRAINING rows and
+                     scored on q_z of the labelled dev set, on its own fit rows, and (xr) the same probe on a fixed random projection of
+                     the pixels to DIM_LATENT columns.  A pass of its own, not a row of SET_SCORES: it needs a second split and a fit
+                     step, and draws its noise from a state of its own, so no other pass's values move.  Not a pass of the reference.
 
 The passes are safe in the middle of training: they run under torch.no_grad() on the current stream only (no second stream, no
 collective), with a feed dict and a noise generator state of their own -- the Trainer's static feed buffers, ring slots and noise state
@@ -47,7 +52,7 @@ run by SequenceEvaluator on a models_ssgan.StateSpaceGAN under the same rules:
 Each is written as a .png sheet (one sequence per row) and a looping .gif; the bytes of both come from one ggan_video_sheet_u8 launch.
 
 `python -m graphical_gan_amd.evaluate CKPT --script gmgan_inference_mnist [--data-dir DIR]` scores a saved checkpoint
-(`--out-dir DIR --manifold` also writes the latent-space pictures of the two MNIST scripts, `--mmd` adds the two MMD^2 rows, `--prdc` the eight precision / recall / density / coverage rows, `--knn` the two k-NN accuracy rows, `--parzen` the three Parzen-window rows, `--rec` the four reconstruction rows);
+(`--out-dir DIR --manifold` also writes the latent-space pictures of the two MNIST scripts, `--mmd` adds the two MMD^2 rows, `--prdc` the eight precision / recall / density / coverage rows, `--knn` the two k-NN accuracy rows, `--parzen` the three Parzen-window rows, `--rec` the four reconstruction rows, `--probe` the three linear-probe rows);
 `... CKPT --script ssgan_inference_moving_mnist|ssgan_inference_chairs [--data-dir DIR] --out-dir DIR` writes the four pairs of files;
 `--rec` prints the four reconstruction rows of the sequences' frames, and alone needs no --out-dir.
 
@@ -76,6 +81,12 @@ PARZEN_MAX_ROWS = 10000   # rows per set of the parzen_scores pass (settings: PA
 PARZEN_VALID_ROWS = 1000  # leading dev rows its bandwidth is chosen on (settings: PARZEN_VALID_ROWS)
 PARZEN_SIGMAS = np.logspace(-1, 0, 10)    # the protocol's bandwidth grid, in [0, 1] pixel units (settings: PARZEN_SIGMAS; at most functional.PARZEN_MAX_SIGMAS)
 REC_MAX_ROWS = 10000      # rows (images; frames of the state-space scripts) of the rec_scores passes (settings: REC_MAX_ROWS)
+PROBE_FIT_ROWS = 10000    # labelled training rows the probe_scores pass fits on (settings: PROBE_FIT_ROWS; may be raised to the whole split)
+PROBE_MAX_ROWS = 10000    # labelled dev rows it scores (settings: PROBE_MAX_ROWS)
+PROBE_RIDGE = 1e-2        # its ridge, on standardised features (settings: PROBE_RIDGE)
+PROBE_SLAB_ROWS = 10000   # images it keeps on the device at a time: only the codes of a slab stay
+PROBE_SEED = 104729       # offset of its own noise state, and of its projection matrix, from the evaluator's seed
+PROBE_KEYS = ('dev probe accuracy z', 'fit probe accuracy z', 'dev probe accuracy xr')
 EVAL_SEED = 7919          # offset of the evaluator's noise seeds from the settings seed (the Trainer's stream of draws is not touched)
 
 # the reference's output file names, per script: (samples, reconstructions), formatted with frame= and mode=
@@ -560,6 +571,89 @@ class Evaluator(_Passes):
         res = self.set_scores(batches, rec=True)
         return (res, self.rec_rows) if return_rows else res
 
+    _probe_rng = _probe_matrix = None     # the probe pass's own noise state and projection matrix, made by its first call
+
+    def _probe_projection(self):
+        """the fixed random map of the pixels to DIM_LATENT columns: RandomState(seed).normal / sqrt(OUTPUT_DIM), drawn once per evaluator"""
+        if self._probe_matrix is None:
+            c = self.cfg
+            rng = np.random.RandomState(int(self.S.get('SEED', 0)) + EVAL_SEED + PROBE_SEED)
+            P = rng.normal(size=(c.output_dim, c.dim_latent)) / np.sqrt(float(c.output_dim))
+            self._probe_matrix = torch.as_tensor(P.astype(np.float32)).to(self.device)
+        return self._probe_matrix
+
+    def _probe_codes(self, batches, rows):
+        """z = q_z (as _score_sets computes sets['z']), xr = real_x through _probe_projection and y = the int32 labels of the leading full
+        minibatches, at most `rows` rows -> device tensors.  The images are staged PROBE_SLAB_ROWS rows at a time; only the codes stay."""
+        c = self.cfg
+        B = c.B
+        full = [b for b in batches if _split(b)[0].shape[0] == B]
+        if not full:
+            raise ValueError('no full minibatch of %d rows to evaluate on' % B)
+        n = min(len(full), max(1, int(rows) // B))
+        if n * B > F.PROBE_MAX_ROWS:
+            raise ValueError('the probe takes at most %d rows, got %d' % (F.PROBE_MAX_ROWS, n * B))
+        new = lambda w: torch.empty((n * B, w), dtype=torch.float32, device=self.device)
+        out = dict(z=new(c.dim_latent), xr=new(c.dim_latent), y=torch.empty((n * B,), dtype=torch.int32, device=self.device))
+        per, proj = max(1, PROBE_SLAB_ROWS // B), self._probe_projection()
+        for s0 in range(0, n, per):
+            X, Y = self._stage(full[s0:min(n, s0 + per)], want_labels=True)
+            out['y'][s0 * B:(s0 + X.shape[0]) * B].copy_(Y)
+            for i in range(X.shape[0]):
+                at = slice((s0 + i) * B, (s0 + i + 1) * B)
+                self.model.set_batch(self.feed, X[i])
+                self.model.sample_noise(self.feed)
+                real_x = self.model.real_x(self.feed)
+                q = self.model.Extractor(real_x, eps=self.feed['q_eps']) if c.agg else self.model.Extractor(real_x)
+                out['z'][at].copy_(q[0] if isinstance(q, tuple) else q)
+                out['xr'][at].copy_(F.Gemm.apply(real_x.float().reshape(B, -1).contiguous(), proj, None, False, False, F.ACT_NONE, 0.0))
+        return out
+
+    def probe_scores(self, fit_batches, dev_batches, return_fit=False):
+        """{'dev probe accuracy z', 'fit probe accuracy z', 'dev probe accuracy xr'}: a least-squares linear probe (functional.lsq_probe_fit:
+        the ridge-regularised least-squares classifier on standardised columns, ridge PROBE_RIDGE, in closed form -- neither logistic
+        regression nor an SVM) fitted on q_z of the leading PROBE_FIT_ROWS rows of the labelled TRAINING minibatches fit_batches and scored on
+        q_z of the leading PROBE_MAX_ROWS rows of the labelled dev minibatches (dev), on its own fit rows (fit: a large gap to dev shows
+        overfitting) and, as the baseline a code has to beat, the same probe on a fixed random projection of the pixels to DIM_LATENT
+        columns (xr).  The code is the one _score_sets builds -- one sample with a stochastic Extractor --, so the value sits beside dev knn
+        accuracy z.  The pass draws from a noise state of its own, swapped into the feed while it runs: every other pass logs the same values
+        whether it is on or not.  ONE host synchronisation; a raised status word (a label out of range, a non-finite moment, a failed
+        factorisation: a diverged model) gives nan and one printed message, no exception.
+        return_fit: (values, {fit, fit_xr: the ProbeFit records, fit_z, fit_xr_rows, fit_y, dev_z, dev_xr, dev_y: the device rows})."""
+        S = self.S
+        ridge = float(S.get('PROBE_RIDGE', PROBE_RIDGE))
+        if not ridge > 0.0:
+            raise ValueError('PROBE_RIDGE = %s: a positive number expected' % ridge)
+        labels = [_split(b)[1] for b in list(fit_batches) + list(dev_batches)]
+        if not fit_batches or not dev_batches or any(y is None for y in labels):
+            raise ValueError('the probe needs labelled minibatches on both sides')
+        classes = 1 + max(int(y.max()) for y in labels)             # (host labels: no device is asked)
+        if not 1 <= classes <= F.PROBE_MAX_CLASSES:
+            raise ValueError('the probe takes at most %d classes, got %d' % (F.PROBE_MAX_CLASSES, classes))
+        with self._guard():
+            if self._probe_rng is None:
+                self._probe_rng = F.noise_state(self.device, int(S.get('SEED', 0)) + EVAL_SEED + PROBE_SEED)
+            shared, self.feed['rng_state'] = self.feed['rng_state'], self._probe_rng
+            try:
+                fit = self._probe_codes(fit_batches, S.get('PROBE_FIT_ROWS', PROBE_FIT_ROWS))
+                dev = self._probe_codes(dev_batches, S.get('PROBE_MAX_ROWS', PROBE_MAX_ROWS))
+            finally:
+                self.feed['rng_state'] = shared
+            pz = F.lsq_probe_fit(fit['z'], fit['y'], classes, ridge)
+            px = F.lsq_probe_fit(fit['xr'], fit['y'], classes, ridge)
+            hits = [F.lsq_probe_predict(pz, dev['z'], dev['y']), F.lsq_probe_predict(pz, fit['z'], fit['y']),
+                    F.lsq_probe_predict(px, dev['xr'], dev['y'])]
+            host = torch.cat(hits + [pz.status, px.status]).cpu().numpy()
+        rows = (dev['y'].shape[0], fit['y'].shape[0], dev['y'].shape[0])
+        status = (int(host[3]), int(host[3]), int(host[4]))
+        if any(status):
+            print('[evaluate] probe: status %d (z) / %d (xr) -- 1: a label out of range, 2: a non-finite moment or entry, 4: a pivot that is not '
+                  'positive -- its values are nan' % (status[0], status[2]))
+        res = {k: (float('nan') if st else int(h) / float(n)) for k, h, n, st in zip(PROBE_KEYS, host[:3], rows, status)}
+        if return_fit:
+            return res, dict(fit=pz, fit_xr=px, fit_z=fit['z'], fit_xr_rows=fit['xr'], fit_y=fit['y'], dev_z=dev['z'], dev_xr=dev['xr'], dev_y=dev['y'])
+        return res
+
     def manifold(self, batches, out_dir, frame):
         """embeds the point sets of latent_sets with functional.tsne and writes the scatters under the reference's file names; returns
         the paths: the four pictures of gmgan_inference_mnist with a mixture prior, the one of gan_inference_mnist without.  MNIST models
@@ -851,6 +945,7 @@ def main(argv=None):
     ap.add_argument('--manifold', action='store_true', help='also write the latent-space t-SNE pictures of the MNIST scripts to --out-dir')
     for row in SET_SCORES:
         ap.add_argument('--' + row.name, action='store_true', help=row.help)
+    ap.add_argument('--probe', action='store_true', help='also fit a least-squares linear probe on the codes of labelled training rows and score it on the labelled dev set (dev probe accuracy z / fit probe accuracy z / dev probe accuracy xr; image scripts with labelled data)')
     ap.add_argument('--ema', action='store_true', help="score the averaged generator-side weights the checkpoint holds (its ema/gen/ keys, written by a run with $GGAN_EMA_DECAY) instead of the last iterate: every name gets the suffix ' ema', every file '_ema'; the critic of 'dev gen cost ema' is the live one")
     ap.add_argument('--set', action='append', default=[], metavar='KEY=VALUE', help='override an UPPERCASE setting (int / float / str)')
     a = ap.parse_args(argv)
@@ -870,6 +965,8 @@ def main(argv=None):
         for row in SET_SCORES:
             if getattr(a, row.name) and row.sequences is not True:
                 ap.error('--%s: %s' % (row.name, row.sequences))
+        if a.probe:
+            ap.error('--probe: %s' % _NO_CODE)
     if a.manifold:          # (checked before anything is built)
         name = os.path.splitext(os.path.basename(a.script))[0]
         if name not in MANIFOLD_SCRIPTS:
@@ -897,14 +994,16 @@ def main(argv=None):
         # the checkpoint's live ones), and the evaluators only name what they write
         tr.load_params(ema)
         tr.ema_loaded = True
-    res = evaluate_once(tr, S, out_dir=a.out_dir, manifold=a.manifold, **{row.name: getattr(a, row.name) for row in SET_SCORES})
+    res = evaluate_once(tr, S, out_dir=a.out_dir, manifold=a.manifold, probe=a.probe, **{row.name: getattr(a, row.name) for row in SET_SCORES})
     for k in sorted(res):
         print('%s\t%s' % (k, res[k]))
     return res
 
 
-def evaluate_once(tr, S, out_dir=None, frame='eval', manifold=False, **scores):
+def evaluate_once(tr, S, out_dir=None, frame='eval', manifold=False, probe=False, **scores):
     """every pass the script's data allow, once -> {name: value}; manifold: the latent-space pictures too (labelled dev data only);
+    probe: the three values of Evaluator.probe_scores too, after the set-level scores (image scripts; skipped with one message where the
+    dev set or the training split has no labels);
     scores: the set-level scores of SET_SCORES to add, by name (mmd=True, ...: Evaluator.set_scores' keywords, one build of the sets for all
     of them; a score that needs labels is skipped on unlabelled dev data); a trainer whose weights are averaged ones loaded from a
     checkpoint (tr.ema_loaded, main --ema): names and files carry the suffixes.  The state-space scripts: the video files (with out_dir)
@@ -913,6 +1012,8 @@ def evaluate_once(tr, S, out_dir=None, frame='eval', manifold=False, **scores):
     from . import run
     ema_names = bool(getattr(tr, 'ema_loaded', False))
     if S['DATASET'] in run.SEQUENCE_DATASETS:       # the video passes: files only (train_data: the first dev minibatch)
+        if probe:
+            raise ValueError('probe: %s' % _NO_CODE)
         ev = SequenceEvaluator(tr, S)
         ev.weights = 'ema' if ema_names else 'live'
         dev, _ = run.eval_sets(S, tr.model, tr.device)
@@ -936,6 +1037,12 @@ def evaluate_once(tr, S, out_dir=None, frame='eval', manifold=False, **scores):
             scores[row.name] = False
     if any(scores.values()):
         res.update(ev.tag(ev.set_scores(dev, **scores)))
+    if probe:
+        fit = run.probe_sets(S) if run.labelled(dev) else None
+        if not fit:
+            print('[evaluate] dev probe accuracy skipped: no labelled dev set and training split')
+        else:
+            res.update(ev.tag(ev.probe_scores(fit, dev)))
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
         ev.set_fixed_data(dev[0])

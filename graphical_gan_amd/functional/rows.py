@@ -1,4 +1,5 @@
 """row glue of the objectives: joins / splits / fan-out of row blocks, mixture and reparameterisation ops, the wali-gp interpolates."""
+import collections
 import ctypes as C
 import math
 import torch
@@ -578,6 +579,77 @@ def psnr_from_mse(mse):
     inf, which would poison a mean -> float64 tensor on the same device (plain torch arithmetic on n numbers: the caller keeps the one host
     synchronisation)"""
     return -10.0 * torch.log10(torch.clamp(mse.double(), min=1e-10))
+
+
+PROBE_MAX_DIM, PROBE_MAX_CLASSES, PROBE_MAX_ROWS, PROBE_ROW_BLOCK = 128, 32, 131072, 256   # include/ggan.h: GGAN_PROBE_MAX_DIM / _MAX_CLASSES, the row range, GGAN_PROBE_ROW_BLOCK
+PROBE_BAD_LABEL, PROBE_NONFINITE, PROBE_BAD_PIVOT = 1, 2, 4                                # ... and the bits of the status word
+
+ProbeFit = collections.namedtuple('ProbeFit', 'mean inv_std W bias counts status')
+ProbeFit.__doc__ = """a fitted least-squares probe, device tensors: mean, inv_std float32 [d] (inv_std 0 for a constant column), W float32 [d, classes], bias
+float32 [classes] (the class frequencies), counts int32 [classes], status int32 [1] (0, or PROBE_BAD_LABEL | PROBE_NONFINITE | PROBE_BAD_PIVOT;
+W is NaN where the solve failed)"""
+
+
+def _probe_rows(name, z, y, d=None, least=1):
+    """float32 rows [rows, d <= PROBE_MAX_DIM] and (or None) int32 labels [rows] on the rows' device (ValueError otherwise) -> (z, y) contiguous"""
+    if z.dim() != 2 or z.dtype != torch.float32 or z.shape[0] > PROBE_MAX_ROWS:
+        raise ValueError('%s: float32 rows [rows <= %d, d] expected, got %s %s' % (name, PROBE_MAX_ROWS, z.dtype, tuple(z.shape)))
+    if z.shape[0] < least:
+        raise ValueError('%s: at least %d rows expected, got %d' % (name, least, z.shape[0]))
+    if not 1 <= z.shape[1] <= PROBE_MAX_DIM or (d is not None and z.shape[1] != d):
+        raise ValueError('%s: %s columns expected, got %d' % (name, '1 <= d <= %d' % PROBE_MAX_DIM if d is None else d, z.shape[1]))
+    if y is not None:
+        y = _labels(name, 'y', y, z.shape[0], z.device)
+    _no_grad(name, [z])
+    return _c(z), y
+
+
+def lsq_probe_fit(z, y, classes, ridge):
+    """the ridge-regularised least-squares classifier of the labelled rows (z float32 [n, d], y int32 [n] in [0, classes)) on standardised
+    columns, in closed form (ggan_probe_moments / _normal / _solve): with zs = (z - mean) * inv_std, G = zs^T zs / n and R[:, c] = (1/n) the sum of
+    the zs rows of class c, W = (G + ridge I)^-1 R and the unpenalised intercept is the class frequencies -> ProbeFit.  d <= PROBE_MAX_DIM,
+    classes <= PROBE_MAX_CLASSES, n >= 2, ridge > 0.  Nothing is read back: a label out of range, a non-finite moment or a failed
+    factorisation is a bit of the record's status word.  Forward only."""
+    name = 'lsq_probe_fit'
+    classes, ridge = int(classes), float(ridge)
+    if not 1 <= classes <= PROBE_MAX_CLASSES:
+        raise ValueError('%s: 1 <= classes <= %d expected, got %d' % (name, PROBE_MAX_CLASSES, classes))
+    if not (math.isfinite(ridge) and ridge > 0.0):
+        raise ValueError('%s: ridge must be finite and positive, got %s' % (name, ridge))
+    z, y = _probe_rows(name, z, y, least=2)
+    n, d = z.shape
+    dev = z.device
+    new = lambda shape, dt=torch.float32: torch.empty(shape, dtype=dt, device=dev)
+    fit = ProbeFit(new((d,)), new((d,)), new((d, classes)), new((classes,)), new((classes,), torch.int32), new((1,), torch.int32))
+    G, R = new((d, d)), new((d, classes))
+    L = _L()
+    ws, nbytes = _workspace(max(L.ggan_probe_moments_workspace(n, d, classes), L.ggan_probe_normal_workspace(n, d, classes)), dev)
+    check(L.ggan_probe_moments(_p(z), _p(y), n, d, classes, _p(fit.mean), _p(fit.inv_std), _p(fit.counts), _p(fit.status), _p(ws), nbytes,
+                               _stream()), 'ggan_probe_moments')
+    check(L.ggan_probe_normal(_p(z), _p(y), n, d, classes, _p(fit.mean), _p(fit.inv_std), _p(G), _p(R), _p(ws), nbytes, _stream()),
+          'ggan_probe_normal')
+    check(L.ggan_probe_solve(_p(G), _p(R), _p(fit.counts), n, d, classes, ridge, _p(fit.W), _p(fit.bias), _p(fit.status), _stream()),
+          'ggan_probe_solve')
+    return fit
+
+
+def lsq_probe_predict(fit, z, y=None, return_pred=False):
+    """a fitted probe on the rows z float32 [m, d] (ggan_probe_predict): the class of the largest score ((z - mean) * inv_std) W + bias, the
+    lowest class on a tie.  With y (int32 [m]): correct int32 [1] = the number of rows that hit their label; with return_pred: (correct,
+    pred int32 [m]); without y: pred.  Device tensors, nothing is read back.  Forward only."""
+    name = 'lsq_probe_predict'
+    d, classes = fit.W.shape
+    z, y = _probe_rows(name, z, y, d)
+    if any(t.device != z.device for t in fit):
+        raise ValueError('%s: the fit lives on %s, the rows on %s' % (name, fit.W.device, z.device))
+    m = z.shape[0]
+    pred = torch.empty((m,), dtype=torch.int32, device=z.device) if (return_pred or y is None) else None
+    correct = torch.empty((1,), dtype=torch.int32, device=z.device) if y is not None else None
+    check(_L().ggan_probe_predict(_p(z), _p(y), m, d, classes, _p(fit.mean), _p(fit.inv_std), _p(fit.W), _p(fit.bias), _p(pred), _p(correct),
+                                  _stream()), 'ggan_probe_predict')
+    if y is None:
+        return pred
+    return (correct, pred) if return_pred else correct
 
 
 class Reparam(Function):

@@ -150,6 +150,46 @@ def scores_due(S, it):
     return tuple(name for name, n in every if n and it % n == n - 1)
 
 
+# the least-squares linear probe of the codes (evaluate.Evaluator.probe_scores) is a pass of its own, outside the table of set-level scores:
+# it needs the labelled TRAINING split as well and a fit step.  Off unless asked for
+PROBE_DATA_SEED = 271828      # numpy's global RNG while the fit rows are drawn: the loaders' shuffle then gives the same rows every run
+
+
+def probe_settings(script):
+    """{'PROBE_EVERY': N} for the eight image scripts when $GGAN_PROBE_EVERY = N is set, {} otherwise and for every other script (the
+    state-space scripts have no single code to probe)"""
+    name = os.path.splitext(os.path.basename(script))[0]
+    n = os.environ.get('GGAN_PROBE_EVERY')
+    return {'PROBE_EVERY': int(n)} if n and name in _IMAGE_SCRIPTS else {}
+
+
+def probe_due(S, it):
+    """does the probe pass fire after iteration `it`: it % N == N - 1, the cadence of the other passes"""
+    n = int(S.get('PROBE_EVERY') or 0)
+    return bool(n and it % n == n - 1)
+
+
+def probe_sets(S):
+    """the labelled minibatches the probe is fitted on: the leading PROBE_FIT_ROWS rows of the loader's TRAINING split (MNIST, CIFAR-10,
+    SVHN), drawn with numpy's global RNG seeded to a constant -- the same rows every run -- inside the saved and restored state; None
+    where the data have no labels (celebA, synthetic minibatches) or are not there.  The dev side is eval_sets' labelled dev set."""
+    from .evaluate import PROBE_FIT_ROWS
+    ds, B = S['DATASET'], S['BATCH_SIZE']
+    n = max(1, int(S.get('PROBE_FIT_ROWS', PROBE_FIT_ROWS)) // B)
+    state = np.random.get_state()
+    try:
+        if S.get('SYNTHETIC') == 'force' or ds not in ('mnist', 'cifar10', 'svhn'):
+            return None
+        np.random.seed(PROBE_DATA_SEED)
+        train = lib.mnist.load(B, B)[0] if ds == 'mnist' else getattr(lib, ds).load(B, S.get('DATA_DIR', ''))[0]
+        fit = [tuple(np.array(a) for a in b[:2]) for b in itertools.islice(train(), n)]      # (copies: the loaders yield views of one array)
+        return fit if labelled(fit) else None
+    except FileNotFoundError:
+        return None
+    finally:
+        np.random.set_state(state)
+
+
 # an exponential moving average of the generator-side weights (engine.Trainer's ema_decay), kept on the device inside the steps and used by
 # the passes only: off unless asked for; which weights the passes score is a second switch
 EMA_EVAL_MODES = ('live', 'ema', 'both')
@@ -445,8 +485,17 @@ def train(S, cfg, model=None, out_dir=None):
             if r.name in on and 'labels' in r.needs and not labelled(the_sets()[0]):
                 print('[run] %s skipped: no labelled dev set (%s data)' % (r.title, source))
                 on.discard(r.name)
-    ev = the_eval() if plan or manifold or on else None
-    ev_dev, ev_test = the_sets() if plan or manifold or (on and not sequences) else (None, None)
+    # the linear probe of the codes: the labelled training rows it is fitted on are loaded once per run, and only where the pass is on
+    probe = bool(S.get('PROBE_EVERY')) and lead
+    the_fit = functools.lru_cache(None)(lambda: probe_sets(S))
+    if probe and sequences:
+        print('[run] dev probe accuracy skipped: the state-space models have no single code to compare')
+        probe = False
+    elif probe and not (labelled(the_sets()[0]) and the_fit()):
+        print('[run] dev probe accuracy skipped: no labelled dev set and training split (%s data)' % source)
+        probe = False
+    ev = the_eval() if plan or manifold or on or probe else None
+    ev_dev, ev_test = the_sets() if plan or manifold or probe or (on and not sequences) else (None, None)
     flush = lambda: lib.plot.flush(out_dir, os.path.join(out_dir, 'logfile.txt') if out_dir else None)
     eval_ms = 0.0            # wall time of the evaluation passes (kept out of `time`)
     for it in range(S['ITERS']):
@@ -482,6 +531,11 @@ def train(S, cfg, model=None, out_dir=None):
             for w in passes:
                 with _on_weights(ev, w):
                     eval_ms += _timed(device, lambda: _plot(ev.tag(ev.rec_scores(rec_dev) if sequences else ev.set_scores(ev_dev, **scores))))
+            flush()
+        if probe and probe_due(S, it):
+            for w in passes:
+                with _on_weights(ev, w):
+                    eval_ms += _timed(device, lambda: _plot(ev.tag(ev.probe_scores(the_fit(), ev_dev))))
             flush()
         lib.plot.tick()
         if out_dir and S.get('SAVE_EVERY') and (it + 1) % S['SAVE_EVERY'] == 0:

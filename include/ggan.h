@@ -502,6 +502,44 @@ size_t ggan_ssim_pairs_workspace(int n, int c, int h, int w);
 int ggan_ssim_pairs(const float* A, const float* B, int n, int c, int h, int w, float scale_a, float shift_a, float scale_b, float shift_b,
                     float* mse /*[n]*/, float* ssim /*[n]*/, void* ws, size_t ws_bytes, ggan_stream_t stream);
 
+/* Least-squares linear probe: a ridge-regularised least-squares classifier on standardised rows, fitted in closed form
+ * (evaluate.Evaluator.probe_scores, functional.lsq_probe_fit / lsq_probe_predict).  Z[n,d] row-major device fp32, y int32 labels in
+ * [0, classes), 1 <= d <= GGAN_PROBE_MAX_DIM, 1 <= classes <= GGAN_PROBE_MAX_CLASSES, rows <= 131072 (the fit: n >= 2).
+ *   ggan_probe_moments: mean[j] = mean_i z_ij, inv_std[j] = 1 / sqrt(mean_i (z_ij - mean_j)^2) -- 0 for a constant column, which so drops
+ *                       out --, counts[c] = #{i : y_i == c}.  Two passes over the rows, the column sums in fp64 per block of
+ *                       GGAN_PROBE_ROW_BLOCK rows and over the blocks in block order; the second pass centres with the fp64 mean.
+ *                       status[0] is WRITTEN: GGAN_PROBE_BAD_LABEL if a label lies outside [0, classes) (it is never used as an index and
+ *                       counted nowhere), GGAN_PROBE_NONFINITE if a mean or a variance is not finite, else 0.
+ *   ggan_probe_normal:  G[d,d] = Zs^T Zs / n and R[d,classes] with R[:, c] = (1/n) sum_{i: y_i = c} zs_i, zs_i = (z_i - mean) * inv_std
+ *                       formed in fp32 on the fly: neither Zs nor a one-hot label matrix exists in memory.  A block of GGAN_PROBE_ROW_BLOCK
+ *                       rows is summed in fp32 in row order (v_mfma_f32_32x32x2_f32, d padded to a multiple of 32; instance t = ceil(d / 32)),
+ *                       the block partials in fp64 in block order.
+ *   ggan_probe_solve:   W[d,classes] = (G + ridge I)^-1 R by a Cholesky factorisation in fp64 in one workgroup's LDS, rounded once to
+ *                       fp32; bias[c] = counts[c] / n.  ridge > 0.  status[0] |= GGAN_PROBE_NONFINITE for a non-finite entry of G or R,
+ *                       GGAN_PROBE_BAD_PIVOT for a pivot that is not positive; W is then filled with NaN.
+ *   ggan_probe_predict: pred[i] = argmax_c bias[c] + sum_j ((z_ij - mean_j) * inv_std_j) W[j,c], the LOWEST class on a tie (pred may be
+ *                       NULL); with labels y and correct: correct[0] = #{i : pred[i] == y_i}, which the entry zeroes first (integer adds).
+ * ws: ggan_probe_*_workspace(n, d, classes) bytes of 16-byte aligned device scratch (0 = arguments out of range).  No floating-point
+ * atomics, every sum in a fixed order: repeated calls give the same bits.  Arguments out of range, a null pointer or a short workspace
+ * return a negative code before any device work.
+ * Forward only.  Added without a version change: no existing entry point or struct is touched. */
+#define GGAN_PROBE_MAX_DIM 128
+#define GGAN_PROBE_MAX_CLASSES 32
+#define GGAN_PROBE_ROW_BLOCK 256
+#define GGAN_PROBE_BAD_LABEL 1
+#define GGAN_PROBE_NONFINITE 2
+#define GGAN_PROBE_BAD_PIVOT 4
+size_t ggan_probe_moments_workspace(int n, int d, int classes);
+int ggan_probe_moments(const float* Z, const int32_t* y, int n, int d, int classes, float* mean, float* inv_std, int32_t* counts,
+                       int32_t* status, void* ws, size_t ws_bytes, ggan_stream_t stream);
+size_t ggan_probe_normal_workspace(int n, int d, int classes);
+int ggan_probe_normal(const float* Z, const int32_t* y, int n, int d, int classes, const float* mean, const float* inv_std, float* G,
+                      float* R, void* ws, size_t ws_bytes, ggan_stream_t stream);
+int ggan_probe_solve(const float* G, const float* R, const int32_t* counts, int n, int d, int classes, float ridge, float* W, float* bias,
+                     int32_t* status, ggan_stream_t stream);
+int ggan_probe_predict(const float* Z, const int32_t* y, int m, int d, int classes, const float* mean, const float* inv_std,
+                       const float* W, const float* bias, int32_t* pred, int32_t* correct, ggan_stream_t stream);
+
 /* Stochastic encoder head, TYPE_Q = 'learn_std' (gan_inference_cifar10.py:173-188): std = exp(log_std), z = mean + eps * std; the backward
  * takes the gradients arriving at z and at std (either may be NULL). */
 int ggan_reparam_fwd(const float* mean, const float* log_std, const float* eps, float* z, float* std_out, size_t n, ggan_stream_t stream);
