@@ -35,6 +35,9 @@ int check_launch(const char* name);
 bool launch_skipped(const char* name);
 // debugging aid: GGAN_TRACE_LAUNCHES=1 prints one stderr line per launch (name, grid, block, dynamic LDS, flops)
 void trace_launch(const char* name, dim3 grid, dim3 block, size_t shmem, double flops);
+// pointwise.hip: join == true: P[r, c] = c < split ? A[r, c] : A2[r, c - split] for the [R, C] matrix P (A is [R, split], A2 [R, C - split]);
+// join == false: the inverse, P dealt out to A and A2.  One launch; what ggan_gemm_split stages a split off its tile grid with.
+int stage_cols(bool join, float* A, float* A2, float* P, int R, int C, int split, hipStream_t stream);
 
 // LAUNCH(name, flops, bytes, kernel, grid, block, shmem, stream, args...)
 // (GGAN_SKIP_KERNELS is compiled in only with -DGGAN_DIAG -- build.py adds it under GGAN_BUILD_DIAG=1; the product library has

@@ -1054,8 +1054,40 @@ int ggan_gemm_split(int ta, int tb, int M, int N, int K, const float* A, const f
     GGAN_CHECK_ARG(A && B && C, "null pointer");
     GGAN_CHECK_ARG(M > 0 && N > 0 && K > 0, "bad shape");
     GGAN_CHECK_ARG(!colsum_b || !tb, "column sums need B stored [K,N]");
-    return gemm_launch(ta, tb, M, N, K, A, B, bias, C, colsum_b, act, alpha, ws, ws_bytes, (hipStream_t)stream, nullptr, nullptr, 0,
-                       0.f, A2, a_split, C2, c_split);
+    hipStream_t s = (hipStream_t)stream;
+    // (a split on the 16-grid is read / stored in place too where gemm_launch hands the product to gemm_skinny_k: the same conditions,
+    //  restated -- where the two disagree the product is either staged, with the same result, or refused as before, never wrong)
+    const int tiles = cdiv(M, BM) * cdiv(N, BN);
+    const bool skinny = !ta && !colsum_b && M >= 32 && K >= 64 && K <= 1024 && tiles < 64 && cdiv(M, 16) * cdiv(N, 16) <= 1024 &&
+                        !(K <= 128 && tiles >= 32) && (size_t)M * K * 4 < 0x7FFFFFF0ull && (size_t)N * K * 4 < 0x7FFFFFF0ull;
+    const bool stage_a = A2 && (a_split % 64) != 0 && !(skinny && a_split % 16 == 0 && (!C2 || c_split % 16 == 0));
+    const bool stage_c = C2 && (c_split % 64) != 0 && !(skinny && c_split % 16 == 0 && (!A2 || a_split % 16 == 0));
+    if (stage_a || stage_c) {
+        // A split off the tile grid.  The product kernels switch sources per tile, so a_split / c_split must be a multiple of the tile
+        // step; the mixture scripts' code-space Linears read [z | k] with DIM_LATENT = 8 columns of z (gmgan_inference_cifar10.py:74,
+        // 236-237): a few thousand elements.  Those are staged by one pointwise launch (ggan::stage_cols, pointwise.hip) -- [A | A2] side by
+        // side in front of the product, or the product's [M, N] result dealt out to its two buffers behind it -- and the product itself
+        // runs on one source / one output.  The staged matrix lives at the END of the workspace, the product keeps the front.
+        GGAN_CHECK_ARG(!(A2 && C2), "one of the two splits at a time");
+        const int R = stage_a ? (ta ? K : M) : M, Ct = stage_a ? (ta ? M : K) : N, split = stage_a ? a_split : c_split;
+        GGAN_CHECK_ARG(split > 0 && split < Ct, "split outside the matrix");
+        GGAN_CHECK_ARG(!stage_c || (!colsum_b && !bias && act == GGAN_ACT_NONE), "a split output takes no epilogue");
+        const size_t elems = (size_t)R * Ct, bytes = (elems * sizeof(float) + 255) & ~(size_t)255;
+        GGAN_CHECK_ARG(elems < 0x7FFFFFFFull, "matrix too large to stage");
+        GGAN_CHECK_ARG(ws && ws_bytes >= kWsReserved + bytes + 512 && al16(ws), "workspace too small to stage a split off the tile grid");
+        const size_t front = (ws_bytes - bytes) & ~(size_t)255;
+        float* P = (float*)((char*)ws + front);
+        if (stage_a) {
+            int rc = ggan::stage_cols(true, const_cast<float*>(A), const_cast<float*>(A2), P, R, Ct, split, s);
+            if (rc) return rc;
+            return gemm_launch(ta, tb, M, N, K, P, B, bias, C, colsum_b, act, alpha, ws, front, s);
+        }
+        int rc = gemm_launch(ta, tb, M, N, K, A, B, nullptr, P, nullptr, GGAN_ACT_NONE, 0.f, ws, front, s);
+        if (rc) return rc;
+        return ggan::stage_cols(false, C, C2, P, R, Ct, split, s);
+    }
+    return gemm_launch(ta, tb, M, N, K, A, B, bias, C, colsum_b, act, alpha, ws, ws_bytes, s, nullptr, nullptr, 0, 0.f, A2, a_split, C2,
+                       c_split);
 }
 
 int ggan_gemm_colsum(int ta, int M, int N, int K, const float* A, const float* B, float* C, float* colsum_b, void* ws,

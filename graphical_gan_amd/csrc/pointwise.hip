@@ -218,7 +218,37 @@ __global__ void reparam_bwd_k(const float* __restrict__ gz, const float* __restr
     }
 }
 
+// ---- two row-major matrices side by side: [A | A2] <-> P (ggan::stage_cols; the mixture scripts' Linear on concat([z, k], 1)) -----------
+// JOIN: P[r, c] = c < split ? A[r, c] : A2[r, c - split];  !JOIN: the inverse (P is read, A and A2 are written).  One element per thread.
+template <bool JOIN>
+__global__ void __launch_bounds__(kBlock) stage_cols_k(float* __restrict__ A, float* __restrict__ A2, float* __restrict__ P, int R, int C,
+                                                       int split) {
+    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= (size_t)R * C) return;
+    const int r = (int)(i / (size_t)C), c = (int)(i - (size_t)r * C);
+    float* q = c < split ? A + (size_t)r * split + c : A2 + (size_t)r * (C - split) + (c - split);
+    if (JOIN) P[i] = *q;
+    else *q = P[i];
+}
+
 }  // namespace
+
+namespace ggan {
+
+int stage_cols(bool join, float* A, float* A2, float* P, int R, int C, int split, hipStream_t s) {
+    GGAN_CHECK_ARG(A && A2 && P && R > 0 && split > 0 && split < C, "bad argument");
+    const size_t n = (size_t)R * C;
+    GGAN_CHECK_ARG(cdivz(n, kBlock) < 0x7FFFFFFFull, "matrix too large");
+    const dim3 grid((unsigned)cdivz(n, kBlock));
+    if (join) {
+        GGAN_LAUNCH("stage_cols<join>", 0, 8.0 * n, stage_cols_k<true>, grid, dim3(kBlock), 0, s, A, A2, P, R, C, split);
+    } else {
+        GGAN_LAUNCH("stage_cols<deal>", 0, 8.0 * n, stage_cols_k<false>, grid, dim3(kBlock), 0, s, A, A2, P, R, C, split);
+    }
+    return 0;
+}
+
+}  // namespace ggan
 
 extern "C" {
 

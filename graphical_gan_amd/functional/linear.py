@@ -104,10 +104,16 @@ class Gemm2(Function):
     """[a1 | a2] @ w + bias without materialising the concatenation (tf.concat + Linear of the joint critic,
     gan_inference_cifar10.py:246-248): the GEMM reads its A operand from two buffers, its weight gradient likewise, and its
     data gradient leaves in two buffers (ggan_gemm_split).  Falls back to concatenate + Gemm while a double backward is
-    recorded (wali-gp) or when the split is not tile-aligned."""
+    recorded (wali-gp).  A split that is not tile-aligned (the mixture scripts' [z | k] with DIM_LATENT = 8) is staged by the
+    library in its workspace (gemm_stage_cols_k), in front of the product or behind it."""
 
     @staticmethod
     def usable(a1, a2):
+        return a1.shape[1] >= 1 and a2.shape[1] >= 1 and a1.shape[0] == a2.shape[0] and a1.is_cuda
+
+    @staticmethod
+    def aligned(a1, a2):
+        """the split sits on the product kernels' tile grid: what the critic head (ggan_critic_head_*), which plans its own products, takes"""
         return a1.shape[1] % 64 == 0 and a2.shape[1] >= 1 and a1.shape[0] == a2.shape[0]
 
     @staticmethod

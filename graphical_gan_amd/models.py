@@ -2,7 +2,8 @@
 
 One parametrised definition covers the six image scripts (the reference repeats it per file):
   gan_inference_cifar10.py:133-255,261-366      Generator / Extractor / Discriminator, MODE ali | alice* | wali | wali-gp | vegan | vegan-wgan-gp
-  gmgan_inference_cifar10.py:114-301,341-398    + HyperGenerator / HyperExtractor / HyperDiscriminator, MODE local_ep
+  gmgan_inference_cifar10.py:114-336,341-407    + HyperGenerator / HyperExtractor / HyperDiscriminator, MODE local_ep | local_epce (two local
+                                                critics) | ali | alice (one joint critic on (x, z, k)) | vegan (a critic on (z, k)): Config.critic
   gmgan_inference_mnist.py:166-300              28x28x1, crop [:,:,:7,:7], sigmoid output, float input
   gan_inference_mnist.py:122-250                the same nets, but a critic of its own (BatchNorm, two more Linear layers: Config.critic_deep)
   gmgan_inference_face.py:82-274                64x64x3, four conv stages, DIM 32, no BatchNorm, dequantisation
@@ -56,10 +57,13 @@ class Config(object):
                              'vegan-wgan-gp', 'vegan-mmd', 'vegan-kl', 'vegan-ikl', 'vegan-jsd')
         self.agg = self.mode in ('vegan-kl', 'vegan-ikl', 'vegan-jsd')
         self.learn_std, self.z_samples = self.agg, 100               # TYPE_Q, Z_SAMPLES (:41-43)
-        self.latent_critic = self.mode in ('vegan', 'vegan-wgan-gp')
+        # the mixture scripts' critic (gmgan_inference_cifar10.py:233-336,359-379), by MODE: 'local' -- the factorised pair HyperDiscriminator(z, k)
+        # and Discriminator(x, z) of local_ep / local_epce; 'global' -- ONE joint Discriminator(x, z, k) under ali / alice, the GMGAN-G
+        # baseline; 'latent' -- Discriminator(z, k) on codes alone under vegan.  None without a mixture prior.
+        self.critic = self._mixture_critic(self.mode) if n_coms else None
+        self.latent_critic = self.mode in ('vegan', 'vegan-wgan-gp') and not n_coms      # (gan_inference_*: the noisy MLP on z)
         self.lamb = 1.0                                                  # LAMBDA (gan_inference_cifar10.py:62)
         self.no_critic = self.mode == 'vegan-mmd' or self.agg
-        assert not ((self.latent_critic or self.no_critic) and n_coms)
         self.top = self.dim * 2 ** (self.nl - 1)
         self.flat = 16 * self.top
         self.output_dim = self.C * self.S * self.S
@@ -78,6 +82,21 @@ class Config(object):
         self.critic_deep = dataset == 'mnist' and not n_coms and not self.latent_critic and not self.no_critic
         if self.critic_deep and self.bn:
             self.batch_critic = False
+
+    @staticmethod
+    def _mixture_critic(mode):
+        """the critic kind of a mixture script's MODE; the MODEs the reference's gmgan scripts cannot run themselves are refused by name"""
+        kind = {'local_ep': 'local', 'local_epce': 'local', 'ali': 'global', 'alice': 'global', 'vegan': 'latent'}.get(mode)
+        if kind is not None:
+            return kind
+        if mode == 'vegan-wgan-gp':
+            raise NotImplementedError('MODE vegan-wgan-gp with N_COMS: gmgan_inference_cifar10.py:233 builds its critic on (z, k), but the '
+                                      'objective chain (:385-410) has no branch for it and ends in raise(\'NotImplementedError\')')
+        if mode in ('vegan-mmd', 'vegan-kl', 'vegan-ikl', 'vegan-jsd'):
+            raise NotImplementedError('MODE %s with N_COMS: the critic-free MODEs build no net in the gmgan scripts '
+                                      '(gmgan_inference_cifar10.py:303-304) and have no objective there (:385-410)' % mode)
+        raise NotImplementedError('MODE %s with N_COMS: the gmgan scripts\' objective chain (gmgan_inference_cifar10.py:385-410) knows ali, '
+                                  'alice, local_ep, local_epce and vegan only' % mode)
 
 
 class GraphicalGAN(object):
@@ -222,10 +241,10 @@ class GraphicalGAN(object):
             return lib.ops.conv2d.Conv2D(name, cin, cout, 5, x, stride=2, activation=act, grad_rows=grad_rows)
         return F.ActFwd.apply(lib.ops.conv2d.Conv2D(name, cin, cout, 5, x, stride=2, grad_rows=grad_rows), act, 0.2)
 
-    def _lin(self, name, nin, nout, x, act):
+    def _lin(self, name, nin, nout, x, act, split_any=False):
         if self.cfg.fuse:
-            return lib.ops.linear.Linear(name, nin, nout, x, activation=act)
-        return F.ActFwd.apply(lib.ops.linear.Linear(name, nin, nout, x), act, 0.2)
+            return lib.ops.linear.Linear(name, nin, nout, x, activation=act, split_any=split_any)
+        return F.ActFwd.apply(lib.ops.linear.Linear(name, nin, nout, x, split_any=split_any), act, 0.2)
 
     def _bn(self, name, axes, x, act):
         if self.cfg.fuse:
@@ -299,6 +318,12 @@ class GraphicalGAN(object):
         will be differentiated twice (gradient-penalty pass): plain layer composition instead of the fused critic tail"""
         c = self.cfg
         out, z_out = self._critic_stack(x, z, grad_rows, before_z, z_out)
+        if c.critic == 'global':     # gmgan_inference_cifar10.py:329-336: concat -> zkx1 -> Output
+            joint = self._critic_names()[2]
+            if c.fuse:
+                return lib.ops.linear.LinearLReLULinear(joint, c.flat + 512, 512, 'Discriminator.Output', (out, z_out), differentiable=twice)
+            out = self._lin(joint, c.flat + 512, 512, (out, z_out), LRELU)
+            return lib.ops.linear.Linear('Discriminator.Output', 512, 1, out).reshape(-1)
         if c.critic_deep:            # gan_inference_mnist.py:236-248: z1 -> '2' | concat -> zx1 -> zx2 -> Output
             z_out = self._lin('Discriminator.2', 512, 512, z_out, LRELU)
             out = self._lin('Discriminator.zx1', c.flat + 512, 512, (out, z_out), LRELU)
@@ -337,9 +362,10 @@ class GraphicalGAN(object):
         c = self.cfg
         out = x.reshape(-1, c.C, c.S, c.S)
         ch = c.C
+        conv_name = self._critic_names()[0]
         for i in range(c.nl):
             cout = c.dim * 2 ** i
-            name = 'Discriminator.%d' % (i + 1)
+            name = conv_name % (i + 1)
             if c.critic_deep and c.bn and i > 0:              # gan_inference_mnist.py:223-230
                 out = lib.ops.conv2d.Conv2D(name, ch, cout, 5, out, stride=2, grad_rows=grad_rows)
                 out = self._bn('Discriminator.BN%d' % (i + 1), [0, 2, 3], out, LRELU)
@@ -354,8 +380,27 @@ class GraphicalGAN(object):
         if before_z is not None:
             before_z()               # (forward_nets: z's second half may still be in flight on the other stream)
         if z_out is None:            # (else: _critic already ran the z path on the second stream)
-            z_out = self._lin('Discriminator.z1', c.dim_latent, 512, z, LRELU)
+            z_out = self._critic_z(z)
         return out, z_out
+
+    def _critic_names(self):
+        """(conv layers' name pattern, first layer on the codes, Linear on [conv features | code features]) of the critic on images: the
+        reference names the joint critic on (x, z, k) apart from the one on (x, z) (gmgan_inference_cifar10.py:310-330: x1..x3, zk1, zkx1;
+        gmgan_inference_face.py:207-231 keeps 1..4 and spells the last zxk1)"""
+        c = self.cfg
+        if c.critic == 'global':
+            face = c.dataset == 'face'
+            return ('Discriminator.%d' if face else 'Discriminator.x%d'), 'Discriminator.zk1', ('Discriminator.zxk1' if face else 'Discriminator.zkx1')
+        return 'Discriminator.%d', 'Discriminator.z1', 'Discriminator.zx1'
+
+    def _critic_z(self, z):
+        """the image critic's first layer on the codes: z1 on z, or -- the joint critic of the mixture scripts' ali / alice, where z is the
+        pair (z, k) -- zk1 on concat([z, k], 1), which the product reads in place"""
+        c = self.cfg
+        name = self._critic_names()[1]
+        if c.critic == 'global':
+            return self._lin(name, c.dim_latent + c.K, 512, z, LRELU, split_any=True)
+        return self._lin(name, c.dim_latent, 512, z, LRELU)
 
     def LatentDiscriminator(self, z, noise):
         """gan_inference_cifar10.py:192-222: the vegan critic on codes; Gaussian noise (std .3 on the input, .5 after the first
@@ -403,9 +448,44 @@ class GraphicalGAN(object):
                    gen_train_op=res[2], disc_train_op=res[3])
         return out
 
+    def _forward_mixture_latent(self, feed, which, out):
+        """MODE vegan of the mixture scripts (gmgan_inference_cifar10.py:233-251,359-361,405-407): the critic is Discriminator(z, k) under
+        the Hyper* layer names; disc_fake = D(p_z, hyper_p_k), disc_real = D(q_z, q_k) -- the roles _forward_latent has the other way
+        round --, objective gan_inference.vegan with rec_penalty = l2(real_x, G(q_z)).  A critic step evaluates the critic once on
+        [fake; real]; a generator step's cost reads disc_fake alone (the Extractor gets its gradient from the reconstruction term only),
+        so it evaluates the fake half and nothing else."""
+        c, B = self.cfg, self.cfg.B
+        real_x, q_z, p_z, q_k, onehot = out['real_x'], out['q_z'], out['p_z'], out['q_k'], feed['k_onehot']
+        J = lib.objs.gan_inference
+        J.ONLY[0] = which
+        if which == 'disc' and 'Generator.Input.W' not in lib.named_params():
+            # the script's graph holds Generator(q_z) whichever cost is fetched; a critic step that is built first registers the
+            # Generator's variables here, once, so that the var lists below are complete (the pass itself is read by nobody)
+            with torch.no_grad():
+                self.Generator(q_z)
+        with (lib.frozen('Discriminator') if which == 'gen' else lib.frozen()):
+            if which == 'gen':
+                d_fake, d_real = self.HyperDiscriminator(p_z, onehot), None
+            elif which == 'disc' and c.batch_critic:
+                d = self.HyperDiscriminator(F.JoinRows.apply(p_z.detach(), q_z.detach()), F.JoinRows.apply(onehot, q_k.detach()))
+                d_fake, d_real = F.SplitRows.apply(d, B)
+            else:
+                det = (lambda t: t.detach()) if which == 'disc' else (lambda t: t)
+                d_fake, d_real = self.HyperDiscriminator(det(p_z), onehot), self.HyperDiscriminator(det(q_z), det(q_k))
+        rec = F.Distance.apply(real_x, self.Generator(out.get('q_z_rec', q_z)), 2, 1.0) if which != 'disc' else None
+        gen_params, disc_params = self._var_lists()
+        res = J.vegan(d_fake, d_real, rec, gen_params, disc_params, c.lamb, lr=c.lr, beta1=c.beta1, one_launch=True)
+        J.ONLY[0] = None
+        out.update(disc_fake=d_fake, disc_real=d_real, rec_penalty=rec, gen_cost=res[0], disc_cost=res[1],
+                   gen_train_op=res[2], disc_train_op=res[3])
+        return out
+
     def HyperDiscriminator(self, z, k):
+        """the critic on (z, k): one of the two local critics of local_ep / local_epce (gmgan_inference_cifar10.py:255-271), and under the
+        same layer names THE critic of the mixture scripts' vegan (:235-251) -- no BatchNorm, no noise layers, dropout the identity"""
         c = self.cfg
-        out = self._lin('Discriminator.HyperInput', c.dim_latent + c.K, 512, (z, k), LRELU)     # Linear on concat([z, k], 1)
+        # Linear on concat([z, k], 1); under vegan z has DIM_LATENT = 8 columns, a split the library stages (functional.Gemm2)
+        out = self._lin('Discriminator.HyperInput', c.dim_latent + c.K, 512, (z, k), LRELU, split_any=c.critic == 'latent')
         out = self._lin('Discriminator.Hyper2', 512, 512, out, LRELU)
         if c.fuse:
             return lib.ops.linear.LinearLReLULinear('Discriminator.Hyper3', 512, 512, 'Discriminator.HyperOutput', out)
@@ -526,6 +606,11 @@ class GraphicalGAN(object):
         early, self._early = self._early, False
         p_z, p_z_gen = F.fanout(p_z, 2) if (c.K and c.fuse) else (p_z, p_z)          # (critics | Generator)
         fan_q = (lambda q: F.fanout(q, 2)) if (c.K and c.fuse) else (lambda q: (q, q))     # (critics | HyperExtractor)
+        if c.fuse and c.mode in ('alice', 'vegan') and c.critic in ('global', 'latent'):
+            # (| Generator(q_z) of the reconstruction term: a third alias, so that its gradient too is summed by this library's launch)
+            fan3 = fan_q = lambda q: F.fanout(q, 3)
+        else:
+            fan3 = None
         if fork and early:
             # begin_nets() forked before the noise launch: the Extractor pass (which reads no noise) is a ROOT branch of the step
             # graph on the second stream, the Generator pass follows the noise launch on this one.  The branches are joined
@@ -541,10 +626,13 @@ class GraphicalGAN(object):
                 real_x = self.real_x(feed, xs[1], defer=True)
                 ev_x = torch.cuda.Event()
                 q_src = self.Extractor(real_x, zs[1], after_first=lambda: ev_x.record(self._side))
-                q_z, q_z_h = fan_q(q_src)
+                fq = fan_q(q_src)
+                q_z, q_z_h = fq[0], fq[1]
                 if isinstance(real_x, F.PendingCast):
                     real_x = real_x.out
                 out = dict(real_x=real_x, q_z=q_z, p_z=p_z, q_z_src=q_src)
+                if fan3 is not None:
+                    out['q_z_rec'] = fq[2]
                 if c.K:
                     ks = F.RowSlot(feed['k_pair'], B, 2 * B) if (c.batch_critic and 'k_pair' in feed) else None
                     _, out['q_k'] = self.HyperExtractor(q_z_h, feed.get('gumbel_u'), ks)
@@ -565,14 +653,19 @@ class GraphicalGAN(object):
             q_z, q_mean, q_std = self.Extractor(real_x, eps=feed['q_eps'])
             return dict(real_x=real_x, q_z=q_z, q_z_mean=q_mean, q_z_std=q_std, p_z=p_z)
         q_src = self.Extractor(real_x, zs[1])
-        q_z, q_z_h = fan_q(q_src)
+        fq = fan_q(q_src)
+        q_z, q_z_h = fq[0], fq[1]
         if isinstance(real_x, F.PendingCast):
             real_x = real_x.out
         out = dict(real_x=real_x, q_z=q_z, p_z=p_z, q_z_src=q_src)
+        if fan3 is not None:
+            out['q_z_rec'] = fq[2]
         if c.K:
             ks = F.RowSlot(feed['k_pair'], B, 2 * B) if (c.batch_critic and 'k_pair' in feed) else None
             _, q_k = self.HyperExtractor(q_z_h, feed.get('gumbel_u'), ks)
             out['q_k'] = q_k
+        if c.critic == 'latent':       # (the critic reads codes alone: nothing fetches Generator(p_z), and TF prunes it)
+            return out
         if fork:
             cur.wait_stream(self._side)
         else:
@@ -585,11 +678,14 @@ class GraphicalGAN(object):
         is not part of gen_cost); None builds everything.  nets: a forward_nets() result to continue from."""
         c = self.cfg
         out = dict(nets) if nets is not None else self.forward_nets(feed)
-        defer = c.batch_critic and which in ('gen', 'disc') and not (c.latent_critic or c.agg or c.mode == 'vegan-mmd')
+        defer = (c.batch_critic and which in ('gen', 'disc')
+                 and not (c.latent_critic or c.critic == 'latent' or c.agg or c.mode == 'vegan-mmd'))
         if not defer:
             self.join_side()
         if c.latent_critic:
             return self._forward_latent(feed, which, out)
+        if c.critic == 'latent':
+            return self._forward_mixture_latent(feed, which, out)
         if c.agg:
             rec = 1. * lib.utils.distance.distance(out['real_x'], self.Generator(out['q_z']), 'l2')
             gen_params, _ = self._var_lists()
@@ -647,7 +743,7 @@ class GraphicalGAN(object):
         # (engine.Trainer, head_hint) runs the backward at once: the critic head leaves that cost's gradient behind with its forward
         hint, hkind = None, 'bce'
         if (getattr(self, 'head_hint', False) and batched and c.fuse and real_x.is_cuda and not os.environ.get('GGAN_NO_HEAD_HINT')):
-            if c.mode == 'ali' and not c.K:
+            if c.mode == 'ali' and c.critic in (None, 'global'):       # (the mixture scripts' joint critic on (x, z, k): the same one head, the same cost)
                 fl, rl = (1.0, 0.0) if which == 'gen' else (0.0, 1.0)
                 hint = [(c.B, fl, 1.0), (c.B, rl, 1.0)]
             elif c.mode == 'local_ep' and c.K:
@@ -667,7 +763,14 @@ class GraphicalGAN(object):
             torch.cuda.current_stream(real_x.device).wait_stream(self._gp_stream)
         gen_params, disc_params = self._var_lists()
         rec_penalty = None
-        if which != 'disc' and c.mode in ('alice', 'alice-z', 'alice-x', 'local_epce'):
+        if which != 'disc' and c.critic == 'global' and c.mode == 'alice':
+            # gmgan_inference_cifar10.py:389-393: l2(real_x, G(q_z)) alone -- the script has the p_z and the k terms commented out
+            # (the Generator's second pass of the step reaches its weights through second autograd leaves: the optimizer sums the two
+            #  contributions of every weight where it packs the bucket, as for the wali-gp penalty pass -- no addition launch per weight)
+            with lib.second_leaf():
+                rec_x = self.Generator(out.get('q_z_rec', q_z))
+            rec_penalty = out['rec_penalty'] = F.Distance.apply(real_x, rec_x, 2, 1.0)
+        elif which != 'disc' and c.mode in ('alice', 'alice-z', 'alice-x', 'local_epce'):
             D = lib.utils.distance.distance
             if c.mode != 'alice-x':
                 rec_penalty = 1. * D(real_x, self.Generator(q_z), 'l2')
@@ -678,8 +781,8 @@ class GraphicalGAN(object):
         if c.mode == 'local_epce':
             res = J.local_epce(d_fake, d_real, rec_penalty, gen_params, disc_params, lr=c.lr, beta1=c.beta1)
         elif c.mode.startswith('alice'):
-            res = J.alice(d_fake, d_real, rec_penalty, gen_params, disc_params, lr=c.lr, beta1=c.beta1)
-        elif c.K:
+            res = J.alice(d_fake, d_real, rec_penalty, gen_params, disc_params, lr=c.lr, beta1=c.beta1, one_launch=c.critic == 'global')
+        elif c.critic == 'local':
             res = J.local_ep(d_fake, d_real, gen_params, disc_params, lr=c.lr, beta1=c.beta1)
         elif c.mode == 'wali':           # RMSProp, critic weights clipped inside the critic's update kernel
             r = J.wali(d_fake, d_real, gen_params, disc_params)
@@ -719,6 +822,8 @@ class GraphicalGAN(object):
         p_z, q_z, q_k, and the conv stack's data-gradient is needed for the fake half only (grad_rows)."""
         c = self.cfg
         if not batched:
+            if c.critic == 'global':       # gmgan_inference_cifar10.py:376-377
+                return self.Discriminator(fake_x, (p_z, onehot)), self.Discriminator(real_x, (q_z, q_k))
             if c.K:
                 return ([self.HyperDiscriminator(p_z, onehot), self.Discriminator(fake_x, p_z)],
                         [self.HyperDiscriminator(q_z, q_k), self.Discriminator(real_x, q_z)])
@@ -731,7 +836,9 @@ class GraphicalGAN(object):
         assert detach or not real_x.requires_grad, 'batched critic with grad_rows: real_x must not require a gradient'
         self.join_side(x_only=True)
         x_cat, z_cat = F.JoinRows.apply(fake_x, real_x), F.JoinRows.apply(p_z, q_z)
-        z_cat, z_cat_h = F.fanout(z_cat, 2) if (c.K and c.fuse) else (z_cat, z_cat)          # (joint critic | mixture critic)
+        z_cat, z_cat_h = F.fanout(z_cat, 2) if (c.critic == 'local' and c.fuse) else (z_cat, z_cat)          # (joint critic | mixture critic)
+        # the joint critic on (x, z, k): its first layer on the codes reads the pairs [p_z ; q_z] and [one-hot draw ; q_k] side by side
+        z_in = (z_cat, F.JoinRows.apply(onehot, q_k)) if c.critic == 'global' else z_cat
         z_out = None
         pj = self._pending_join
         gp_on_side = self._gp_stream is not None and self.cfg.mode == 'wali-gp' and detach and self.fork_now
@@ -741,11 +848,11 @@ class GraphicalGAN(object):
             # before the critic's tail then waits for z_out instead of q_z
             with torch.cuda.stream(self._side):
                 self._side.wait_event(self._noise_event)
-                z_out = self._lin('Discriminator.z1', c.dim_latent, 512, z_cat, LRELU)
+                z_out = self._critic_z(z_in)
                 ev = torch.cuda.Event()
                 ev.record(self._side)
                 pj[2] = ev
-        fork_h = bool(c.K) and self.fork_nets and self.fork_now and x_cat.is_cuda
+        fork_h = c.critic == 'local' and self.fork_nets and self.fork_now and x_cat.is_cuda
         if fork_h:
             # the mixture critic on (z, k) is a chain of ~12 short launches per direction that reads nothing of the image critic: it
             # runs on the second stream beside the conv stack (autograd keeps each pass's backward on the stream of its forward)
@@ -756,20 +863,20 @@ class GraphicalGAN(object):
             ev_z = torch.cuda.Event()
             with torch.cuda.stream(self._side):
                 if z_out is None:
-                    z_out = self._lin('Discriminator.z1', c.dim_latent, 512, z_cat, LRELU)      # (the image critic's z path too)
+                    z_out = self._critic_z(z_in)      # (the image critic's z path too)
                     ev_z.record(self._side)
                 else:
                     ev_z = None
                 h = self.HyperDiscriminator(z_cat_h, F.JoinRows.apply(onehot, q_k))
             before = (lambda: cur.wait_event(ev_z)) if ev_z is not None else self.join_side
-            d = self.Discriminator(x_cat, z_cat, grad_rows=None if detach else B, before_z=before, z_out=z_out)
+            d = self.Discriminator(x_cat, z_in, grad_rows=None if detach else B, before_z=before, z_out=z_out)
         else:
-            d = self.Discriminator(x_cat, z_cat, grad_rows=None if detach else B, before_z=self.join_side, z_out=z_out)
+            d = self.Discriminator(x_cat, z_in, grad_rows=None if detach else B, before_z=self.join_side, z_out=z_out)
         if fork_h:
             cur.wait_stream(self._side)
-        elif c.K:
+        elif c.critic == 'local':
             h = self.HyperDiscriminator(z_cat_h, F.JoinRows.apply(onehot, q_k))
-        if c.K:
+        if c.critic == 'local':
             (hf, hr), (df, dr) = F.SplitRows.apply(h, B), F.SplitRows.apply(d, B)
             return [hf, df], [hr, dr]
         return F.SplitRows.apply(d, B)

@@ -412,6 +412,10 @@ def config(S):
         raise NotImplementedError('MODE_K = %r: gmgan_inference_face builds only the CONCRETE relaxation' % mode_k)
     if S['MODE'] == 'vae':
         raise NotImplementedError('MODE vae: the reference Generator returns no decoder statistics (DESIGN.md 8)')
+    if S['DATASET'] == 'face' and S.get('N_COMS') and S['MODE'] not in ('ali', 'local_ep'):
+        # (gmgan_inference_face.py:35,148,204,268-277: the script builds the local critics or the joint one and has objectives for
+        #  ali and local_ep alone; every other MODE ends in its raise('NotImplementedError'))
+        raise NotImplementedError('MODE = %r: gmgan_inference_face runs ali and local_ep only (gmgan_inference_face.py:268-277)' % S['MODE'])
     assert S.get('DISTANCE_X', 'l2') == 'l2' and S.get('LAMBDA', 1.) == 1. and S.get('BETA1', .5) == .5 and S.get('Z_SAMPLES', 100) == 100, S
     assert S.get('DIM_G', S.get('DIM')) == S.get('DIM_D', S.get('DIM')), 'one model width'
     return Config(S['DATASET'], batch_size=S['BATCH_SIZE'], n_coms=S.get('N_COMS', 0), mode=S['MODE'], dim=S.get('DIM', S.get('DIM_G')),

@@ -70,19 +70,37 @@ def local_epce(disc_fake_list, disc_real_list, rec_penalty, gen_params, disc_par
     return gen_cost, disc_cost, TrainOp(gen_opt, gen_cost), TrainOp(disc_opt, disc_cost)
 
 
-def alice(disc_fake, disc_real, rec_penalty, gen_params, disc_params, lr=2e-4, beta1=0.5, s_f=None):
-    """tflib/objs/gan_inference.py:162-195: the ali costs, generator side + s_f + rec_penalty."""
+def _plus_one_launch(cost, term):
+    """cost + term, both one-element, as ONE launch of this library in each direction (a two-term MeanSum: the mean of one element is
+    the element) instead of at::add and its backward"""
+    if cost is None or term is None:
+        return cost
+    return F.MeanSum.apply((1.0, 1.0), _val(cost), term)
+
+
+def alice(disc_fake, disc_real, rec_penalty, gen_params, disc_params, lr=2e-4, beta1=0.5, s_f=None, one_launch=False):
+    """tflib/objs/gan_inference.py:162-195: the ali costs, generator side + s_f + rec_penalty.  one_launch (extension; needs s_f None):
+    the reconstruction term is added by a launch of this library (_plus_one_launch)."""
     gen_cost, disc_cost = _bce_costs([disc_fake], [disc_real], [1.0])
-    gen_cost = _plus(gen_cost, s_f, rec_penalty)
+    if one_launch:
+        assert s_f is None
+        gen_cost = _plus_one_launch(gen_cost, rec_penalty)
+    else:
+        gen_cost = _plus(gen_cost, s_f, rec_penalty)
     gen_opt = get_optimizer('gen', gen_params, lr=lr, beta1=beta1, beta2=0.999)
     disc_opt = get_optimizer('disc', disc_params, lr=lr, beta1=beta1, beta2=0.999)
     return gen_cost, disc_cost, TrainOp(gen_opt, gen_cost), TrainOp(disc_opt, disc_cost)
 
 
-def vegan(disc_fake, disc_real, rec_penalty, gen_params, disc_params, lamb, lr=2e-4, beta1=.5, s_f=None):
-    """tflib/objs/gan_inference.py:197-225: gen = lamb*(BCE(fake,1) + s_f) + rec_penalty; disc = lamb/2 * ali critic cost."""
+def vegan(disc_fake, disc_real, rec_penalty, gen_params, disc_params, lamb, lr=2e-4, beta1=.5, s_f=None, one_launch=False):
+    """tflib/objs/gan_inference.py:197-225: gen = lamb*(BCE(fake,1) + s_f) + rec_penalty; disc = lamb/2 * ali critic cost.
+    one_launch (extension; needs s_f None): lamb is the BCE term's weight inside its launch and the reconstruction term is added by a
+    launch of this library (_plus_one_launch)."""
     gen_cost = disc_cost = None
-    if ONLY[0] != 'disc':
+    if ONLY[0] != 'disc' and one_launch:
+        assert s_f is None
+        gen_cost = _plus_one_launch(F.BceSum.apply((1.0,), (float(lamb),), disc_fake), rec_penalty)
+    elif ONLY[0] != 'disc':
         gen_cost = F.BceSum.apply((1.0,), (1.0,), disc_fake)
         gen_cost = _val(_plus(gen_cost, s_f)) * float(lamb)
         gen_cost = _plus(gen_cost, rec_penalty)

@@ -60,9 +60,10 @@ def _initial(initialization, input_dim, output_dim):
 
 
 def Linear(name, input_dim, output_dim, inputs, biases=True, initialization=None, weightnorm=None, gain=1.,
-           activation=None, alpha=0.2, out=None):
+           activation=None, alpha=0.2, out=None, split_any=False):
     """Same signature as the reference; `activation`/`alpha` are an optional fused epilogue and `out` an optional
-    functional.RowSlot the result is written into (extensions)."""
+    functional.RowSlot the result is written into (extensions).  split_any: a pair of inputs whose split is off the product kernels'
+    tile grid goes through functional.Gemm2 all the same (the library stages it) instead of a concatenation here."""
     if _draw(name + '.W'):
         weight_values = _initial(initialization, input_dim, output_dim)
         weight_values *= gain
@@ -82,7 +83,7 @@ def Linear(name, input_dim, output_dim, inputs, biases=True, initialization=None
         # extension: a pair (x1, x2) stands for tf.concat([x1, x2], 1) -- the GEMM reads both operands in place
         x1, x2 = inputs
         assert x1.dim() == 2 and x2.dim() == 2 and x1.shape[1] + x2.shape[1] == input_dim, (name, x1.shape, x2.shape, input_dim)
-        if out is None and F.Gemm2.usable(x1, x2):
+        if out is None and (F.Gemm2.aligned(x1, x2) or (split_any and F.Gemm2.usable(x1, x2))):
             return F.Gemm2.apply(x1, x2, weight, b, act, float(alpha))
         import torch
         inputs = torch.cat([x1, x2], 1)
@@ -103,7 +104,7 @@ def LinearLReLULinear(name1, input_dim, hidden_dim, name2, inputs, alpha=0.2, di
     pair = isinstance(inputs, (tuple, list))
     x1, x2 = inputs if pair else (inputs, None)
     usable = (not differentiable and x1.dim() == 2 and hidden_dim % 4 == 0
-              and (x2 is None or (x2.dim() == 2 and F.Gemm2.usable(x1, x2))))
+              and (x2 is None or (x2.dim() == 2 and F.Gemm2.aligned(x1, x2))))
     if not usable:
         h = Linear(name1, input_dim, hidden_dim, inputs, activation=F.ACT_LRELU, alpha=alpha)
         return Linear(name2, hidden_dim, 1, h).reshape(-1)

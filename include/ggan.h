@@ -114,9 +114,14 @@ int ggan_linear_bwd_weight_act(int M, int N, int K, const float* x, const float*
  * gan_inference_cifar10.py:246-248 tf.concat + Linear, and its two gradients):
  *   A2 != NULL: op(A) = [A | A2] side by side along the SECOND stored dimension of A (k when ta == 0, m when ta == 1); the
  *               first a_split columns come from A (leading dimension a_split), the rest from A2 (leading dimension whole -
- *               a_split); a_split must be a multiple of 64.
+ *               a_split); a_split a multiple of 64 (of 16 where the product is one the skinny kernel takes) reads both in place, any
+ *               other 0 < a_split < whole is staged side by side at
+ *               the end of the workspace by one pointwise launch in front of the product (the mixture scripts' Linear on [z | k]
+ *               with DIM_LATENT = 8, gmgan_inference_cifar10.py:74,236-237): the workspace must hold that matrix.
  *   C2 != NULL: output columns [0, c_split) go to C (leading dimension c_split), [c_split, N) to C2 (leading dimension N -
- *               c_split); c_split a multiple of 64; no bias / activation / column sums with a split output.
+ *               c_split); no bias / activation / column sums with a split output.  c_split a multiple of 64 stores directly,
+ *               any other 0 < c_split < N is dealt out of the workspace by one pointwise launch behind the product.  Not both
+ *               A2 and C2 where either split is off the grid.
  *   colsum_b (may be NULL; tb == 0 only): column sums of B, as ggan_gemm_colsum. */
 int ggan_gemm_split(int ta, int tb, int M, int N, int K, const float* A, const float* A2, int a_split, const float* B,
                     const float* bias, float* C, float* C2, int c_split, float* colsum_b, int act, float alpha, void* ws,

@@ -7,7 +7,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from graphical_gan_amd import run
 
-MODE = 'local_ep'  # local_ep, local_epce
+MODE = 'local_ep'  # ali, local_ep, alice, local_epce, vegan
 MODE_K = 'CONCRETE'  # CONCRETE, STRAIGHT_THROUGHT_CONCRETE, STRAIGHT_THROUGHT (REINFORCE is not built)
 SETTINGS = run.reference_block(__file__, MODE=MODE, MODE_K=MODE_K)
 # edit the block here, e.g. SETTINGS['N_COMS'] = 10 -- or pass it to reference_block, which then derives N_VIS etc. from it
