@@ -4,59 +4,43 @@
 //   ggan_probe_solve    W = (G + ridge I)^-1 R by an fp64 Cholesky factorisation in one workgroup's LDS, bias = counts / n;
 //   ggan_probe_predict  argmax_c of bias + zs W per row (the lowest class on a tie), the number of rows that hit their label.
 // The reduction of the normal equations runs over the ROW index -- tens of thousands of rows into at most 128 x (128 + 32) outputs --, the
-// transpose of the set-level Gram sweeps of set_rows.h, so it has a skeleton of its own: the rows are cut into blocks of kRB = 256, a
-// workgroup sums ONE block in fp32 in row order (v_mfma_f32_32x32x2_f32: the standardised rows are both operands of the G tiles, and a
-// one-hot of the label made in registers is the B operand of the R tiles), and a second launch adds the block partials in fp64 in block
-// order.  The moments are two such passes with fp64 partials (the second centred by the fp64 mean: no E[z^2] - mean^2).  Nothing here
+// transpose of the set-level Gram sweeps of set_rows.h, so it has a skeleton of its own (row_blocks.h, shared with frechet.hip): the rows
+// are cut into blocks of kRB = 256, a workgroup sums ONE block in fp32 in row order (v_mfma_f32_32x32x2_f32: the standardised rows are both
+// operands of the G tiles, and a one-hot of the label made in registers is the B operand of the R tiles), and a second launch adds the
+// block partials in fp64 in block order.  The moments are two such passes with fp64 partials (the second centred by the fp64 mean: no E[z^2] - mean^2).  Nothing here
 // depends on the launch shape and there is no floating-point atomic: two calls give the same bits.
 #include <math.h>
-#include "common.h"
+#include "row_blocks.h"
 using namespace ggan;
 
 namespace {
 
-constexpr int kMaxD = GGAN_PROBE_MAX_DIM, kMaxC = GGAN_PROBE_MAX_CLASSES, kRB = GGAN_PROBE_ROW_BLOCK;
+constexpr int kMaxD = GGAN_PROBE_MAX_DIM, kMaxC = GGAN_PROBE_MAX_CLASSES;
 constexpr int kMaxRows = 131072;
-constexpr int kKC = 64;            // rows of a block staged per step of probe_normal_k
 constexpr int kPR = 64;            // rows per workgroup of probe_predict_k
 constexpr int kCnt = kMaxC + 1;    // label histogram of a block: the classes and, last, the labels out of range
-static_assert(kRB == 256 && kRB % kKC == 0 && kMaxC == 32 && kMaxD % 32 == 0, "the kernels below assume these");
+static_assert(kMaxC == 32 && kMaxD % 32 == 0, "the kernels below assume these");
 
 inline bool shape_ok(int rows, int d, int C) { return rows >= 1 && rows <= kMaxRows && d >= 1 && d <= kMaxD && C >= 1 && C <= kMaxC; }
-inline int row_blocks(int n) { return cdiv(n, kRB); }
-inline size_t align16(size_t b) { return (b + 15) & ~(size_t)15; }
 
 // ---- moments ----------------------------------------------------------------------------------------------------------------------
-// one block of kRB rows: part[blk][c] = sum over its rows of z (PASS 0) or of (z - mu_c)^2 (PASS 1), in fp64.  cw = the power of two >=
-// d: thread (g, col) = (tid / cw, tid % cw) walks the rows g, g + 256 / cw, ... of its column, the groups are added in group order.
+// one block of kRB rows: part[blk][c] = sum over its rows of z (PASS 0) or of (z - mu_c)^2 (PASS 1), in fp64 (block_colsum_*).
 // PASS 0 also counts the block's labels: cnt[blk][0 .. 32) per class, cnt[blk][32] those outside [0, C) (no label is an index).
 template <int PASS>
 __global__ __launch_bounds__(256) void probe_colsum_k(const float* __restrict__ Z, const int* __restrict__ y, int n, int d, int C, int lg,
                                                       const double* __restrict__ mu, double* __restrict__ part, int* __restrict__ cnt) {
     __shared__ double sm[256];
     __shared__ int hist[kCnt];
-    const int tid = threadIdx.x, cw = 1 << lg, col = tid & (cw - 1), g = tid >> lg, ng = 256 >> lg;
+    const int tid = threadIdx.x;
     const int r0 = blockIdx.x * kRB, r1 = min(r0 + kRB, n);
-    double acc = 0.0;
-    if (col < d) {
-        const double m = PASS ? mu[col] : 0.0;
-        for (int r = r0 + g; r < r1; r += ng) {
-            const double v = (double)Z[(size_t)r * d + col] - m;
-            acc += PASS ? v * v : v;
-        }
-    }
-    sm[tid] = acc;
+    sm[tid] = block_colsum_thread<PASS>(Z, n, d, lg, mu);
     if (PASS == 0 && tid < kCnt) hist[tid] = 0;
     __syncthreads();
     if (PASS == 0 && r0 + tid < r1) {
         const int l = y[r0 + tid];
         atomicAdd(&hist[(l >= 0 && l < C) ? l : kMaxC], 1);
     }
-    if (tid < cw && tid < d) {
-        double t = 0.0;
-        for (int q = 0; q < ng; ++q) t += sm[q * cw + tid];
-        part[(size_t)blockIdx.x * d + tid] = t;
-    }
+    block_colsum_store(sm, d, lg, part);
     if (PASS == 0) {
         __syncthreads();
         if (tid < kCnt) cnt[(size_t)blockIdx.x * kCnt + tid] = hist[tid];
@@ -67,9 +51,7 @@ __global__ __launch_bounds__(256) void probe_colsum_k(const float* __restrict__ 
 __global__ __launch_bounds__(kMaxD) void probe_mean_k(const double* __restrict__ part, int nblk, int n, int d, double* __restrict__ mu) {
     const int c = threadIdx.x;
     if (c >= d) return;
-    double t = 0.0;
-    for (int b = 0; b < nblk; ++b) t += part[(size_t)b * d + c];
-    mu[c] = t / (double)n;
+    mu[c] = blocks_sum(part, nblk, d, c) / (double)n;
 }
 
 __global__ __launch_bounds__(kMaxD) void probe_moments_final_k(const double* __restrict__ part, const int* __restrict__ cnt,
@@ -82,9 +64,7 @@ __global__ __launch_bounds__(kMaxD) void probe_moments_final_k(const double* __r
     __syncthreads();
     int bits = 0;
     if (c < d) {
-        double t = 0.0;
-        for (int b = 0; b < nblk; ++b) t += part[(size_t)b * d + c];
-        const double v = t / (double)n, m = mu[c];
+        const double v = blocks_sum(part, nblk, d, c) / (double)n, m = mu[c];
         const float s = v > 0.0 ? (float)(1.0 / sqrt(v)) : 0.f;
         if (!isfinite(m) || !isfinite(v) || !isfinite(s)) bits |= GGAN_PROBE_NONFINITE;
         mean[c] = (float)m;
@@ -109,73 +89,33 @@ struct NormalParams {
     int n, d, C;
 };
 
-// one block of kRB rows, d padded to DP = 32 T columns (a padded column is all zeros).  The outputs are T * T tiles of G and T tiles of R,
-// 32 x 32 each, dealt to the four waves round-robin; the reduction index of every MFMA is the row: lane l holds A[i = l & 31][k = l >> 5]
-// = zs[row k][column i] and B[k][j = l & 31] = zs[row k][column j] (G) or [label of row k == j] (R), so a tile is the fp32 sum over the
-// block's rows in row order.  The rows are staged kKC at a time, standardised, as zs[row][column]: a fragment read is 32 consecutive
-// floats per half-wave, and the row stride LD = 32 mod 64 puts the two halves of a wave on different banks.
+// one block of kRB rows through block_gram (row_blocks.h): the T * T tiles of G and T tiles of R, the rows standardised as they are staged,
+// the B operand of an R tile a one-hot of the staged label made in a register
 template <int T>
 __global__ __launch_bounds__(256) void probe_normal_k(const NormalParams P) {
-    constexpr int DP = 32 * T, LD = (DP % 64 == 0) ? DP + 32 : DP, NT = T * T + T, NQ = (NT + 3) / 4;
-    __shared__ float zs[kKC * LD];
-    __shared__ float mu_s[DP], is_s[DP];
+    using S = GramBlock<T, T>;
+    __shared__ float zs[kKC * S::LD];
+    __shared__ float mu_s[S::DP], is_s[S::DP];
     __shared__ int lab[kKC];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, half = lane >> 5;
-    for (int c = tid; c < DP; c += 256) {
+    const int tid = threadIdx.x;
+    for (int c = tid; c < S::DP; c += 256) {
         mu_s[c] = c < P.d ? P.mean[c] : 0.f;
         is_s[c] = c < P.d ? P.inv_std[c] : 0.f;
     }
-    f32x16 acc[NQ];
-#pragma unroll
-    for (int q = 0; q < NQ; ++q)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[q][r] = 0.f;
-    const int r0 = blockIdx.x * kRB;
-    for (int s = 0; s < kRB / kKC; ++s) {
-        const int rs = r0 + s * kKC;
-        if (rs >= P.n) break;                      // (the same for the whole workgroup)
-        __syncthreads();                           // the reads of the step before; mu_s / is_s the first time
-        for (int e = tid; e < kKC * DP; e += 256) {
-            const int k = e / DP, c = e % DP, r = rs + k;
-            float v = 0.f;
-            if (r < P.n && c < P.d) v = (P.Z[(size_t)r * P.d + c] - mu_s[c]) * is_s[c];
-            zs[k * LD + c] = v;
-        }
-        if (tid < kKC) lab[tid] = rs + tid < P.n ? P.y[rs + tid] : -1;      // (a row past the end matches no class)
-        __syncthreads();
-        for (int kk = 0; kk < kKC; kk += 2) {
-            const int k = kk + half;
-#pragma unroll
-            for (int q = 0; q < NQ; ++q) {
-                const int t = wave + 4 * q;
-                if (t < NT) {                      // (wave-uniform)
-                    const bool is_g = t < T * T;
-                    const int ti = is_g ? t / T : t - T * T;
-                    const float a = zs[k * LD + ti * 32 + l31];
-                    const float b = is_g ? zs[k * LD + (t % T) * 32 + l31] : (lab[k] == l31 ? 1.f : 0.f);
-                    acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc[q], 0, 0, 0);
-                }
-            }
-        }
-    }
     float* out = P.part + (size_t)blockIdx.x * ((size_t)P.d * P.d + (size_t)P.d * P.C);
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-        const int t = wave + 4 * q;
-        if (t >= NT) continue;
-        const bool is_g = t < T * T;
-        const int ti = is_g ? t / T : t - T * T, j = is_g ? (t % T) * 32 + l31 : l31;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int i = ti * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;       // the 32x32 accumulator map: column = lane & 31
-            if (i >= P.d) continue;
+    block_gram<T, T>(
+        P.n, P.d, zs, [&](int r, int c) { return (P.Z[(size_t)r * P.d + c] - mu_s[c]) * is_s[c]; },
+        [&](int rs) {
+            if (tid < kKC) lab[tid] = rs + tid < P.n ? P.y[rs + tid] : -1;      // (a row past the end matches no class)
+        },
+        [&](int k, int j) { return lab[k] == j ? 1.f : 0.f; },
+        [&](bool is_g, int i, int j, float v) {
             if (is_g) {
-                if (j < P.d) out[(size_t)i * P.d + j] = acc[q][r];
+                if (j < P.d) out[(size_t)i * P.d + j] = v;
             } else if (j < P.C) {
-                out[(size_t)P.d * P.d + (size_t)i * P.C + j] = acc[q][r];
+                out[(size_t)P.d * P.d + (size_t)i * P.C + j] = v;
             }
-        }
-    }
+        });
 }
 
 // element e of [G; R]: the block partials in fp64 in block order, over n, rounded once
@@ -315,12 +255,6 @@ __global__ __launch_bounds__(256) void probe_predict_k(const float* __restrict__
         const int hits = __popcll(__ballot(hit));
         if ((tid & 63) == 0 && hits) atomicAdd(correct, hits);
     }
-}
-
-inline int log2_ceil(int d) {
-    int lg = 0;
-    while ((1 << lg) < d) ++lg;
-    return lg;
 }
 
 }  // namespace

@@ -33,6 +33,12 @@
                      scored on q_z of the labelled dev set, on its own fit rows, and (xr) the same probe on a fixed random projection of
                      the pixels to DIM_LATENT columns.  A pass of its own, not a row of SET_SCORES: it needs a second split and a fit
                      step, and draws its noise from a state of its own, so no other pass's values move.  Not a pass of the reference.
+  frechet_scores     `dev frechet z` / `dev frechet mean z` / `dev frechet xr` / `dev frechet mean xr`: the Frechet distance between Gaussians
+                     fitted to two sets -- |dmu|^2 + tr S1 + tr S2 - 2 tr (S1 S2)^(1/2), the "FD" of FID, functional.frechet_distance -- of
+                     q_z against as many prior draws (z) and of the dev images against as many generated ones, both through one fixed
+                     random projection to FRECHET_PROJ_DIM columns (xr); the `mean` rows are the |dmu|^2 part.  A pass of its own with a
+                     noise state of its own, no labels needed.  It stands in for tflib/inception_score.py, which needs a download; the
+                     features are not Inception's, so no value is comparable with a published FID.
 
 The passes are safe in the middle of training: they run under torch.no_grad() on the current stream only (no second stream, no
 collective), with a feed dict and a noise generator state of their own -- the Trainer's static feed buffers, ring slots and noise state
@@ -52,7 +58,7 @@ run by SequenceEvaluator on a models_ssgan.StateSpaceGAN under the same rules:
 Each is written as a .png sheet (one sequence per row) and a looping .gif; the bytes of both come from one ggan_video_sheet_u8 launch.
 
 `python -m graphical_gan_amd.evaluate CKPT --script gmgan_inference_mnist [--data-dir DIR]` scores a saved checkpoint
-(`--out-dir DIR --manifold` also writes the latent-space pictures of the two MNIST scripts, `--mmd` adds the two MMD^2 rows, `--prdc` the eight precision / recall / density / coverage rows, `--knn` the two k-NN accuracy rows, `--parzen` the three Parzen-window rows, `--rec` the four reconstruction rows, `--probe` the three linear-probe rows);
+(`--out-dir DIR --manifold` also writes the latent-space pictures of the two MNIST scripts, `--mmd` adds the two MMD^2 rows, `--prdc` the eight precision / recall / density / coverage rows, `--knn` the two k-NN accuracy rows, `--parzen` the three Parzen-window rows, `--rec` the four reconstruction rows, `--probe` the three linear-probe rows, `--frechet` the four Frechet-distance rows);
 `... CKPT --script ssgan_inference_moving_mnist|ssgan_inference_chairs [--data-dir DIR] --out-dir DIR` writes the four pairs of files;
 `--rec` prints the four reconstruction rows of the sequences' frames, and alone needs no --out-dir.
 
@@ -87,6 +93,10 @@ PROBE_RIDGE = 1e-2        # its ridge, on standardised features (settings: PROBE
 PROBE_SLAB_ROWS = 10000   # images it keeps on the device at a time: only the codes of a slab stay
 PROBE_SEED = 104729       # offset of its own noise state, and of its projection matrix, from the evaluator's seed
 PROBE_KEYS = ('dev probe accuracy z', 'fit probe accuracy z', 'dev probe accuracy xr')
+FRECHET_MAX_ROWS = 10000  # rows per set of the frechet_scores pass (settings: FRECHET_MAX_ROWS)
+FRECHET_PROJ_DIM = 128    # columns of its fixed random projection of the pixels: functional.FRECHET_MAX_DIM, whatever DIM_LATENT is
+FRECHET_SEED = 130003     # offset of its own noise state, and of its projection matrix, from the evaluator's seed
+FRECHET_KEYS = ('dev frechet z', 'dev frechet mean z', 'dev frechet xr', 'dev frechet mean xr')
 EVAL_SEED = 7919          # offset of the evaluator's noise seeds from the settings seed (the Trainer's stream of draws is not touched)
 
 # the reference's output file names, per script: (samples, reconstructions), formatted with frame= and mode=
@@ -654,6 +664,85 @@ class Evaluator(_Passes):
             return res, dict(fit=pz, fit_xr=px, fit_z=fit['z'], fit_xr_rows=fit['xr'], fit_y=fit['y'], dev_z=dev['z'], dev_xr=dev['xr'], dev_y=dev['y'])
         return res
 
+    _frechet_rng = _frechet_matrix = None     # the Frechet pass's own noise state and projection matrix, made by its first call
+
+    def _frechet_projection(self):
+        """the fixed random map of the pixels to FRECHET_PROJ_DIM columns: RandomState(seed).normal / sqrt(OUTPUT_DIM), drawn once per
+        evaluator (as _probe_projection, from a seed of its own)"""
+        if self._frechet_matrix is None:
+            rng = np.random.RandomState(int(self.S.get('SEED', 0)) + EVAL_SEED + FRECHET_SEED)
+            P = rng.normal(size=(self.cfg.output_dim, FRECHET_PROJ_DIM)) / np.sqrt(float(self.cfg.output_dim))
+            self._frechet_matrix = torch.as_tensor(P.astype(np.float32)).to(self.device)
+        return self._frechet_matrix
+
+    def _frechet_sets(self, batches, rows):
+        """z = q_z and pz = as many fresh prior draws, built exactly as _score_sets builds them; xr / gxr = real_x / Generator(pz), minibatch
+        by minibatch, taken to the unit pixel range and through _frechet_projection -- over the full minibatches, at most `rows` rows per
+        set.  The images themselves do not stay.  Called inside the pass's guard, under its own noise state."""
+        c = self.cfg
+        X, _ = self._stage(batches)
+        B = c.B
+        n = min(X.shape[0], max(1, int(rows) // B))
+        new = lambda w: torch.empty((n * B, w), dtype=torch.float32, device=self.device)
+        sets = dict(z=new(c.dim_latent), pz=new(c.dim_latent), xr=new(FRECHET_PROJ_DIM), gxr=new(FRECHET_PROJ_DIM))
+        proj = self._frechet_projection()
+        lo = 0.0 if c.out_act == 'sigmoid' else -1.0                      # (as _to_unit)
+
+        def projected(x):
+            x = x.float().reshape(B, -1).contiguous()
+            if lo:
+                x = F.Axpby.apply(x, None, 1.0 / (1.0 - lo), 0.0, -lo / (1.0 - lo))
+            return F.Gemm.apply(x, proj, None, False, False, F.ACT_NONE, 0.0)
+        self.kept = []
+        for i in range(n):
+            at = slice(i * B, (i + 1) * B)
+            self._load(X[i])
+            real_x = self.model.real_x(self.feed)
+            q = self.model.Extractor(real_x, eps=self.feed['q_eps']) if c.agg else self.model.Extractor(real_x)
+            sets['z'][at].copy_(q[0] if isinstance(q, tuple) else q)
+            sets['xr'][at].copy_(projected(real_x))
+            p_z = self.model.HyperGenerator(self.feed['k_onehot'], self.feed['p_z_noise']) if c.K else self.feed['p_z_noise']
+            sets['pz'][at].copy_(p_z)
+            sets['gxr'][at].copy_(projected(self.model.Generator(sets['pz'][at])))
+        return sets
+
+    def frechet_scores(self, batches, return_sets=False):
+        """{'dev frechet z', 'dev frechet mean z', 'dev frechet xr', 'dev frechet mean xr'}: the Frechet distance between Gaussians fitted
+        to two sets (functional.frechet_distance: |dmu|^2 + tr S1 + tr S2 - 2 tr (S1 S2)^(1/2), fp64 behind the moments, singular
+        covariances allowed, not clipped at 0) -- z: q_z of the dev images against as many prior draws (through HyperGenerator with a mixture
+        prior), the sets of `dev mmd z`; xr: the dev images against as many generated ones, pixels in [0, 1], both through one fixed random
+        projection to FRECHET_PROJ_DIM = 128 columns whatever DIM_LATENT is.  The `mean` rows are the |dmu|^2 part of the row in front of
+        them.  Over the full dev minibatches, at most FRECHET_MAX_ROWS rows per set and at least two.  The pass draws from a noise state of
+        its own, swapped into the feed while it runs: every other pass logs the same values, and training reaches the same weights, whether
+        it is on or not.  ONE host synchronisation; a raised status word (a non-finite moment: a diverged model; an eigenvalue iteration
+        that did not converge) gives nan for that pair of rows and one printed message, no exception.  It fits GAUSSIANS, it is biased
+        upward by about d^2 / n -- compare figures at equal row counts --, and xr is not comparable with any published FID.
+        return_sets: (values, {z, pz, xr, gxr}: the device rows)."""
+        S = self.S
+        rows = int(S.get('FRECHET_MAX_ROWS', FRECHET_MAX_ROWS))
+        if rows > F.FRECHET_MAX_ROWS:
+            raise ValueError('FRECHET_MAX_ROWS = %d: at most %d rows per set' % (rows, F.FRECHET_MAX_ROWS))
+        if self.cfg.dim_latent > F.FRECHET_MAX_DIM:
+            raise ValueError('the Frechet pass takes at most %d columns, DIM_LATENT is %d' % (F.FRECHET_MAX_DIM, self.cfg.dim_latent))
+        with self._guard():
+            if self._frechet_rng is None:
+                self._frechet_rng = F.noise_state(self.device, int(S.get('SEED', 0)) + EVAL_SEED + FRECHET_SEED)
+            shared, self.feed['rng_state'] = self.feed['rng_state'], self._frechet_rng
+            try:
+                sets = self._frechet_sets(batches, rows)
+            finally:
+                self.feed['rng_state'] = shared
+            if sets['z'].shape[0] < 2:
+                raise ValueError('the Frechet pass needs at least 2 rows per set')
+            (vz, sz), (vx, sx) = F.frechet_distance(sets['z'], sets['pz']), F.frechet_distance(sets['xr'], sets['gxr'])
+            host = torch.cat([vz[:2], vx[:2], sz.double(), sx.double()]).cpu().numpy()
+        status = (int(host[4]), int(host[5]))
+        if any(status):
+            print('[evaluate] frechet: status %d (z) / %d (xr) -- %d: a non-finite moment or entry, %d: the eigenvalue iteration did not converge '
+                  '-- its values are nan' % (status[0], status[1], F.FRECHET_NONFINITE, F.FRECHET_NOT_CONVERGED))
+        res = {k: (float('nan') if status[i // 2] else float(host[i])) for i, k in enumerate(FRECHET_KEYS)}
+        return (res, sets) if return_sets else res
+
     def manifold(self, batches, out_dir, frame):
         """embeds the point sets of latent_sets with functional.tsne and writes the scatters under the reference's file names; returns
         the paths: the four pictures of gmgan_inference_mnist with a mixture prior, the one of gan_inference_mnist without.  MNIST models
@@ -946,6 +1035,7 @@ def main(argv=None):
     for row in SET_SCORES:
         ap.add_argument('--' + row.name, action='store_true', help=row.help)
     ap.add_argument('--probe', action='store_true', help='also fit a least-squares linear probe on the codes of labelled training rows and score it on the labelled dev set (dev probe accuracy z / fit probe accuracy z / dev probe accuracy xr; image scripts with labelled data)')
+    ap.add_argument('--frechet', action='store_true', help='also score the dev set by the Frechet distance between Gaussians fitted to q_z and prior draws, and to randomly projected dev and generated images (dev frechet z / xr and their mean parts; image scripts; not comparable with a published FID)')
     ap.add_argument('--ema', action='store_true', help="score the averaged generator-side weights the checkpoint holds (its ema/gen/ keys, written by a run with $GGAN_EMA_DECAY) instead of the last iterate: every name gets the suffix ' ema', every file '_ema'; the critic of 'dev gen cost ema' is the live one")
     ap.add_argument('--set', action='append', default=[], metavar='KEY=VALUE', help='override an UPPERCASE setting (int / float / str)')
     a = ap.parse_args(argv)
@@ -967,6 +1057,8 @@ def main(argv=None):
                 ap.error('--%s: %s' % (row.name, row.sequences))
         if a.probe:
             ap.error('--probe: %s' % _NO_CODE)
+        if a.frechet:
+            ap.error('--frechet: %s' % _NO_CODE)
     if a.manifold:          # (checked before anything is built)
         name = os.path.splitext(os.path.basename(a.script))[0]
         if name not in MANIFOLD_SCRIPTS:
@@ -994,16 +1086,17 @@ def main(argv=None):
         # the checkpoint's live ones), and the evaluators only name what they write
         tr.load_params(ema)
         tr.ema_loaded = True
-    res = evaluate_once(tr, S, out_dir=a.out_dir, manifold=a.manifold, probe=a.probe, **{row.name: getattr(a, row.name) for row in SET_SCORES})
+    res = evaluate_once(tr, S, out_dir=a.out_dir, manifold=a.manifold, probe=a.probe, frechet=a.frechet, **{row.name: getattr(a, row.name) for row in SET_SCORES})
     for k in sorted(res):
         print('%s\t%s' % (k, res[k]))
     return res
 
 
-def evaluate_once(tr, S, out_dir=None, frame='eval', manifold=False, probe=False, **scores):
+def evaluate_once(tr, S, out_dir=None, frame='eval', manifold=False, probe=False, frechet=False, **scores):
     """every pass the script's data allow, once -> {name: value}; manifold: the latent-space pictures too (labelled dev data only);
     probe: the three values of Evaluator.probe_scores too, after the set-level scores (image scripts; skipped with one message where the
-    dev set or the training split has no labels);
+    dev set or the training split has no labels); frechet: the four values of Evaluator.frechet_scores too, after those (image scripts; no
+    labels needed);
     scores: the set-level scores of SET_SCORES to add, by name (mmd=True, ...: Evaluator.set_scores' keywords, one build of the sets for all
     of them; a score that needs labels is skipped on unlabelled dev data); a trainer whose weights are averaged ones loaded from a
     checkpoint (tr.ema_loaded, main --ema): names and files carry the suffixes.  The state-space scripts: the video files (with out_dir)
@@ -1014,6 +1107,8 @@ def evaluate_once(tr, S, out_dir=None, frame='eval', manifold=False, probe=False
     if S['DATASET'] in run.SEQUENCE_DATASETS:       # the video passes: files only (train_data: the first dev minibatch)
         if probe:
             raise ValueError('probe: %s' % _NO_CODE)
+        if frechet:
+            raise ValueError('frechet: %s' % _NO_CODE)
         ev = SequenceEvaluator(tr, S)
         ev.weights = 'ema' if ema_names else 'live'
         dev, _ = run.eval_sets(S, tr.model, tr.device)
@@ -1043,6 +1138,8 @@ def evaluate_once(tr, S, out_dir=None, frame='eval', manifold=False, probe=False
             print('[evaluate] dev probe accuracy skipped: no labelled dev set and training split')
         else:
             res.update(ev.tag(ev.probe_scores(fit, dev)))
+    if frechet:
+        res.update(ev.tag(ev.frechet_scores(dev)))
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
         ev.set_fixed_data(dev[0])

@@ -652,6 +652,62 @@ def lsq_probe_predict(fit, z, y=None, return_pred=False):
     return (correct, pred) if return_pred else correct
 
 
+FRECHET_MAX_DIM, FRECHET_MAX_ROWS = 128, 131072             # include/ggan.h: GGAN_FRECHET_MAX_DIM, the row range
+FRECHET_NONFINITE, FRECHET_NOT_CONVERGED = 1, 2             # ... and the bits of the status word
+
+
+def _frechet_rows(name, x):
+    """float32 rows [2 <= rows <= FRECHET_MAX_ROWS, 1 <= d <= FRECHET_MAX_DIM] (ValueError otherwise), no gradient"""
+    if x.dim() != 2 or x.dtype != torch.float32 or x.shape[0] > FRECHET_MAX_ROWS:
+        raise ValueError('%s: float32 rows [rows <= %d, d] expected, got %s %s' % (name, FRECHET_MAX_ROWS, x.dtype, tuple(x.shape)))
+    if x.shape[0] < 2:
+        raise ValueError('%s: at least 2 rows expected, got %d' % (name, x.shape[0]))
+    if not 1 <= x.shape[1] <= FRECHET_MAX_DIM:
+        raise ValueError('%s: 1 <= d <= %d columns expected, got %d' % (name, FRECHET_MAX_DIM, x.shape[1]))
+    _no_grad(name, [x])
+
+
+def _frechet_moments(name, x):
+    """(mean, cov, status) of checked rows, made contiguous on the device"""
+    x = _c(x)
+    n, d = x.shape
+    mean = torch.empty((d,), dtype=torch.float64, device=x.device)
+    cov = torch.empty((d, d), dtype=torch.float64, device=x.device)
+    status = torch.empty((1,), dtype=torch.int32, device=x.device)
+    ws, nbytes = _workspace(_L().ggan_frechet_moments_workspace(n, d), x.device)
+    check(_L().ggan_frechet_moments(_p(x), n, d, _p(mean), _p(cov), _p(status), _p(ws), nbytes, _stream()), 'ggan_frechet_moments')
+    return mean, cov, status
+
+
+def frechet_moments(x):
+    """(mean float64 [d], covariance float64 [d, d] over n - 1) of the rows x float32 [n, d] (ggan_frechet_moments): the mean from fp64 sums,
+    the covariance from rows centred by that mean, a block of 256 rows summed in fp32, the blocks in fp64; kept in fp64.  2 <= n <= 131072,
+    d <= FRECHET_MAX_DIM.  Device tensors, nothing is read back; a non-finite entry shows as a non-finite moment.  Forward only."""
+    _frechet_rows('frechet_moments', x)
+    mean, cov, _ = _frechet_moments('frechet_moments', x)
+    return mean, cov
+
+
+def frechet_distance(x, y):
+    """the Frechet distance between Gaussians fitted to the row sets x [m, d] and y [n, d] (float32, one width d <= FRECHET_MAX_DIM, at least
+    two rows each): |mu_x - mu_y|^2 + tr S_x + tr S_y - 2 tr (S_x S_y)^(1/2) (ggan_frechet_moments, ggan_frechet_distance: all fp64 behind
+    the moments, singular covariances allowed) -> (values float64 [4] = [the distance, |dmu|^2, tr S_x + tr S_y, 2 tr (S_x S_y)^(1/2)],
+    status int32 [1]: 0, or FRECHET_NONFINITE | FRECHET_NOT_CONVERGED).  The distance is not clipped at 0: two samples of one distribution
+    may land a hair below.  Device tensors, no host synchronisation.  Forward only."""
+    name = 'frechet_distance'
+    _row_shapes(name, [x, y])
+    _frechet_rows(name, x)
+    _frechet_rows(name, y)
+    m1, c1, s1 = _frechet_moments(name, x)
+    m2, c2, s2 = _frechet_moments(name, y)
+    d = x.shape[1]
+    out = torch.empty((4,), dtype=torch.float64, device=m1.device)
+    status = torch.empty((1,), dtype=torch.int32, device=m1.device)
+    ws, nbytes = _workspace(_L().ggan_frechet_distance_workspace(d), m1.device)
+    check(_L().ggan_frechet_distance(_p(m1), _p(c1), _p(m2), _p(c2), d, _p(out), _p(status), _p(ws), nbytes, _stream()), 'ggan_frechet_distance')
+    return out, status | s1 | s2
+
+
 class Reparam(Function):
     """(z, std) = (mean + eps * exp(log_std), exp(log_std)): the stochastic encoder head (gan_inference_cifar10.py:173-188)"""
 

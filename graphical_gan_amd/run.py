@@ -190,6 +190,22 @@ def probe_sets(S):
         np.random.set_state(state)
 
 
+# the Frechet distance of codes and of projected images (evaluate.Evaluator.frechet_scores) is a pass of its own too: it draws its noise from
+# a state of its own, so that switching it on moves no other logged number.  Off unless asked for
+def frechet_settings(script):
+    """{'FRECHET_EVERY': N} for the eight image scripts when $GGAN_FRECHET_EVERY = N is set, {} otherwise and for every other script (the
+    state-space scripts have no single code to compare)"""
+    name = os.path.splitext(os.path.basename(script))[0]
+    n = os.environ.get('GGAN_FRECHET_EVERY')
+    return {'FRECHET_EVERY': int(n)} if n and name in _IMAGE_SCRIPTS else {}
+
+
+def frechet_due(S, it):
+    """does the Frechet pass fire after iteration `it`: it % N == N - 1, the cadence of the other passes"""
+    n = int(S.get('FRECHET_EVERY') or 0)
+    return bool(n and it % n == n - 1)
+
+
 # an exponential moving average of the generator-side weights (engine.Trainer's ema_decay), kept on the device inside the steps and used by
 # the passes only: off unless asked for; which weights the passes score is a second switch
 EMA_EVAL_MODES = ('live', 'ema', 'both')
@@ -498,8 +514,13 @@ def train(S, cfg, model=None, out_dir=None):
     elif probe and not (labelled(the_sets()[0]) and the_fit()):
         print('[run] dev probe accuracy skipped: no labelled dev set and training split (%s data)' % source)
         probe = False
-    ev = the_eval() if plan or manifold or on or probe else None
-    ev_dev, ev_test = the_sets() if plan or manifold or probe or (on and not sequences) else (None, None)
+    # the Frechet distance of codes and of projected images: no labels needed, so every image script's data will do
+    frechet = bool(S.get('FRECHET_EVERY')) and lead
+    if frechet and sequences:
+        print('[run] dev frechet skipped: the state-space models have no single code to compare')
+        frechet = False
+    ev = the_eval() if plan or manifold or on or probe or frechet else None
+    ev_dev, ev_test = the_sets() if plan or manifold or probe or frechet or (on and not sequences) else (None, None)
     flush = lambda: lib.plot.flush(out_dir, os.path.join(out_dir, 'logfile.txt') if out_dir else None)
     eval_ms = 0.0            # wall time of the evaluation passes (kept out of `time`)
     for it in range(S['ITERS']):
@@ -540,6 +561,11 @@ def train(S, cfg, model=None, out_dir=None):
             for w in passes:
                 with _on_weights(ev, w):
                     eval_ms += _timed(device, lambda: _plot(ev.tag(ev.probe_scores(the_fit(), ev_dev))))
+            flush()
+        if frechet and frechet_due(S, it):
+            for w in passes:
+                with _on_weights(ev, w):
+                    eval_ms += _timed(device, lambda: _plot(ev.tag(ev.frechet_scores(ev_dev))))
             flush()
         lib.plot.tick()
         if out_dir and S.get('SAVE_EVERY') and (it + 1) % S['SAVE_EVERY'] == 0:

@@ -545,6 +545,36 @@ int ggan_probe_solve(const float* G, const float* R, const int32_t* counts, int 
 int ggan_probe_predict(const float* Z, const int32_t* y, int m, int d, int classes, const float* mean, const float* inv_std,
                        const float* W, const float* bias, int32_t* pred, int32_t* correct, ggan_stream_t stream);
 
+/* Frechet distance between Gaussians fitted to two row sets, |mu1 - mu2|^2 + tr S1 + tr S2 - 2 tr (S1 S2)^(1/2) -- the "FD" of FID
+ * (evaluate.Evaluator.frechet_scores, functional.frechet_moments / frechet_distance).  It stands in for the one number about samples the
+ * reference publishes, tflib/inception_score.py (which needs a download), on the sets the reference draws as pictures in
+ * gan_inference_cifar10.py:381-391; the features are the codes, or a fixed random projection of the pixels, not Inception's.
+ *   ggan_frechet_moments:  mean[d] and cov[d,d] (divisor n - 1) of the device fp32 rows X[n,d], 2 <= n <= 131072, 1 <= d <=
+ *                          GGAN_FRECHET_MAX_DIM, both in fp64.  The mean from fp64 sums per block of GGAN_PROBE_ROW_BLOCK rows, added in block
+ *                          order; the covariance from rows centred by that fp64 mean (never E[x^2] - mean^2): a block's products are summed
+ *                          in fp32 in row order (v_mfma_f32_32x32x2_f32, d padded to a multiple of 32; instance t = ceil(d / 32)), the block
+ *                          partials in fp64 in block order, and the result is NOT rounded to fp32.  status[0] is WRITTEN:
+ *                          GGAN_FRECHET_NONFINITE if a mean or an entry is not finite, else 0.
+ *   ggan_frechet_distance: out[4] = { fd, |mu1 - mu2|^2, tr S1 + tr S2, 2 tr (S1 S2)^(1/2) } from device fp64 moments, in one workgroup, all
+ *                          fp64: a diagonally pivoted Cholesky factorisation of S1 that tolerates a semi-definite matrix (once the largest
+ *                          remaining pivot is at or below d eps tr S1 the remaining columns are zero), M = L^T S2 L, the eigenvalues of M by
+ *                          two-sided Jacobi rotations in round-robin ordering, sum sqrt(max(lambda, 0)).  fd is NOT clipped at 0.  status[0]
+ *                          is WRITTEN: GGAN_FRECHET_NONFINITE for a non-finite input (out is then NaN), GGAN_FRECHET_NOT_CONVERGED if the
+ *                          off-diagonal norm of M is above 1e-14 of its Frobenius norm at the start after the fixed cap of sweeps, else 0.
+ * ws: ggan_frechet_*_workspace(...) bytes of 16-byte aligned device scratch (0 = arguments out of range).  No floating-point atomics,
+ * every sum in a fixed order: repeated calls give the same bits.  Arguments out of range, a null pointer or a short workspace return a
+ * negative code before any device work.
+ * Forward only.  Added without a version change: no existing entry point or struct is touched. */
+#define GGAN_FRECHET_MAX_DIM 128
+#define GGAN_FRECHET_NONFINITE 1
+#define GGAN_FRECHET_NOT_CONVERGED 2
+size_t ggan_frechet_moments_workspace(int n, int d);
+int ggan_frechet_moments(const float* X, int n, int d, double* mean, double* cov, int32_t* status, void* ws, size_t ws_bytes,
+                         ggan_stream_t stream);
+size_t ggan_frechet_distance_workspace(int d);
+int ggan_frechet_distance(const double* mean1, const double* cov1, const double* mean2, const double* cov2, int d, double* out,
+                          int32_t* status, void* ws, size_t ws_bytes, ggan_stream_t stream);
+
 /* Stochastic encoder head, TYPE_Q = 'learn_std' (gan_inference_cifar10.py:173-188): std = exp(log_std), z = mean + eps * std; the backward
  * takes the gradients arriving at z and at std (either may be NULL). */
 int ggan_reparam_fwd(const float* mean, const float* log_std, const float* eps, float* z, float* std_out, size_t n, ggan_stream_t stream);
