@@ -98,6 +98,8 @@ SIGNATURES = {
     'ggan_frechet_moments': (_I, [_P, _I, _I, _P, _P, _P, _P, _Z, _P]),
     'ggan_frechet_distance_workspace': (_Z, [_I]),
     'ggan_frechet_distance': (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _Z, _P]),
+    'ggan_swd_workspace': (_Z, [_I, _I, _I]),
+    'ggan_swd': (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _Z, _P]),
     'ggan_noise_fill': (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _P]),
     'ggan_gmm_latent_fwd': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _P]),
     'ggan_gmm_latent_bwd': (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P]),

@@ -39,6 +39,13 @@
                      random projection to FRECHET_PROJ_DIM columns (xr); the `mean` rows are the |dmu|^2 part.  A pass of its own with a
                      noise state of its own, no labels needed.  It stands in for tflib/inception_score.py, which needs a download; the
                      features are not Inception's, so no value is comparable with a published FID.
+  swd_scores         `dev swd z` / `dev swd max z` / `dev swd x` / `dev swd max x`: the sliced Wasserstein distance -- both sets projected onto
+                     SWD_DIRS fixed random unit directions, per direction W_p^p between the two sorted columns, the p-th root of the mean
+                     over the directions and (`max`) of the largest, functional.sliced_wasserstein_projected -- of q_z against as many
+                     prior draws (z) and of the dev images against as many generated ones in the FULL pixel space (x: 784 / 3072 / 12288
+                     columns, pixels in [0, 1]).  No kernel width, no Gaussian fit, no column cap.  A pass of its own with a noise state
+                     of its own, no labels needed.  It too stands in for tflib/inception_score.py; a Monte-Carlo estimate over the
+                     drawn directions, in pixel space, so no value is comparable with a published SWD.
 
 The passes are safe in the middle of training: they run under torch.no_grad() on the current stream only (no second stream, no
 collective), with a feed dict and a noise generator state of their own -- the Trainer's static feed buffers, ring slots and noise state
@@ -58,7 +65,7 @@ run by SequenceEvaluator on a models_ssgan.StateSpaceGAN under the same rules:
 Each is written as a .png sheet (one sequence per row) and a looping .gif; the bytes of both come from one ggan_video_sheet_u8 launch.
 
 `python -m graphical_gan_amd.evaluate CKPT --script gmgan_inference_mnist [--data-dir DIR]` scores a saved checkpoint
-(`--out-dir DIR --manifold` also writes the latent-space pictures of the two MNIST scripts, `--mmd` adds the two MMD^2 rows, `--prdc` the eight precision / recall / density / coverage rows, `--knn` the two k-NN accuracy rows, `--parzen` the three Parzen-window rows, `--rec` the four reconstruction rows, `--probe` the three linear-probe rows, `--frechet` the four Frechet-distance rows);
+(`--out-dir DIR --manifold` also writes the latent-space pictures of the two MNIST scripts, `--mmd` adds the two MMD^2 rows, `--prdc` the eight precision / recall / density / coverage rows, `--knn` the two k-NN accuracy rows, `--parzen` the three Parzen-window rows, `--rec` the four reconstruction rows, `--probe` the three linear-probe rows, `--frechet` the four Frechet-distance rows, `--swd` the four sliced-Wasserstein rows);
 `... CKPT --script ssgan_inference_moving_mnist|ssgan_inference_chairs [--data-dir DIR] --out-dir DIR` writes the four pairs of files;
 `--rec` prints the four reconstruction rows of the sequences' frames, and alone needs no --out-dir.
 
@@ -97,6 +104,11 @@ FRECHET_MAX_ROWS = 10000  # rows per set of the frechet_scores pass (settings: F
 FRECHET_PROJ_DIM = 128    # columns of its fixed random projection of the pixels: functional.FRECHET_MAX_DIM, whatever DIM_LATENT is
 FRECHET_SEED = 130003     # offset of its own noise state, and of its projection matrix, from the evaluator's seed
 FRECHET_KEYS = ('dev frechet z', 'dev frechet mean z', 'dev frechet xr', 'dev frechet mean xr')
+SWD_MAX_ROWS = 10000      # rows per set of the swd_scores pass (settings: SWD_MAX_ROWS)
+SWD_DIRS = 512            # its random unit directions, drawn once per evaluator (settings: SWD_DIRS)
+SWD_P = 2                 # its exponent, 1 or 2 (settings: SWD_P)
+SWD_SEED = 155317         # offset of its own noise state, and of its direction matrices, from the evaluator's seed
+SWD_KEYS = ('dev swd z', 'dev swd max z', 'dev swd x', 'dev swd max x')
 EVAL_SEED = 7919          # offset of the evaluator's noise seeds from the settings seed (the Trainer's stream of draws is not touched)
 
 # the reference's output file names, per script: (samples, reconstructions), formatted with frame= and mode=
@@ -743,6 +755,93 @@ class Evaluator(_Passes):
         res = {k: (float('nan') if status[i // 2] else float(host[i])) for i, k in enumerate(FRECHET_KEYS)}
         return (res, sets) if return_sets else res
 
+    _swd_rng = _swd_thetas = None             # the sliced-Wasserstein pass's own noise state and direction matrices, made by its first call
+
+    def _swd_directions(self, L):
+        """(theta_z [DIM_LATENT, L], theta_x [OUTPUT_DIM, L]): random unit directions, RandomState(seed).normal -- the latent matrix first,
+        then the pixel matrix --, every column normalised in float64 and then cast to float32; drawn once per evaluator"""
+        if self._swd_thetas is None or self._swd_thetas[0].shape[1] != L:
+            rng = np.random.RandomState(int(self.S.get('SEED', 0)) + EVAL_SEED + SWD_SEED)
+            made = []
+            for d in (self.cfg.dim_latent, self.cfg.output_dim):
+                t = rng.normal(size=(d, L))
+                t /= np.sqrt(np.sum(t * t, axis=0, keepdims=True))
+                made.append(torch.as_tensor(t.astype(np.float32)).to(self.device))
+            self._swd_thetas = tuple(made)
+        return self._swd_thetas
+
+    def _swd_sets(self, batches, rows, L):
+        """z = q_z, pz = as many fresh prior draws, real and generated images built exactly as _frechet_sets builds them, over the full
+        minibatches, at most `rows` rows per set -- each minibatch projected at once onto its directions into its rows of a [rows, L]
+        buffer: the pass holds four [rows, L] arrays whatever OUTPUT_DIM is, and the images do not stay.  Called inside the pass's guard,
+        under its own noise state."""
+        c = self.cfg
+        X, _ = self._stage(batches)
+        B = c.B
+        n = min(X.shape[0], max(1, int(rows) // B))
+        theta_z, theta_x = self._swd_directions(L)
+        new = lambda: torch.empty((n * B, L), dtype=torch.float32, device=self.device)
+        sets = dict(z_proj=new(), pz_proj=new(), x_proj=new(), gx_proj=new(), theta_z=theta_z, theta_x=theta_x)
+        lo = 0.0 if c.out_act == 'sigmoid' else -1.0                      # (as _to_unit)
+
+        def pixels(x):
+            x = x.float().reshape(B, -1).contiguous()
+            if lo:
+                x = F.Axpby.apply(x, None, 1.0 / (1.0 - lo), 0.0, -lo / (1.0 - lo))
+            return F.Gemm.apply(x, theta_x, None, False, False, F.ACT_NONE, 0.0)
+        codes = lambda z: F.Gemm.apply(z.float().contiguous(), theta_z, None, False, False, F.ACT_NONE, 0.0)
+        self.kept = []
+        for i in range(n):
+            at = slice(i * B, (i + 1) * B)
+            self._load(X[i])
+            real_x = self.model.real_x(self.feed)
+            q = self.model.Extractor(real_x, eps=self.feed['q_eps']) if c.agg else self.model.Extractor(real_x)
+            sets['z_proj'][at].copy_(codes(q[0] if isinstance(q, tuple) else q))
+            sets['x_proj'][at].copy_(pixels(real_x))
+            p_z = self.model.HyperGenerator(self.feed['k_onehot'], self.feed['p_z_noise']) if c.K else self.feed['p_z_noise']
+            sets['pz_proj'][at].copy_(codes(p_z))
+            sets['gx_proj'][at].copy_(pixels(self.model.Generator(p_z.contiguous())))
+        return sets
+
+    def swd_scores(self, batches, return_sets=False):
+        """{'dev swd z', 'dev swd max z', 'dev swd x', 'dev swd max x'}: the sliced Wasserstein distance (functional.
+        sliced_wasserstein_projected: per direction W_p^p between the two sorted columns, sorted on the device, fp64 behind the float32
+        projections) over SWD_DIRS fixed random unit directions, p = SWD_P -- z: q_z of the dev images against as many prior draws (through
+        HyperGenerator with a mixture prior), the sets of `dev mmd z`; x: the dev images against as many generated ones in the full pixel
+        space, pixels in [0, 1].  The first row of a pair is (the mean over the directions)^(1/p), the `max` row (the largest)^(1/p), a lower
+        bound of the max-sliced distance: it shows whether the discrepancy sits in a few directions.  Over the full dev minibatches, at
+        most SWD_MAX_ROWS rows per set.  The pass draws from a noise state of its own, swapped into the feed while it runs: every other
+        pass logs the same values, and training reaches the same weights, whether it is on or not.  ONE host synchronisation; a raised
+        status word (a non-finite projection: a diverged model) gives nan for that pair of rows and one printed message, no exception.
+        A Monte-Carlo estimate over directions fixed per seed -- compare figures at equal directions and row counts --, in pixel space,
+        not comparable with any published SWD.
+        return_sets: (values, {z_proj, pz_proj, x_proj, gx_proj: the projected device rows [rows, L]; theta_z, theta_x: the directions})."""
+        S = self.S
+        rows, L, p = int(S.get('SWD_MAX_ROWS', SWD_MAX_ROWS)), int(S.get('SWD_DIRS', SWD_DIRS)), int(S.get('SWD_P', SWD_P))
+        if not 1 <= rows <= F.SWD_MAX_ROWS:
+            raise ValueError('SWD_MAX_ROWS = %d: 1 to %d rows per set' % (rows, F.SWD_MAX_ROWS))
+        if not 1 <= L <= F.SWD_MAX_DIRS:
+            raise ValueError('SWD_DIRS = %d: 1 to %d directions' % (L, F.SWD_MAX_DIRS))
+        if p not in (1, 2):
+            raise ValueError('SWD_P = %d: 1 or 2' % p)
+        with self._guard():
+            if self._swd_rng is None:
+                self._swd_rng = F.noise_state(self.device, int(S.get('SEED', 0)) + EVAL_SEED + SWD_SEED)
+            shared, self.feed['rng_state'] = self.feed['rng_state'], self._swd_rng
+            try:
+                sets = self._swd_sets(batches, rows, L)
+            finally:
+                self.feed['rng_state'] = shared
+            (vz, _, sz), (vx, _, sx) = (F.sliced_wasserstein_projected(sets['z_proj'], sets['pz_proj'], p),
+                                        F.sliced_wasserstein_projected(sets['x_proj'], sets['gx_proj'], p))
+            host = torch.cat([vz, vx, sz.double(), sx.double()]).cpu().numpy()
+        status = (int(host[4]), int(host[5]))
+        if any(status):
+            print('[evaluate] swd: status %d (z) / %d (x) -- %d: a non-finite projected value -- its values are nan'
+                  % (status[0], status[1], F.SWD_NONFINITE))
+        res = {k: (float('nan') if status[i // 2] else float(host[i])) for i, k in enumerate(SWD_KEYS)}
+        return (res, sets) if return_sets else res
+
     def manifold(self, batches, out_dir, frame):
         """embeds the point sets of latent_sets with functional.tsne and writes the scatters under the reference's file names; returns
         the paths: the four pictures of gmgan_inference_mnist with a mixture prior, the one of gan_inference_mnist without.  MNIST models
@@ -1036,6 +1135,7 @@ def main(argv=None):
         ap.add_argument('--' + row.name, action='store_true', help=row.help)
     ap.add_argument('--probe', action='store_true', help='also fit a least-squares linear probe on the codes of labelled training rows and score it on the labelled dev set (dev probe accuracy z / fit probe accuracy z / dev probe accuracy xr; image scripts with labelled data)')
     ap.add_argument('--frechet', action='store_true', help='also score the dev set by the Frechet distance between Gaussians fitted to q_z and prior draws, and to randomly projected dev and generated images (dev frechet z / xr and their mean parts; image scripts; not comparable with a published FID)')
+    ap.add_argument('--swd', action='store_true', help='also score the dev set by the sliced Wasserstein distance of q_z against prior draws and of the dev images against generated ones in the full pixel space, over fixed random unit directions (dev swd z / x and their max rows; image scripts; not comparable with a published SWD)')
     ap.add_argument('--ema', action='store_true', help="score the averaged generator-side weights the checkpoint holds (its ema/gen/ keys, written by a run with $GGAN_EMA_DECAY) instead of the last iterate: every name gets the suffix ' ema', every file '_ema'; the critic of 'dev gen cost ema' is the live one")
     ap.add_argument('--set', action='append', default=[], metavar='KEY=VALUE', help='override an UPPERCASE setting (int / float / str)')
     a = ap.parse_args(argv)
@@ -1059,6 +1159,8 @@ def main(argv=None):
             ap.error('--probe: %s' % _NO_CODE)
         if a.frechet:
             ap.error('--frechet: %s' % _NO_CODE)
+        if a.swd:
+            ap.error('--swd: %s' % _NO_CODE)
     if a.manifold:          # (checked before anything is built)
         name = os.path.splitext(os.path.basename(a.script))[0]
         if name not in MANIFOLD_SCRIPTS:
@@ -1086,17 +1188,17 @@ def main(argv=None):
         # the checkpoint's live ones), and the evaluators only name what they write
         tr.load_params(ema)
         tr.ema_loaded = True
-    res = evaluate_once(tr, S, out_dir=a.out_dir, manifold=a.manifold, probe=a.probe, frechet=a.frechet, **{row.name: getattr(a, row.name) for row in SET_SCORES})
+    res = evaluate_once(tr, S, out_dir=a.out_dir, manifold=a.manifold, probe=a.probe, frechet=a.frechet, swd=a.swd, **{row.name: getattr(a, row.name) for row in SET_SCORES})
     for k in sorted(res):
         print('%s\t%s' % (k, res[k]))
     return res
 
 
-def evaluate_once(tr, S, out_dir=None, frame='eval', manifold=False, probe=False, frechet=False, **scores):
+def evaluate_once(tr, S, out_dir=None, frame='eval', manifold=False, probe=False, frechet=False, swd=False, **scores):
     """every pass the script's data allow, once -> {name: value}; manifold: the latent-space pictures too (labelled dev data only);
     probe: the three values of Evaluator.probe_scores too, after the set-level scores (image scripts; skipped with one message where the
     dev set or the training split has no labels); frechet: the four values of Evaluator.frechet_scores too, after those (image scripts; no
-    labels needed);
+    labels needed); swd: the four values of Evaluator.swd_scores too, after those (image scripts; no labels needed);
     scores: the set-level scores of SET_SCORES to add, by name (mmd=True, ...: Evaluator.set_scores' keywords, one build of the sets for all
     of them; a score that needs labels is skipped on unlabelled dev data); a trainer whose weights are averaged ones loaded from a
     checkpoint (tr.ema_loaded, main --ema): names and files carry the suffixes.  The state-space scripts: the video files (with out_dir)
@@ -1109,6 +1211,8 @@ def evaluate_once(tr, S, out_dir=None, frame='eval', manifold=False, probe=False
             raise ValueError('probe: %s' % _NO_CODE)
         if frechet:
             raise ValueError('frechet: %s' % _NO_CODE)
+        if swd:
+            raise ValueError('swd: %s' % _NO_CODE)
         ev = SequenceEvaluator(tr, S)
         ev.weights = 'ema' if ema_names else 'live'
         dev, _ = run.eval_sets(S, tr.model, tr.device)
@@ -1140,6 +1244,8 @@ def evaluate_once(tr, S, out_dir=None, frame='eval', manifold=False, probe=False
             res.update(ev.tag(ev.probe_scores(fit, dev)))
     if frechet:
         res.update(ev.tag(ev.frechet_scores(dev)))
+    if swd:
+        res.update(ev.tag(ev.swd_scores(dev)))
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
         ev.set_fixed_data(dev[0])

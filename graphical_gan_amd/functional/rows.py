@@ -708,6 +708,79 @@ def frechet_distance(x, y):
     return out, status | s1 | s2
 
 
+SWD_MAX_ROWS, SWD_MAX_DIRS = 16384, 4096                   # include/ggan.h: GGAN_SWD_MAX_ROWS, GGAN_SWD_MAX_DIRS
+SWD_NONFINITE = 1                                           # ... and the status word
+
+
+def _swd_rows(name, x, what='d'):
+    """float32 rows [1 <= rows <= SWD_MAX_ROWS, 1 <= columns] (ValueError otherwise)"""
+    if x.dim() != 2 or x.dtype != torch.float32 or x.shape[0] > SWD_MAX_ROWS:
+        raise ValueError('%s: float32 rows [rows <= %d, %s] expected, got %s %s' % (name, SWD_MAX_ROWS, what, x.dtype, tuple(x.shape)))
+    if x.shape[0] < 1:
+        raise ValueError('%s: at least 1 row expected, got %d' % (name, x.shape[0]))
+    if x.shape[1] < 1:
+        raise ValueError('%s: at least 1 column expected, got %d' % (name, x.shape[1]))
+
+
+def _swd_p(name, p):
+    if p not in (1, 2):
+        raise ValueError('%s: p must be 1 or 2, got %s' % (name, p))
+    return int(p)
+
+
+def _swd_dirs(name, L):
+    if not 1 <= L <= SWD_MAX_DIRS:
+        raise ValueError('%s: 1 <= L <= %d directions expected, got %d' % (name, SWD_MAX_DIRS, L))
+
+
+def sliced_wasserstein_projected(px, py, p=2):
+    """the sliced Wasserstein distance of two row sets already projected onto L directions, px float32 [m, L] and py float32 [n, L] (one
+    width 1 <= L <= SWD_MAX_DIRS, 1 <= m, n <= SWD_MAX_ROWS, p 1 or 2; ggan_swd): per direction W_p^p between the empirical measures of the
+    two columns -- both sorted on the device, the quantile integral with integer weights in fp64 -> (values float64 [2] = [(mean_l
+    per_l)^(1/p), (max_l per_l)^(1/p)], per float64 [L], status int32 [1]: 0, or SWD_NONFINITE when a value of either set is NaN or
+    +-inf; values and per are then NaN).  The result depends on the multiset of each column only: permuted rows give the same bits.  Device
+    tensors, no host synchronisation.  Forward only."""
+    name = 'sliced_wasserstein_projected'
+    _row_shapes(name, [px, py])
+    _swd_rows(name, px, 'L')
+    _swd_rows(name, py, 'L')
+    _swd_dirs(name, px.shape[1])
+    p = _swd_p(name, p)
+    _no_grad(name, [px, py])
+    same = px is py
+    px = _c(px)
+    py = px if same else _c(py)
+    (m, L), n = px.shape, py.shape[0]
+    dev = px.device
+    per = torch.empty((L,), dtype=torch.float64, device=dev)
+    out = torch.empty((2,), dtype=torch.float64, device=dev)
+    status = torch.empty((1,), dtype=torch.int32, device=dev)
+    ws, nbytes = _workspace(_L().ggan_swd_workspace(m, n, L), dev)
+    check(_L().ggan_swd(_p(px), _p(py), m, n, L, p, _p(per), _p(out), _p(status), _p(ws), nbytes, _stream()), 'ggan_swd')
+    return out, per, status
+
+
+def sliced_wasserstein(x, y, theta, p=2):
+    """the sliced Wasserstein distance of the row sets x float32 [m, d] and y float32 [n, d] over the directions theta float32 [d, L], used
+    as given (normalising the columns is the caller's business): both sets through linear.Gemm onto the directions, then
+    sliced_wasserstein_projected -> (values float64 [2], per float64 [L], status int32 [1]).  No column cap: d is the full pixel space
+    if the caller wants it.  Device tensors, no host synchronisation.  Forward only."""
+    name = 'sliced_wasserstein'
+    _row_shapes(name, [x, y])
+    _swd_rows(name, x)
+    _swd_rows(name, y)
+    if theta.dim() != 2 or theta.dtype != torch.float32 or theta.shape[0] != x.shape[1]:
+        raise ValueError('%s: float32 directions [%d, L] expected, got %s %s' % (name, x.shape[1], theta.dtype, tuple(theta.shape)))
+    _swd_dirs(name, theta.shape[1])
+    p = _swd_p(name, p)
+    _no_grad(name, [x, y, theta])
+    same = x is y
+    theta = _c(theta)
+    px = Gemm.apply(_c(x), theta, None, False, False, _lib.ACT_NONE, 0.0)
+    py = px if same else Gemm.apply(_c(y), theta, None, False, False, _lib.ACT_NONE, 0.0)
+    return sliced_wasserstein_projected(px, py, p)
+
+
 class Reparam(Function):
     """(z, std) = (mean + eps * exp(log_std), exp(log_std)): the stochastic encoder head (gan_inference_cifar10.py:173-188)"""
 

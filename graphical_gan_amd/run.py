@@ -206,6 +206,22 @@ def frechet_due(S, it):
     return bool(n and it % n == n - 1)
 
 
+# the sliced Wasserstein distance of codes and of images in the full pixel space (evaluate.Evaluator.swd_scores): a pass of its own as well,
+# with a noise state of its own.  Off unless asked for
+def swd_settings(script):
+    """{'SWD_EVERY': N} for the eight image scripts when $GGAN_SWD_EVERY = N is set, {} otherwise and for every other script (the state-space
+    scripts have no single code to compare; a frames-in-pixel-space twin needs fresh-noise sequence sets)"""
+    name = os.path.splitext(os.path.basename(script))[0]
+    n = os.environ.get('GGAN_SWD_EVERY')
+    return {'SWD_EVERY': int(n)} if n and name in _IMAGE_SCRIPTS else {}
+
+
+def swd_due(S, it):
+    """does the sliced-Wasserstein pass fire after iteration `it`: it % N == N - 1, the cadence of the other passes"""
+    n = int(S.get('SWD_EVERY') or 0)
+    return bool(n and it % n == n - 1)
+
+
 # an exponential moving average of the generator-side weights (engine.Trainer's ema_decay), kept on the device inside the steps and used by
 # the passes only: off unless asked for; which weights the passes score is a second switch
 EMA_EVAL_MODES = ('live', 'ema', 'both')
@@ -519,8 +535,13 @@ def train(S, cfg, model=None, out_dir=None):
     if frechet and sequences:
         print('[run] dev frechet skipped: the state-space models have no single code to compare')
         frechet = False
-    ev = the_eval() if plan or manifold or on or probe or frechet else None
-    ev_dev, ev_test = the_sets() if plan or manifold or probe or frechet or (on and not sequences) else (None, None)
+    # the sliced Wasserstein distance of codes and of images: no labels needed either
+    swd = bool(S.get('SWD_EVERY')) and lead
+    if swd and sequences:
+        print('[run] dev swd skipped: the state-space models have no single code to compare')
+        swd = False
+    ev = the_eval() if plan or manifold or on or probe or frechet or swd else None
+    ev_dev, ev_test = the_sets() if plan or manifold or probe or frechet or swd or (on and not sequences) else (None, None)
     flush = lambda: lib.plot.flush(out_dir, os.path.join(out_dir, 'logfile.txt') if out_dir else None)
     eval_ms = 0.0            # wall time of the evaluation passes (kept out of `time`)
     for it in range(S['ITERS']):
@@ -566,6 +587,11 @@ def train(S, cfg, model=None, out_dir=None):
             for w in passes:
                 with _on_weights(ev, w):
                     eval_ms += _timed(device, lambda: _plot(ev.tag(ev.frechet_scores(ev_dev))))
+            flush()
+        if swd and swd_due(S, it):
+            for w in passes:
+                with _on_weights(ev, w):
+                    eval_ms += _timed(device, lambda: _plot(ev.tag(ev.swd_scores(ev_dev))))
             flush()
         lib.plot.tick()
         if out_dir and S.get('SAVE_EVERY') and (it + 1) % S['SAVE_EVERY'] == 0:

@@ -575,6 +575,31 @@ size_t ggan_frechet_distance_workspace(int d);
 int ggan_frechet_distance(const double* mean1, const double* cov1, const double* mean2, const double* cov2, int d, double* out,
                           int32_t* status, void* ws, size_t ws_bytes, ggan_stream_t stream);
 
+/* Sliced Wasserstein distance between two row sets, already projected onto L directions: PX[m,L] and PY[n,L] (device fp32, row-major;
+ * direction l is column l, stride L; no alignment is assumed and L need be no multiple of anything), 1 <= m, n <= GGAN_SWD_MAX_ROWS,
+ * 1 <= L <= GGAN_SWD_MAX_DIRS, p = 1 or 2 (evaluate.Evaluator.swd_scores, functional.sliced_wasserstein_projected / sliced_wasserstein).
+ * Like the Frechet entries it stands in for the one number about samples the reference publishes, tflib/inception_score.py (which needs a
+ * download): it compares the whole distributions in the full pixel space, with no kernel width, no Gaussian fit and no column cap.
+ *   per[L]  (fp64) W_p^p(l) = the integral over t in (0, 1) of |F_a^-1(t) - F_b^-1(t)|^p between the empirical measures of column l of PX
+ *           (mass 1/m a point) and of PY (mass 1/n a point): both columns sorted by a bitonic network in LDS (padded with +inf to a power of
+ *           two), then, with point i of a owning [i n, (i+1) n) and point j of b owning [j m, (j+1) m) in units of 1/(m n), the sum over the
+ *           overlapping pairs of (the integer overlap) |a_i - b_j|^p, over m n.  Equal sizes give mean_i |a_i - b_i|^p.  The differences of
+ *           fp32 keys are exact in fp64; power, weights and sums are fp64, summed in an order fixed by sorted position.
+ *   out[2]  (fp64) { (mean_l per[l])^(1/p), (max_l per[l])^(1/p) }: the sliced distance, and the largest distance over the given directions
+ *           (a lower bound of the max-sliced distance).
+ *   status[0] is WRITTEN: GGAN_SWD_NONFINITE if a value of PX or PY is NaN or +-inf -- per and out are then NaN, never a fault --, else 0.
+ * ws: ggan_swd_workspace(m, n, L) bytes of 16-byte aligned device scratch, 4 L (m + n) rounded up (the transposed columns; 0 = arguments
+ * out of range).  No floating-point atomics: the result depends on the multiset of each column only -- rows of PX or of PY permuted give the
+ * same bits, as do repeated calls.  Arguments out of range, a null pointer, a misaligned fp64 output or a short or misaligned workspace
+ * return a negative code before any device work.
+ * Forward only.  Added without a version change: no existing entry point or struct is touched. */
+#define GGAN_SWD_MAX_ROWS 16384
+#define GGAN_SWD_MAX_DIRS 4096
+#define GGAN_SWD_NONFINITE 1
+size_t ggan_swd_workspace(int m, int n, int L);
+int ggan_swd(const float* PX, const float* PY, int m, int n, int L, int p, double* per, double* out, int32_t* status, void* ws,
+             size_t ws_bytes, ggan_stream_t stream);
+
 /* Stochastic encoder head, TYPE_Q = 'learn_std' (gan_inference_cifar10.py:173-188): std = exp(log_std), z = mean + eps * std; the backward
  * takes the gradients arriving at z and at std (either may be NULL). */
 int ggan_reparam_fwd(const float* mean, const float* log_std, const float* eps, float* z, float* std_out, size_t n, ggan_stream_t stream);
