@@ -323,11 +323,11 @@ int ggan_row_lerp(const float* x, const float* y, const float* alpha, float* out
     GGAN_CHECK_ARG(x && y && alpha && out && rows > 0 && cols > 0, "bad argument");
     size_t n = (size_t)rows * cols;
     if ((double)n * cols < 4.0e9) {
-        GGAN_LAUNCH("row_lerp", 0, 12.0 * n, row_lerp32_k, dim3(grid_for(n)), dim3(kBlock), 0, (hipStream_t)stream, x, y, alpha, out, (unsigned)n, cols,
+        GGAN_LAUNCH("row_lerp<32>", 0, 12.0 * n, row_lerp32_k, dim3(grid_for(n)), dim3(kBlock), 0, (hipStream_t)stream, x, y, alpha, out, (unsigned)n, cols,
                     make_fastdiv((uint32_t)cols));
         return 0;
     }
-    GGAN_LAUNCH("row_lerp", 0, 12.0 * n, row_lerp_k, dim3(grid_for(n)), dim3(kBlock), 0, (hipStream_t)stream, x, y, alpha, out, rows, cols);
+    GGAN_LAUNCH("row_lerp<64>", 0, 12.0 * n, row_lerp_k, dim3(grid_for(n)), dim3(kBlock), 0, (hipStream_t)stream, x, y, alpha, out, rows, cols);
     return 0;
 }
 
@@ -363,12 +363,12 @@ int ggan_chansum(const float* x, float* out, int N, int C, int HW, void* ws, siz
     if (!ws || (size_t)C * P * sizeof(float) > ws_bytes) P = 1;
     if (P <= 1) {
         const int threads = (size_t)N * HW >= 16384 ? 1024 : 256;
-        GGAN_LAUNCH("chansum", 0, 4.0 * N * C * HW, chansum_part_k, dim3(C, 1), dim3(threads), 0, s, x, out, N, C, HW, 1);
+        GGAN_LAUNCH("chansum<one>", 0, 4.0 * N * C * HW, chansum_part_k, dim3(C, 1), dim3(threads), 0, s, x, out, N, C, HW, 1);
         return 0;
     }
     const int threads = HW >= 1024 ? 256 : (HW >= 256 ? 128 : 64);
     float* part = (float*)ws;
-    GGAN_LAUNCH("chansum", 0, 4.0 * N * C * HW, chansum_part_k, dim3(C, P), dim3(threads), 0, s, x, part, N, C, HW, P);
+    GGAN_LAUNCH("chansum<part>", 0, 4.0 * N * C * HW, chansum_part_k, dim3(C, P), dim3(threads), 0, s, x, part, N, C, HW, P);
     GGAN_LAUNCH("chansum_final", 0, 4.0 * C * P, chansum_final_k, dim3(cdiv(C, 4)), dim3(256), 0, s, (const float*)part, out, C, P);
     return 0;
 }
