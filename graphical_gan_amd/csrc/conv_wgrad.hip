@@ -870,7 +870,8 @@ int conv_wgrad_mfma(const ggan_conv_geom& g, const float* x, const float* gy, Gy
     }
     const size_t xb = (size_t)g.N * g.Ci * g.H * g.W * 4, gb = (size_t)g.N * g.Co * g.Ho * g.Wo * 4;
     if (xb >= 0x7FFFFFF0ull || gb >= 0x7FFFFFF0ull) return 1;
-    if ((((uintptr_t)x) & 15) || (((uintptr_t)gy) & 15)) return 1;
+    // (the mask reference is fetched in the same 16-byte units as gy)
+    if ((((uintptr_t)x) & 15) || (((uintptr_t)gy) & 15) || (m.act != GGAN_ACT_NONE && (((uintptr_t)m.ref) & 15))) return 1;
     WgradParams P;
     memset(&P, 0, sizeof(P));
     P.x = x; P.gy = gy;

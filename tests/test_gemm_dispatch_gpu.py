@@ -49,11 +49,14 @@ def _host(values, ctype):
     return arr, C.cast(arr, C.c_void_p)
 
 
-def _dev(a, gpu, off=0):
-    """a float32 copy of `a` on the device, `off` floats into a NaN-filled buffer that ends 4 floats behind it"""
+def _dev(a, gpu, off=0, band=0):
+    """a float32 copy of `a` on the device, `off` floats into a NaN-filled buffer that ends 4 floats behind it; `band` (a multiple of
+    4) more NaN floats on each side"""
     import torch
     a = np.ascontiguousarray(a, dtype=np.float32)
-    buf = torch.full((off + a.size + 4,), float('nan'), dtype=torch.float32, device=gpu)
+    assert band % 4 == 0
+    buf = torch.full((band + off + a.size + 4 + band,), float('nan'), dtype=torch.float32, device=gpu)
+    off += band
     view = buf[off:off + a.size].view(a.shape)
     view.copy_(torch.from_numpy(a))
     assert view.data_ptr() % 16 == (4 * off) % 16

@@ -36,11 +36,13 @@ DB_ABS = 1.7e-5                # 3 x 5.5e-6, the worst |db| over the rows on MI3
 _GUARDS = []                   # (buffer, floats in front of the output, floats of the output) of every _out() of the running test
 
 
-def _out(shape, gpu, off=0):
-    """a NaN-filled float32 output, `off` floats into its buffer"""
+def _out(shape, gpu, off=0, band=0):
+    """a NaN-filled float32 output, `off` floats into its buffer; `band` (a multiple of 4) more NaN floats on each side"""
     import torch
     n = int(np.prod(shape))
-    buf = torch.full((off + n + 4,), float('nan'), dtype=torch.float32, device=gpu)
+    assert band % 4 == 0
+    buf = torch.full((band + off + n + 4 + band,), float('nan'), dtype=torch.float32, device=gpu)
+    off += band
     view = buf[off:off + n].view(shape)
     assert view.data_ptr() % 16 == (4 * off) % 16
     _GUARDS.append((buf, off, n))
