@@ -100,6 +100,10 @@ SIGNATURES = {
     'ggan_frechet_distance': (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _Z, _P]),
     'ggan_swd_workspace': (_Z, [_I, _I, _I]),
     'ggan_swd': (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _Z, _P]),
+    'ggan_softmax_xent_workspace': (_Z, [_I, _I]),
+    'ggan_softmax_xent_fwd_grad': (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
+    'ggan_class_score_workspace': (_Z, [_I, _I, _I]),
+    'ggan_class_score': (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _Z, _P]),
     'ggan_noise_fill': (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _P]),
     'ggan_gmm_latent_fwd': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _P]),
     'ggan_gmm_latent_bwd': (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P]),

@@ -46,6 +46,14 @@
                      columns, pixels in [0, 1]).  No kernel width, no Gaussian fit, no column cap.  A pass of its own with a noise state
                      of its own, no labels needed.  It too stands in for tflib/inception_score.py; a Monte-Carlo estimate over the
                      drawn directions, in pixel space, so no value is comparable with a published SWD.
+  classifier_scores  `dev classifier score x` / `dev classifier score std x` / `dev classifier score data` / `dev classifier accuracy` /
+                     `dev classifier frechet x`: the reference's own sample pass (gan_inference_cifar10.py:381-391,483-487: 50000 images
+                     from fresh prior noise, the inception-score formula of tflib/inception_score.py:47-53 over ten splits) under a
+                     classifier the run fits for itself on labelled training rows (classifier.ImageClassifier, functional.SoftmaxXent)
+                     in place of the downloaded Inception graph -- functional.class_score of its logits --, with the same score of the
+                     dev images, its accuracy on them, and the Frechet distance of its 128-wide features.  A pass of its own with a
+                     noise state of its own; labelled data only.  The name `inception score` is not logged: no value is comparable
+                     with a published inception score or FID, nor with a value under another classifier ($GGAN_CLS_CKPT shares one).
 
 The passes are safe in the middle of training: they run under torch.no_grad() on the current stream only (no second stream, no
 collective), with a feed dict and a noise generator state of their own -- the Trainer's static feed buffers, ring slots and noise state
@@ -65,7 +73,7 @@ run by SequenceEvaluator on a models_ssgan.StateSpaceGAN under the same rules:
 Each is written as a .png sheet (one sequence per row) and a looping .gif; the bytes of both come from one ggan_video_sheet_u8 launch.
 
 `python -m graphical_gan_amd.evaluate CKPT --script gmgan_inference_mnist [--data-dir DIR]` scores a saved checkpoint
-(`--out-dir DIR --manifold` also writes the latent-space pictures of the two MNIST scripts, `--mmd` adds the two MMD^2 rows, `--prdc` the eight precision / recall / density / coverage rows, `--knn` the two k-NN accuracy rows, `--parzen` the three Parzen-window rows, `--rec` the four reconstruction rows, `--probe` the three linear-probe rows, `--frechet` the four Frechet-distance rows, `--swd` the four sliced-Wasserstein rows);
+(`--out-dir DIR --manifold` also writes the latent-space pictures of the two MNIST scripts, `--mmd` adds the two MMD^2 rows, `--prdc` the eight precision / recall / density / coverage rows, `--knn` the two k-NN accuracy rows, `--parzen` the three Parzen-window rows, `--rec` the four reconstruction rows, `--probe` the three linear-probe rows, `--frechet` the four Frechet-distance rows, `--swd` the four sliced-Wasserstein rows, `--cls` the five classifier-score rows);
 `... CKPT --script ssgan_inference_moving_mnist|ssgan_inference_chairs [--data-dir DIR] --out-dir DIR` writes the four pairs of files;
 `--rec` prints the four reconstruction rows of the sequences' frames, and alone needs no --out-dir.
 
@@ -109,6 +117,13 @@ SWD_DIRS = 512            # its random unit directions, drawn once per evaluator
 SWD_P = 2                 # its exponent, 1 or 2 (settings: SWD_P)
 SWD_SEED = 155317         # offset of its own noise state, and of its direction matrices, from the evaluator's seed
 SWD_KEYS = ('dev swd z', 'dev swd max z', 'dev swd x', 'dev swd max x')
+CLS_SAMPLES = 50000       # generated rows the classifier_scores pass scores, floor(CLS_SAMPLES / B) minibatches: the reference's count (settings: CLS_SAMPLES)
+CLS_MAX_ROWS = 10000      # labelled dev rows it scores (settings: CLS_MAX_ROWS)
+CLS_SPLITS = 10           # splits of its score: the reference's (settings: CLS_SPLITS; at most functional.CLS_MAX_SPLITS)
+CLS_FIT_ROWS = 20000      # labelled training rows its classifier is fitted on (settings: CLS_FIT_ROWS)
+CLS_EPOCHS = 4            # passes over them (settings: CLS_EPOCHS)
+CLS_SEED = 179426         # offset of its own noise state, and of the classifier's initial values, from the evaluator's seed
+CLS_KEYS = ('dev classifier score x', 'dev classifier score std x', 'dev classifier score data', 'dev classifier accuracy', 'dev classifier frechet x')
 EVAL_SEED = 7919          # offset of the evaluator's noise seeds from the settings seed (the Trainer's stream of draws is not touched)
 
 # the reference's output file names, per script: (samples, reconstructions), formatted with frame= and mode=
@@ -842,6 +857,131 @@ class Evaluator(_Passes):
         res = {k: (float('nan') if status[i // 2] else float(host[i])) for i, k in enumerate(SWD_KEYS)}
         return (res, sets) if return_sets else res
 
+    _cls_rng = _cls = None                    # the classifier pass's own noise state and its fitted classifier, made by its first call
+    cls_fits = 0                              # how many times this evaluator fitted a classifier (a loaded file counts as none)
+
+    def _cls_rows(self, batches, rows):
+        """the leading full labelled minibatches, at most `rows` rows, as the classifier takes them: [(real_x float32 [B, OUTPUT_DIM], y int32
+        [B])] on the device (copies: real_x may be the feed buffer itself)"""
+        B = self.cfg.B
+        full = [b for b in batches if _split(b)[0].shape[0] == B]
+        if not full:
+            raise ValueError('no full minibatch of %d rows to evaluate on' % B)
+        n = min(len(full), max(1, int(rows) // B))
+        out = []
+        for s0 in range(0, n, max(1, PROBE_SLAB_ROWS // B)):
+            X, Y = self._stage(full[s0:min(n, s0 + max(1, PROBE_SLAB_ROWS // B))], want_labels=True)
+            for i in range(X.shape[0]):
+                self.model.set_batch(self.feed, X[i])
+                out.append((self.model.real_x(self.feed).float().reshape(B, -1).clone(), Y[i * B:(i + 1) * B]))
+        return out
+
+    def _classifier(self, fit_batches, classes):
+        """the evaluator's classifier: the first call loads $GGAN_CLS_CKPT if that file exists, else fits one on the leading CLS_FIT_ROWS
+        labelled training rows for CLS_EPOCHS epochs -> (classifier, fitted just now)"""
+        if self._cls is not None:
+            if self._cls.classes != classes:
+                raise ValueError('the classifier was made for %d classes, these minibatches have %d' % (self._cls.classes, classes))
+            return self._cls, False
+        from .classifier import ImageClassifier
+        S = self.S
+        cls = ImageClassifier(self.cfg, classes, int(S.get('SEED', 0)) + EVAL_SEED + CLS_SEED, device=self.device)
+        path = os.environ.get('GGAN_CLS_CKPT')
+        fitted = not (path and os.path.exists(path))
+        if fitted:
+            cls.fit(self._cls_rows(fit_batches, S.get('CLS_FIT_ROWS', CLS_FIT_ROWS)), int(S.get('CLS_EPOCHS', CLS_EPOCHS)))
+            self.cls_fits += 1
+        else:
+            cls.load(path)
+        self._cls = cls
+        return cls, fitted
+
+    def classifier_scores(self, fit_batches, dev_batches, return_sets=False):
+        """{'dev classifier score x', 'dev classifier score std x', 'dev classifier score data', 'dev classifier accuracy', 'dev classifier
+        frechet x'}: the reference's one number about its samples (gan_inference_cifar10.py:381-391,483-487: 50000 images from fresh prior
+        noise through a classifier, `inception score` and its std over ten splits, tflib/inception_score.py:47-53) under a classifier this
+        run fits for itself (classifier.ImageClassifier: the Extractor's conv stack without BatchNorm, fitted on the leading CLS_FIT_ROWS
+        labelled TRAINING rows for CLS_EPOCHS epochs) instead of the Inception graph the reference downloads.  score x / score std x:
+        functional.class_score of the logits of floor(CLS_SAMPLES / B) generated minibatches (through HyperGenerator with a mixture prior)
+        over CLS_SPLITS splits; score data: the same on at most CLS_MAX_ROWS labelled dev rows, the ceiling this classifier allows;
+        accuracy: its accuracy on those rows, how far to trust the others; frechet x: functional.frechet_distance of its 128-wide
+        features, the dev rows against as many generated rows.  Only logits and features stay on the device, never the images.
+        The first call makes the classifier and keeps it (with $GGAN_CLS_CKPT = path: loads that file if it exists, else writes the fitted
+        classifier there, so that two runs can be scored by ONE classifier -- figures under two classifiers do not compare); later calls,
+        and the other set of weights under EMA_EVAL = both, reuse it.  The pass draws from a noise state of its own, swapped into the feed
+        while it runs: every other pass logs the same values, and training reaches the same weights, whether it is on or not.  ONE host
+        synchronisation per pass (the call that fits also copies the weights out when it writes the file); a raised status word (a label out
+        of range, a non-finite logit or moment: a diverged model) gives nan and one printed message, no exception.  Not comparable with any
+        published inception score or FID.
+        return_sets: (values, {scores_x, scores_data: the per-split scores; entropies_x, entropies_data: (mean row entropy, entropy of the
+        marginal); logits_x, features_x, logits_data, features_data, labels: the device rows; classifier})."""
+        S, c = self.S, self.cfg
+        B = c.B
+        samples, rows, splits = int(S.get('CLS_SAMPLES', CLS_SAMPLES)), int(S.get('CLS_MAX_ROWS', CLS_MAX_ROWS)), int(S.get('CLS_SPLITS', CLS_SPLITS))
+        if not B <= samples <= F.CLS_SCORE_MAX_ROWS:
+            raise ValueError('CLS_SAMPLES = %d: one minibatch (%d) to %d rows' % (samples, B, F.CLS_SCORE_MAX_ROWS))
+        if not 2 <= rows <= min(F.CLS_MAX_BATCH, F.FRECHET_MAX_ROWS):
+            raise ValueError('CLS_MAX_ROWS = %d: 2 to %d rows' % (rows, min(F.CLS_MAX_BATCH, F.FRECHET_MAX_ROWS)))
+        if not 1 <= splits <= F.CLS_MAX_SPLITS:
+            raise ValueError('CLS_SPLITS = %d: 1 to %d splits' % (splits, F.CLS_MAX_SPLITS))
+        labels = [_split(b)[1] for b in list(fit_batches) + list(dev_batches)]
+        if not fit_batches or not dev_batches or any(y is None for y in labels):
+            raise ValueError('the classifier pass needs labelled minibatches on both sides')
+        classes = max(2, 1 + max(int(y.max()) for y in labels))      # (host labels: no device is asked)
+        if classes > F.CLS_MAX_CLASSES:
+            raise ValueError('the classifier takes at most %d classes, got %d' % (F.CLS_MAX_CLASSES, classes))
+        with self._guard():
+            if self._cls_rng is None:
+                self._cls_rng = F.noise_state(self.device, int(S.get('SEED', 0)) + EVAL_SEED + CLS_SEED)
+            shared, self.feed['rng_state'] = self.feed['rng_state'], self._cls_rng
+            try:
+                cls, fitted = self._classifier(fit_batches, classes)
+                n = samples // B
+                new = lambda r, w: torch.empty((r, w), dtype=torch.float32, device=self.device)
+                gl, gf = new(n * B, classes), new(n * B, cls.params['Feature.W'].shape[1])
+                for i in range(n):
+                    self.model.sample_noise(self.feed)
+                    p_z = self.model.HyperGenerator(self.feed['k_onehot'], self.feed['p_z_noise']) if c.K else self.feed['p_z_noise']
+                    lg, ft = cls.logits(self.model.Generator(p_z), features=True)
+                    gl[i * B:(i + 1) * B].copy_(lg)
+                    gf[i * B:(i + 1) * B].copy_(ft)
+                dev = self._cls_rows(dev_batches, rows)
+                m = len(dev) * B
+                dl, df, dy = new(m, classes), new(m, gf.shape[1]), torch.cat([y for _, y in dev])
+                for i, (x, _) in enumerate(dev):
+                    lg, ft = cls.logits(x, features=True)
+                    dl[i * B:(i + 1) * B].copy_(lg)
+                    df[i * B:(i + 1) * B].copy_(ft)
+                del dev
+            finally:
+                self.feed['rng_state'] = shared
+            if m < 2 or n * B < 2:
+                raise ValueError('the classifier pass needs at least 2 rows per set')
+            sx, sd = F.class_score(gl, min(splits, n * B)), F.class_score(dl, min(splits, m))
+            _, hits, st_y = F.softmax_xent(dl, dy)
+            both = min(m, n * B)                                     # as many rows on either side
+            fd, st_f = F.frechet_distance(df[:both], gf[:both])
+            host = torch.cat([sx.mean.reshape(1).double(), sx.std.reshape(1).double(), sd.mean.reshape(1).double(), hits.double(), fd[:1],
+                              sx.status.double(), sd.status.double(), st_y.double(), st_f.double()]).cpu().numpy()
+        status = (int(host[5]), int(host[5]), int(host[6]), int(host[7]), int(host[8]) | int(host[5]) | int(host[6]))
+        if any(status):
+            print('[evaluate] classifier: status %d (x) / %d (data) / %d (accuracy) / %d (frechet) -- scores and accuracy: %d a label out of '
+                  'range, %d a non-finite logit; frechet: %d a non-finite moment, %d the eigenvalue iteration did not converge -- its values '
+                  'are nan' % (status[0], status[2], status[3], int(host[8]), F.CLS_BAD_LABEL, F.CLS_NONFINITE, F.FRECHET_NONFINITE,
+                               F.FRECHET_NOT_CONVERGED))
+        vals = (float(host[0]), float(host[1]), float(host[2]), float(host[3]) / m, float(host[4]))
+        res = {k: (float('nan') if st else v) for k, v, st in zip(CLS_KEYS, vals, status)}
+        if fitted:
+            cls.held_out = res['dev classifier accuracy']
+            path = os.environ.get('GGAN_CLS_CKPT')
+            if path:
+                cls.save(path)
+        if return_sets:
+            return res, dict(scores_x=sx.scores, scores_data=sd.scores, entropies_x=(sx.row_entropy, sx.marginal_entropy),
+                             entropies_data=(sd.row_entropy, sd.marginal_entropy), logits_x=gl, features_x=gf, logits_data=dl, features_data=df,
+                             labels=dy, classifier=cls)
+        return res
+
     def manifold(self, batches, out_dir, frame):
         """embeds the point sets of latent_sets with functional.tsne and writes the scatters under the reference's file names; returns
         the paths: the four pictures of gmgan_inference_mnist with a mixture prior, the one of gan_inference_mnist without.  MNIST models
@@ -1136,6 +1276,7 @@ def main(argv=None):
     ap.add_argument('--probe', action='store_true', help='also fit a least-squares linear probe on the codes of labelled training rows and score it on the labelled dev set (dev probe accuracy z / fit probe accuracy z / dev probe accuracy xr; image scripts with labelled data)')
     ap.add_argument('--frechet', action='store_true', help='also score the dev set by the Frechet distance between Gaussians fitted to q_z and prior draws, and to randomly projected dev and generated images (dev frechet z / xr and their mean parts; image scripts; not comparable with a published FID)')
     ap.add_argument('--swd', action='store_true', help='also score the dev set by the sliced Wasserstein distance of q_z against prior draws and of the dev images against generated ones in the full pixel space, over fixed random unit directions (dev swd z / x and their max rows; image scripts; not comparable with a published SWD)')
+    ap.add_argument('--cls', action='store_true', help='also score 50000 generated images by the inception-score formula under a small classifier fitted on the labelled training rows (or loaded from $GGAN_CLS_CKPT), with the same score of the dev images, its accuracy and the Frechet distance of its features (dev classifier score x / score std x / score data / accuracy / frechet x; image scripts with labelled data; not comparable with a published inception score or FID)')
     ap.add_argument('--ema', action='store_true', help="score the averaged generator-side weights the checkpoint holds (its ema/gen/ keys, written by a run with $GGAN_EMA_DECAY) instead of the last iterate: every name gets the suffix ' ema', every file '_ema'; the critic of 'dev gen cost ema' is the live one")
     ap.add_argument('--set', action='append', default=[], metavar='KEY=VALUE', help='override an UPPERCASE setting (int / float / str)')
     a = ap.parse_args(argv)
@@ -1161,6 +1302,8 @@ def main(argv=None):
             ap.error('--frechet: %s' % _NO_CODE)
         if a.swd:
             ap.error('--swd: %s' % _NO_CODE)
+        if a.cls:
+            ap.error('--cls: the state-space scripts have no single set of images to classify')
     if a.manifold:          # (checked before anything is built)
         name = os.path.splitext(os.path.basename(a.script))[0]
         if name not in MANIFOLD_SCRIPTS:
@@ -1188,17 +1331,18 @@ def main(argv=None):
         # the checkpoint's live ones), and the evaluators only name what they write
         tr.load_params(ema)
         tr.ema_loaded = True
-    res = evaluate_once(tr, S, out_dir=a.out_dir, manifold=a.manifold, probe=a.probe, frechet=a.frechet, swd=a.swd, **{row.name: getattr(a, row.name) for row in SET_SCORES})
+    res = evaluate_once(tr, S, out_dir=a.out_dir, manifold=a.manifold, probe=a.probe, frechet=a.frechet, swd=a.swd, cls=a.cls, **{row.name: getattr(a, row.name) for row in SET_SCORES})
     for k in sorted(res):
         print('%s\t%s' % (k, res[k]))
     return res
 
 
-def evaluate_once(tr, S, out_dir=None, frame='eval', manifold=False, probe=False, frechet=False, swd=False, **scores):
+def evaluate_once(tr, S, out_dir=None, frame='eval', manifold=False, probe=False, frechet=False, swd=False, cls=False, **scores):
     """every pass the script's data allow, once -> {name: value}; manifold: the latent-space pictures too (labelled dev data only);
     probe: the three values of Evaluator.probe_scores too, after the set-level scores (image scripts; skipped with one message where the
     dev set or the training split has no labels); frechet: the four values of Evaluator.frechet_scores too, after those (image scripts; no
-    labels needed); swd: the four values of Evaluator.swd_scores too, after those (image scripts; no labels needed);
+    labels needed); swd: the four values of Evaluator.swd_scores too, after those (image scripts; no labels needed); cls: the five values of
+    Evaluator.classifier_scores too, after those (image scripts; skipped with one message where the dev set or the training split has no labels);
     scores: the set-level scores of SET_SCORES to add, by name (mmd=True, ...: Evaluator.set_scores' keywords, one build of the sets for all
     of them; a score that needs labels is skipped on unlabelled dev data); a trainer whose weights are averaged ones loaded from a
     checkpoint (tr.ema_loaded, main --ema): names and files carry the suffixes.  The state-space scripts: the video files (with out_dir)
@@ -1213,6 +1357,8 @@ def evaluate_once(tr, S, out_dir=None, frame='eval', manifold=False, probe=False
             raise ValueError('frechet: %s' % _NO_CODE)
         if swd:
             raise ValueError('swd: %s' % _NO_CODE)
+        if cls:
+            raise ValueError('cls: the state-space scripts have no single set of images to classify')
         ev = SequenceEvaluator(tr, S)
         ev.weights = 'ema' if ema_names else 'live'
         dev, _ = run.eval_sets(S, tr.model, tr.device)
@@ -1246,6 +1392,12 @@ def evaluate_once(tr, S, out_dir=None, frame='eval', manifold=False, probe=False
         res.update(ev.tag(ev.frechet_scores(dev)))
     if swd:
         res.update(ev.tag(ev.swd_scores(dev)))
+    if cls:
+        fit = run.classifier_sets(S) if run.labelled(dev) else None
+        if not fit:
+            print('[evaluate] dev classifier score skipped: no labelled dev set and training split')
+        else:
+            res.update(ev.tag(ev.classifier_scores(fit, dev)))
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
         ev.set_fixed_data(dev[0])

@@ -31,6 +31,9 @@ from .rows import (  # noqa: F401
     AggDiv, RowLerp, gmm_posterior_assign_, cluster_accuracy_, sheet_grid, video_sheet_u8)
 from .conv3d import _dims3, Im2Col3d, Col2Im3d, _conv3d_patch, _igemm_ok, Conv3dImplicit, conv3d  # noqa: F401
 from .losses import BceSum, Distance, MeanSum, GradPenalty  # noqa: F401
+from .losses import (  # noqa: F401
+    SoftmaxXent, softmax_xent, class_score, ClassScore, CLS_MAX_CLASSES, CLS_MAX_SPLITS, CLS_MAX_BATCH, CLS_SCORE_MAX_ROWS, CLS_BAD_LABEL,
+    CLS_NONFINITE)
 from .optim_ops import ema_step_, swap_  # noqa: F401
 from .optim_ops import adam_step_, rmsprop_step_, NOISE_NORMAL, NOISE_UNIFORM, NOISE_ONEHOT, noise_state, noise_fill_, pack_  # noqa: F401
 from .tsne import (  # noqa: F401

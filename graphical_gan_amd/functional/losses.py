@@ -1,4 +1,5 @@
 """loss heads: sigmoid cross-entropy sums, means, distances, the gradient penalty."""
+import collections
 import ctypes as C
 import torch
 from .. import _lib
@@ -279,6 +280,105 @@ class MeanSum(Function):
             check(_L().ggan_mean_bwd(_p(g), float(w), _p(gx), n, _stream()), 'ggan_mean_bwd')
             outs.append(gx.reshape(shp))
         return (None,) + tuple(outs)
+
+
+CLS_MAX_CLASSES, CLS_MAX_SPLITS, CLS_MAX_BATCH, CLS_SCORE_MAX_ROWS = 64, 64, 65536, 1 << 20   # include/ggan.h: GGAN_CLS_MAX_CLASSES / _MAX_SPLITS, the row ranges
+CLS_BAD_LABEL, CLS_NONFINITE = 1, 2                                                          # ... and the bits of the status word
+
+
+def _cls_logits(name, logits, most):
+    """float32 logits [1 <= rows <= most, 2 <= classes <= CLS_MAX_CLASSES] on the device (GganError for a CPU tensor, ValueError otherwise)"""
+    if not logits.is_cuda or logits.dtype != torch.float32:
+        raise _lib.GganError('%s: float32 logits on a HIP device expected, got %s on %s; there is no CPU path' % (name, logits.dtype, logits.device))
+    if logits.dim() != 2 or not 1 <= logits.shape[0] <= most or not 2 <= logits.shape[1] <= CLS_MAX_CLASSES:
+        raise ValueError('%s: logits [1 <= rows <= %d, 2 <= classes <= %d] expected, got %s' % (name, most, CLS_MAX_CLASSES, tuple(logits.shape)))
+
+
+class _SoftmaxXentGrad(Function):
+    """g * dlogits for SoftmaxXent.backward: nothing for a train op's unit seed, else one pointwise launch (ggan_row_lerp from a zero row:
+    0 + g (dlogits - 0), exact).  It is a node of its own so that a second differentiation meets a backward that says what is missing."""
+
+    @staticmethod
+    def forward(ctx, logits, dlogits, g):
+        if is_unit_seed(g):
+            return dlogits.view_as(dlogits)
+        g = _c(g.reshape(1))
+        out = torch.empty_like(dlogits)
+        zero = torch.zeros_like(dlogits)
+        check(_L().ggan_row_lerp(_p(zero), _p(dlogits), _p(g), _p(out), 1, dlogits.numel(), _stream()), 'ggan_row_lerp')
+        return out
+
+    @staticmethod
+    def backward(ctx, gg):
+        raise NotImplementedError('SoftmaxXent is differentiable once: its second derivative (diag(p) - p p^T per row) is not built')
+
+
+class SoftmaxXent(Function):
+    """(mean_b softmax cross-entropy of logits [B, C] against labels int32 [B] -> 0-dim tensor, hits int32 [1], status int32 [1]) in one
+    sweep (ggan_softmax_xent_fwd_grad), which also leaves d loss / d logits = (softmax - onehot) / B; the backward scales it by the
+    incoming gradient.  Differentiable once.  A label outside [0, C) or a non-finite logit is a bit of status and makes the loss NaN."""
+
+    @staticmethod
+    def forward(ctx, logits, labels):
+        name = 'SoftmaxXent'
+        _cls_logits(name, logits, CLS_MAX_BATCH)
+        logits = _c(logits)
+        B, classes = logits.shape
+        dev = logits.device
+        if labels.dim() != 1 or labels.dtype != torch.int32 or labels.shape[0] != B or labels.device != dev:
+            raise ValueError('%s: labels must be int32 [%d] on %s, got %s %s on %s' % (name, B, dev, labels.dtype, tuple(labels.shape), labels.device))
+        labels = labels.contiguous()
+        loss = torch.empty((1,), dtype=torch.float32, device=dev)
+        dlogits = torch.empty_like(logits)
+        hits = torch.empty((1,), dtype=torch.int32, device=dev)
+        status = torch.empty((1,), dtype=torch.int32, device=dev)
+        nbytes = int(_L().ggan_softmax_xent_workspace(B, classes))
+        ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=dev)
+        check(_L().ggan_softmax_xent_fwd_grad(_p(logits), _p(labels), B, classes, _p(loss), _p(dlogits), _p(hits), _p(status), _p(ws), nbytes,
+                                               _stream()), 'ggan_softmax_xent_fwd_grad')
+        ctx.mark_non_differentiable(hits, status)
+        ctx.save_for_backward(logits, dlogits)
+        return loss.reshape(()), hits, status
+
+    @staticmethod
+    def backward(ctx, g, _ghits, _gstatus):
+        logits, dlogits = ctx.saved_tensors
+        return _SoftmaxXentGrad.apply(logits, dlogits, g), None
+
+
+def softmax_xent(logits, labels):
+    """SoftmaxXent as a function -> (loss 0-dim float32, hits int32 [1], status int32 [1]: 0, or CLS_BAD_LABEL | CLS_NONFINITE), device
+    tensors, nothing is read back.  1 <= B <= CLS_MAX_BATCH, 2 <= C <= CLS_MAX_CLASSES."""
+    return SoftmaxXent.apply(logits, labels)
+
+
+ClassScore = collections.namedtuple('ClassScore', 'scores mean std row_entropy marginal_entropy status')
+ClassScore.__doc__ = """the inception-score formula on a classifier's logits, device tensors: scores float32 [splits], mean and std (population) of the
+scores over the splits, the mean row entropy and the entropy of the marginal over all rows (float32, 0-dim), status int32 [1] (0, or
+CLS_NONFINITE: every value is then NaN)"""
+
+
+def class_score(logits, splits):
+    """exp(mean_i KL(p_i || pbar)) per split of the rows of logits float32 [N, C], p = softmax(logits), pbar the split's mean posterior
+    (ggan_class_score: split s covers the rows [s N / splits, (s + 1) N / splits); computed as exp(H(pbar) - mean_i H(p_i)) from the
+    log-softmax, so an underflowed posterior is 0 and not NaN) -> ClassScore.  1 <= splits <= CLS_MAX_SPLITS, splits <= N <=
+    CLS_SCORE_MAX_ROWS, 2 <= C <= CLS_MAX_CLASSES.  Device tensors, no host synchronisation.  Forward only."""
+    name = 'class_score'
+    _cls_logits(name, logits, CLS_SCORE_MAX_ROWS)
+    splits = int(splits)
+    if not 1 <= splits <= min(CLS_MAX_SPLITS, logits.shape[0]):
+        raise ValueError('%s: 1 <= splits <= min(%d, rows) expected, got %d with %d rows' % (name, CLS_MAX_SPLITS, splits, logits.shape[0]))
+    if torch.is_grad_enabled() and logits.requires_grad:
+        raise _lib.GganError('%s has no backward: detach the logits' % name)
+    logits = _c(logits)
+    (N, classes), dev = logits.shape, logits.device
+    scores = torch.empty((splits,), dtype=torch.float32, device=dev)
+    stats = torch.empty((4,), dtype=torch.float32, device=dev)
+    status = torch.empty((1,), dtype=torch.int32, device=dev)
+    nbytes = int(_L().ggan_class_score_workspace(N, classes, splits))
+    ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=dev)
+    check(_L().ggan_class_score(_p(logits), N, classes, splits, _p(scores), _p(stats), _p(status), _p(ws), nbytes, _stream()), 'ggan_class_score')
+    return ClassScore(scores, stats[0], stats[1], stats[2], stats[3], status)
 
 
 class GradPenalty(Function):

@@ -174,8 +174,14 @@ def probe_sets(S):
     SVHN), drawn with numpy's global RNG seeded to a constant -- the same rows every run -- inside the saved and restored state; None
     where the data have no labels (celebA, synthetic minibatches) or are not there.  The dev side is eval_sets' labelled dev set."""
     from .evaluate import PROBE_FIT_ROWS
+    return _leading_training_rows(S, S.get('PROBE_FIT_ROWS', PROBE_FIT_ROWS))
+
+
+def _leading_training_rows(S, rows):
+    """the leading `rows` rows of the loader's labelled TRAINING split as full minibatches [(images, labels)], drawn under PROBE_DATA_SEED
+    inside the saved and restored numpy state; None without labels or data (probe_sets, classifier_sets)"""
     ds, B = S['DATASET'], S['BATCH_SIZE']
-    n = max(1, int(S.get('PROBE_FIT_ROWS', PROBE_FIT_ROWS)) // B)
+    n = max(1, int(rows) // B)
     state = np.random.get_state()
     try:
         if S.get('SYNTHETIC') == 'force' or ds not in ('mnist', 'cifar10', 'svhn'):
@@ -188,6 +194,30 @@ def probe_sets(S):
         return None
     finally:
         np.random.set_state(state)
+
+
+# the classifier score of generated images (evaluate.Evaluator.classifier_scores): the reference's inception-score pass under a classifier the
+# run fits for itself on the labelled TRAINING split.  A pass of its own with a noise state of its own.  Off unless asked for
+def classifier_settings(script):
+    """{'CLS_EVERY': N} for the eight image scripts when $GGAN_CLS_EVERY = N is set, {} otherwise and for every other script (the state-space
+    scripts have no single set of images to classify)"""
+    name = os.path.splitext(os.path.basename(script))[0]
+    n = os.environ.get('GGAN_CLS_EVERY')
+    return {'CLS_EVERY': int(n)} if n and name in _IMAGE_SCRIPTS else {}
+
+
+def classifier_due(S, it):
+    """does the classifier pass fire after iteration `it`: it % N == N - 1, the cadence of the other passes"""
+    n = int(S.get('CLS_EVERY') or 0)
+    return bool(n and it % n == n - 1)
+
+
+def classifier_sets(S):
+    """the labelled minibatches the classifier is fitted on: the leading CLS_FIT_ROWS rows of the loader's TRAINING split, drawn as
+    probe_sets draws its rows (the same constant seed: the probe's rows lead them); None where the data have no labels (celebA, synthetic
+    minibatches) or are not there.  The dev side is eval_sets' labelled dev set."""
+    from .evaluate import CLS_FIT_ROWS
+    return _leading_training_rows(S, S.get('CLS_FIT_ROWS', CLS_FIT_ROWS))
 
 
 # the Frechet distance of codes and of projected images (evaluate.Evaluator.frechet_scores) is a pass of its own too: it draws its noise from
@@ -540,8 +570,17 @@ def train(S, cfg, model=None, out_dir=None):
     if swd and sequences:
         print('[run] dev swd skipped: the state-space models have no single code to compare')
         swd = False
-    ev = the_eval() if plan or manifold or on or probe or frechet or swd else None
-    ev_dev, ev_test = the_sets() if plan or manifold or probe or frechet or swd or (on and not sequences) else (None, None)
+    # the classifier score of generated images: the labelled training rows its classifier is fitted on are loaded once per run, where the pass is on
+    cls = bool(S.get('CLS_EVERY')) and lead
+    the_cls_fit = functools.lru_cache(None)(lambda: classifier_sets(S))
+    if cls and sequences:
+        print('[run] dev classifier score skipped: the state-space models have no single set of images to classify')
+        cls = False
+    elif cls and not (labelled(the_sets()[0]) and the_cls_fit()):
+        print('[run] dev classifier score skipped: no labelled dev set and training split (%s data)' % source)
+        cls = False
+    ev = the_eval() if plan or manifold or on or probe or frechet or swd or cls else None
+    ev_dev, ev_test = the_sets() if plan or manifold or probe or frechet or swd or cls or (on and not sequences) else (None, None)
     flush = lambda: lib.plot.flush(out_dir, os.path.join(out_dir, 'logfile.txt') if out_dir else None)
     eval_ms = 0.0            # wall time of the evaluation passes (kept out of `time`)
     for it in range(S['ITERS']):
@@ -592,6 +631,11 @@ def train(S, cfg, model=None, out_dir=None):
             for w in passes:
                 with _on_weights(ev, w):
                     eval_ms += _timed(device, lambda: _plot(ev.tag(ev.swd_scores(ev_dev))))
+            flush()
+        if cls and classifier_due(S, it):
+            for w in passes:       # (the classifier is fitted by the first of these and scores both sets of weights)
+                with _on_weights(ev, w):
+                    eval_ms += _timed(device, lambda: _plot(ev.tag(ev.classifier_scores(the_cls_fit(), ev_dev))))
             flush()
         lib.plot.tick()
         if out_dir and S.get('SAVE_EVERY') and (it + 1) % S['SAVE_EVERY'] == 0:

@@ -600,6 +600,44 @@ size_t ggan_swd_workspace(int m, int n, int L);
 int ggan_swd(const float* PX, const float* PY, int m, int n, int L, int p, double* per, double* out, int32_t* status, void* ws,
              size_t ws_bytes, ggan_stream_t stream);
 
+/* A classifier's loss and the score of its posteriors (functional.SoftmaxXent / softmax_xent / class_score, classifier.ImageClassifier).
+ * Both read device fp32 logits [rows, classes] row-major, 2 <= classes <= GGAN_CLS_MAX_CLASSES; one wavefront takes a row and one lane a
+ * class.  fp32 inside a row (the maximum and the sum of exp(x - max) by a fixed butterfly over the wave, expf and logf at their accurate
+ * forms), fp64 across rows (a wave's rows in row order, a workgroup's waves in wave order, the workgroups' partials by one finishing
+ * workgroup in a fixed order).  No floating-point atomics: repeated calls give the same bits.
+ *   ggan_softmax_xent_fwd_grad: tf.nn.softmax_cross_entropy_with_logits with one-hot labels, averaged over the rows (the reference's only use,
+ *                       gmgan_inference_cifar10.py:392,402, is commented out; the library had no categorical cross-entropy), with its gradient
+ *                       in the same launch.  labels int32 [B], 1 <= B <= 65536.
+ *                       loss[0] = mean_b (log sum_c exp(x_bc - max_b) - (x_b,label - max_b)); dlogits[B,classes] = (softmax(x_b) - onehot) / B;
+ *                       hits[0] = the rows whose argmax is their label, the LOWEST class on a tie; status[0] is WRITTEN: GGAN_CLS_BAD_LABEL if a
+ *                       label lies outside [0, classes) (it is never an index: the row's one-hot is empty), GGAN_CLS_NONFINITE for a logit that
+ *                       is NaN or +-inf, else 0.  With a status loss[0] is NaN; every row of dlogits is written all the same.
+ *   ggan_class_score:   tflib/inception_score.py:47-53 from logits instead of posteriors (the frozen Inception graph of :56-90 is a download; the
+ *                       caller brings its own classifier): split s of `splits` covers the rows [s N / splits, (s + 1) N / splits) in integer
+ *                       division (:49), 1 <= splits <= GGAN_CLS_MAX_SPLITS, splits <= N <= 1048576, and
+ *                       scores[s] = exp(mean_i sum_c p_ic (log p_ic - log pbar_c)), pbar = mean_i p_i, computed as exp(H(pbar) - mean_i H(p_i))
+ *                       from sum_i sum_c p_ic log p_ic and the column sums sum_i p_ic of ONE sweep: log p is the log-softmax
+ *                       (x - max) - log sum exp(x - max), never the log of a probability, and pbar log pbar is 0 at pbar = 0 -- where the
+ *                       reference's np.log(part) (:50) turns an underflowed posterior into NaN, this stays finite.
+ *                       stats[4] = { mean_s scores (:53), the population std over the splits (np.std, :53), mean_i H(p_i) over all rows,
+ *                       H of the marginal over all rows }.  status[0] is WRITTEN: GGAN_CLS_NONFINITE for a logit that is NaN or +-inf -- scores
+ *                       and stats are then all NaN --, else 0.  A workgroup of the sweep takes GGAN_CLS_ROW_BLOCK rows of one split.
+ * ws: ggan_softmax_xent_workspace(B, classes) / ggan_class_score_workspace(N, classes, splits) bytes of 16-byte aligned device scratch (0 =
+ * arguments out of range).  Arguments out of range, a null pointer or a short or misaligned workspace return a negative code before any
+ * device work.
+ * Added without a version change: no existing entry point or struct is touched. */
+#define GGAN_CLS_MAX_CLASSES 64
+#define GGAN_CLS_MAX_SPLITS 64
+#define GGAN_CLS_ROW_BLOCK 256
+#define GGAN_CLS_BAD_LABEL 1
+#define GGAN_CLS_NONFINITE 2
+size_t ggan_softmax_xent_workspace(int B, int classes);
+int ggan_softmax_xent_fwd_grad(const float* logits, const int32_t* labels, int B, int classes, float* loss, float* dlogits, int32_t* hits,
+                               int32_t* status, void* ws, size_t ws_bytes, ggan_stream_t stream);
+size_t ggan_class_score_workspace(int N, int classes, int splits);
+int ggan_class_score(const float* logits, int N, int classes, int splits, float* scores, float* stats, int32_t* status, void* ws,
+                     size_t ws_bytes, ggan_stream_t stream);
+
 /* Stochastic encoder head, TYPE_Q = 'learn_std' (gan_inference_cifar10.py:173-188): std = exp(log_std), z = mean + eps * std; the backward
  * takes the gradients arriving at z and at std (either may be NULL). */
 int ggan_reparam_fwd(const float* mean, const float* log_std, const float* eps, float* z, float* std_out, size_t n, ggan_stream_t stream);
