@@ -104,6 +104,14 @@ SIGNATURES = {
     'ggan_softmax_xent_fwd_grad': (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
     'ggan_class_score_workspace': (_Z, [_I, _I, _I]),
     'ggan_class_score': (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _Z, _P]),
+    'ggan_kmeans_workspace': (_Z, [_I, _I, _I]),
+    'ggan_kmeans_seed': (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _Z, _P]),
+    'ggan_kmeans_pick': (_I, [_P, _I, _P, _P, _P]),
+    'ggan_kmeans_assign': (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    'ggan_kmeans_update': (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _Z, _P]),
+    'ggan_kmeans_fit': (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    'ggan_bin_test': (_I, [_P, _P, _I, C.c_double, _P, _P]),
+    'ggan_cluster_scores': (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P]),
     'ggan_noise_fill': (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _P]),
     'ggan_gmm_latent_fwd': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _P]),
     'ggan_gmm_latent_bwd': (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P]),

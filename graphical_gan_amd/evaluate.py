@@ -73,7 +73,7 @@ run by SequenceEvaluator on a models_ssgan.StateSpaceGAN under the same rules:
 Each is written as a .png sheet (one sequence per row) and a looping .gif; the bytes of both come from one ggan_video_sheet_u8 launch.
 
 `python -m graphical_gan_amd.evaluate CKPT --script gmgan_inference_mnist [--data-dir DIR]` scores a saved checkpoint
-(`--out-dir DIR --manifold` also writes the latent-space pictures of the two MNIST scripts, `--mmd` adds the two MMD^2 rows, `--prdc` the eight precision / recall / density / coverage rows, `--knn` the two k-NN accuracy rows, `--parzen` the three Parzen-window rows, `--rec` the four reconstruction rows, `--probe` the three linear-probe rows, `--frechet` the four Frechet-distance rows, `--swd` the four sliced-Wasserstein rows, `--cls` the five classifier-score rows);
+(`--out-dir DIR --manifold` also writes the latent-space pictures of the two MNIST scripts, `--mmd` adds the two MMD^2 rows, `--prdc` the eight precision / recall / density / coverage rows, `--knn` the two k-NN accuracy rows, `--parzen` the three Parzen-window rows, `--rec` the four reconstruction rows, `--probe` the three linear-probe rows, `--frechet` the four Frechet-distance rows, `--swd` the four sliced-Wasserstein rows, `--cls` the five classifier-score rows, `--kmeans` the five NDB / k-means rows);
 `... CKPT --script ssgan_inference_moving_mnist|ssgan_inference_chairs [--data-dir DIR] --out-dir DIR` writes the four pairs of files;
 `--rec` prints the four reconstruction rows of the sequences' frames, and alone needs no --out-dir.
 
@@ -124,6 +124,14 @@ CLS_FIT_ROWS = 20000      # labelled training rows its classifier is fitted on (
 CLS_EPOCHS = 4            # passes over them (settings: CLS_EPOCHS)
 CLS_SEED = 179426         # offset of its own noise state, and of the classifier's initial values, from the evaluator's seed
 CLS_KEYS = ('dev classifier score x', 'dev classifier score std x', 'dev classifier score data', 'dev classifier accuracy', 'dev classifier frechet x')
+KM_BINS = 100             # the bins of the kmeans_scores pass's NDB (settings: KM_BINS; at most functional.KMEANS_MAX_K)
+KM_FIT_ROWS = 20000       # leading training rows its bins are fitted on (settings: KM_FIT_ROWS)
+KM_SAMPLES = 20000        # generated rows it bins, floor(KM_SAMPLES / B) fresh-noise minibatches (settings: KM_SAMPLES)
+KM_MAX_ROWS = 10000       # dev rows it bins and clusters (settings: KM_MAX_ROWS)
+KM_ITERS = 50             # Lloyd iterations of either fit (settings: KM_ITERS)
+KM_Z_THRESHOLD = 1.959963984540054    # the z statistic above which a bin differs: two-sided 5 % (settings: KM_Z_THRESHOLD)
+KM_SEED = 193939          # offset of its own noise state, and of the uniforms of its seedings, from the evaluator's seed
+KM_KEYS = ('dev ndb x', 'dev ndb js x', 'dev ndb data', 'dev kmeans accuracy z', 'dev kmeans nmi z')
 EVAL_SEED = 7919          # offset of the evaluator's noise seeds from the settings seed (the Trainer's stream of draws is not touched)
 
 # the reference's output file names, per script: (samples, reconstructions), formatted with frame= and mode=
@@ -982,6 +990,150 @@ class Evaluator(_Passes):
                              labels=dy, classifier=cls)
         return res
 
+    _km_rng = _km_bins = None                 # the k-means pass's own noise state and its fitted bins, made by its first call
+    _km_said = False                          # the one message about unlabelled dev data was printed
+    km_fits = 0                               # how many times this evaluator fitted the bins ...
+    km_z_fits = 0                             # ... and the clusters of the codes
+
+    def _km_unit(self, x):
+        """[B, OUTPUT_DIM] in the Generator's range -> float32 pixels in [0, 1] (as _to_unit), on the device"""
+        lo = 0.0 if self.cfg.out_act == 'sigmoid' else -1.0
+        x = x.float().reshape(self.cfg.B, -1).contiguous()
+        return F.Axpby.apply(x, None, 1.0 / (1.0 - lo), 0.0, -lo / (1.0 - lo)) if lo else x
+
+    def _km_rows(self, batches, rows, codes=False):
+        """the leading full minibatches, at most `rows` rows -> (pixels float32 [n B, OUTPUT_DIM] in [0, 1], q_z float32 [n B, DIM_LATENT] or
+        None, int32 labels [n B] or None where a minibatch has none), on the device"""
+        c, B = self.cfg, self.cfg.B
+        full = [b for b in batches if _split(b)[0].shape[0] == B]
+        if not full:
+            raise ValueError('no full minibatch of %d rows to evaluate on' % B)
+        n = min(len(full), max(1, int(rows) // B))
+        labels = all(_split(b)[1] is not None for b in full[:n])
+        X = torch.empty((n * B, c.output_dim), dtype=torch.float32, device=self.device)
+        Z = torch.empty((n * B, c.dim_latent), dtype=torch.float32, device=self.device) if codes else None
+        Y = []
+        slab = max(1, PROBE_SLAB_ROWS // B)
+        for s0 in range(0, n, slab):
+            Xs, Ys = self._stage(full[s0:min(n, s0 + slab)], want_labels=labels)
+            Y.append(Ys)
+            for i in range(Xs.shape[0]):
+                at = slice((s0 + i) * B, (s0 + i + 1) * B)
+                if codes:
+                    self._load(Xs[i])
+                else:
+                    self.model.set_batch(self.feed, Xs[i])
+                real_x = self.model.real_x(self.feed)
+                X[at].copy_(self._km_unit(real_x))
+                if codes:
+                    q = self.model.Extractor(real_x, eps=self.feed['q_eps']) if c.agg else self.model.Extractor(real_x)
+                    Z[at].copy_((q[0] if isinstance(q, tuple) else q).float().reshape(B, -1))
+        return X, Z, (torch.cat(Y) if labels else None)
+
+    def _km_uniforms(self, k, which):
+        """the k uniforms of a seeding, drawn on the host from a RandomState of the pass's own: 0 the bins, 1 the clusters of the codes"""
+        return np.random.RandomState(int(self.S.get('SEED', 0)) + EVAL_SEED + KM_SEED + which).rand(k)
+
+    def kmeans_scores(self, fit_batches, dev_batches, return_sets=False):
+        """{'dev ndb x', 'dev ndb js x', 'dev ndb data', 'dev kmeans accuracy z', 'dev kmeans nmi z'}: which regions of the data the Generator
+        over- or under-populates, and whether the classes form clusters in the code space; nothing of it exists in the reference.
+        ndb x / ndb js x: NDB/K of Richardson & Weiss 2018 -- functional.kmeans_fit cuts the pixel space ([0, 1] pixels, Euclidean cells) into
+        KM_BINS Voronoi cells on the leading KM_FIT_ROWS training rows, floor(KM_SAMPLES / B) generated minibatches (through HyperGenerator
+        with a mixture prior) are assigned to the cells a slab at a time, only the counts stay, and functional.bin_test gives the share of
+        cells whose two-proportion z statistic exceeds KM_Z_THRESHOLD and the Jensen-Shannon divergence of the two histograms; ndb data: the
+        same share for at most KM_MAX_ROWS dev images, the floor the statistic has on real data.  kmeans accuracy z / kmeans nmi z: a second
+        k-means on q_z of the labelled dev rows, KM_Z_CLUSTERS clusters (N_COMS under a mixture prior, else the classes seen), then
+        functional.cluster_scores: purity (every cluster takes its majority label) and NMI; unlabelled dev data: the two rows are left
+        out with one message.  The bins are fitted ONCE per evaluator, at the first call (they depend on the data and the seed, not on the
+        model); the clusters of the codes at every call.  The pass draws from a noise state of its own, swapped into the feed while it runs:
+        every other pass logs the same values, and training reaches the same weights, whether it is on or not.  ONE host synchronisation; a
+        raised status word (a non-finite pixel or code: a diverged model) gives nan for the rows it touches and one printed message.
+        return_sets: (values, {centres, counts_fit, counts_x, counts_data, moved, inertia: the bins' fit; and with labels centres_z, assign_z,
+        moved_z, inertia_z, labels, table})."""
+        S, c = self.S, self.cfg
+        B = c.B
+        bins, fit_rows, samples = int(S.get('KM_BINS', KM_BINS)), int(S.get('KM_FIT_ROWS', KM_FIT_ROWS)), int(S.get('KM_SAMPLES', KM_SAMPLES))
+        rows, iters, zthr = int(S.get('KM_MAX_ROWS', KM_MAX_ROWS)), int(S.get('KM_ITERS', KM_ITERS)), float(S.get('KM_Z_THRESHOLD', KM_Z_THRESHOLD))
+        if not 1 <= bins <= F.KMEANS_MAX_K:
+            raise ValueError('KM_BINS = %d: 1 to %d bins' % (bins, F.KMEANS_MAX_K))
+        if not B <= fit_rows <= F.KMEANS_MAX_ROWS:
+            raise ValueError('KM_FIT_ROWS = %d: one minibatch (%d) to %d rows' % (fit_rows, B, F.KMEANS_MAX_ROWS))
+        if samples < B:
+            raise ValueError('KM_SAMPLES = %d: at least one minibatch (%d)' % (samples, B))
+        if not B <= rows <= F.KMEANS_MAX_ROWS:
+            raise ValueError('KM_MAX_ROWS = %d: one minibatch (%d) to %d rows' % (rows, B, F.KMEANS_MAX_ROWS))
+        if not 0 <= iters <= F.KMEANS_MAX_ITERS:
+            raise ValueError('KM_ITERS = %d: 0 to %d iterations' % (iters, F.KMEANS_MAX_ITERS))
+        if not fit_batches or not dev_batches:
+            raise ValueError('the k-means pass needs training minibatches for its bins and dev minibatches')
+        labels = [_split(b)[1] for b in dev_batches]
+        labelled = all(y is not None for y in labels)
+        classes = kz = 0
+        if labelled:
+            classes = max(2, 1 + max(int(np.asarray(y.cpu() if torch.is_tensor(y) else y).max()) for y in labels))      # (host labels: no device is asked)
+            if classes > F.KMEANS_MAX_CLASSES:
+                raise ValueError('the clustering scores take at most %d classes, got %d' % (F.KMEANS_MAX_CLASSES, classes))
+            kz = int(S.get('KM_Z_CLUSTERS') or (c.K if c.K else classes))
+            if not 1 <= kz <= F.KMEANS_MAX_K:
+                raise ValueError('KM_Z_CLUSTERS = %d: 1 to %d clusters' % (kz, F.KMEANS_MAX_K))
+        elif not self._km_said:
+            print('[evaluate] dev kmeans accuracy z / nmi z skipped: no labelled dev set')
+            self._km_said = True
+        zero = lambda k: torch.zeros((k,), dtype=torch.int32, device=self.device)
+        with self._guard():
+            if self._km_rng is None:
+                self._km_rng = F.noise_state(self.device, int(S.get('SEED', 0)) + EVAL_SEED + KM_SEED)
+            shared, self.feed['rng_state'] = self.feed['rng_state'], self._km_rng
+            try:
+                if self._km_bins is None:
+                    X, _, _ = self._km_rows(fit_batches, fit_rows)
+                    self._km_bins = F.kmeans_fit(X, bins, iters, self._km_uniforms(bins, 0))
+                    self.km_fits += 1
+                    del X                                            # (the training images leave the device; stream-ordered)
+                fit = self._km_bins
+                n = samples // B
+                slab = max(1, PROBE_SLAB_ROWS // B)
+                counts_x, st_x = zero(bins), zero(1)
+                buf = torch.empty((min(n, slab) * B, c.output_dim), dtype=torch.float32, device=self.device)
+                for s0 in range(0, n, slab):
+                    m = min(slab, n - s0)
+                    for i in range(m):
+                        self.model.sample_noise(self.feed)
+                        p_z = self.model.HyperGenerator(self.feed['k_onehot'], self.feed['p_z_noise']) if c.K else self.feed['p_z_noise']
+                        buf[i * B:(i + 1) * B].copy_(self._km_unit(self.model.Generator(p_z.contiguous())))
+                    st_x |= F.kmeans_assign(buf[:m * B], fit.centres, counts=counts_x)[4]
+                del buf
+                X, Z, Y = self._km_rows(dev_batches, rows, codes=labelled)
+                counts_d = zero(bins)
+                st_d = F.kmeans_assign(X, fit.centres, counts=counts_d)[4]
+                del X
+                zfit = None
+                if labelled:
+                    zfit = F.kmeans_fit(Z, kz, iters, self._km_uniforms(kz, 1))
+                    self.km_z_fits += 1
+                    zs, table, st_c = F.cluster_scores(zfit.assign, Y, kz, classes)
+            finally:
+                self.feed['rng_state'] = shared
+            ndb_x, ndb_d = F.bin_test(fit.counts, counts_x, zthr), F.bin_test(fit.counts, counts_d, zthr)
+            parts = [ndb_x[1:], ndb_d[1:2], (fit.status | st_x).double(), (fit.status | st_d).double()]
+            if labelled:
+                parts += [zs, (zfit.status | st_c).double()]
+            host = torch.cat(parts).cpu().numpy()
+        status = (int(host[3]), int(host[3]), int(host[4])) + ((int(host[7]), int(host[7])) if labelled else ())
+        if any(status):
+            print('[evaluate] kmeans: status %d (x) / %d (data)%s -- %d: a non-finite pixel, code or distance, %d: a label or an assignment '
+                  'out of range -- its values are nan' % (status[0], status[2], ' / %d (z)' % status[3] if labelled else '', F.KMEANS_NONFINITE,
+                                                          F.KMEANS_BAD_INDEX))
+        vals = (float(host[0]), float(host[1]), float(host[2])) + ((float(host[5]), float(host[6])) if labelled else ())
+        res = {k: (float('nan') if st else v) for k, v, st in zip(KM_KEYS, vals, status)}
+        if return_sets:
+            sets = dict(centres=fit.centres, counts_fit=fit.counts, counts_x=counts_x, counts_data=counts_d, moved=fit.moved, inertia=fit.inertia)
+            if labelled:
+                sets.update(centres_z=zfit.centres, assign_z=zfit.assign, moved_z=zfit.moved, inertia_z=zfit.inertia, labels=Y, table=table,
+                            codes=Z)
+            return res, sets
+        return res
+
     def manifold(self, batches, out_dir, frame):
         """embeds the point sets of latent_sets with functional.tsne and writes the scatters under the reference's file names; returns
         the paths: the four pictures of gmgan_inference_mnist with a mixture prior, the one of gan_inference_mnist without.  MNIST models
@@ -1277,6 +1429,7 @@ def main(argv=None):
     ap.add_argument('--frechet', action='store_true', help='also score the dev set by the Frechet distance between Gaussians fitted to q_z and prior draws, and to randomly projected dev and generated images (dev frechet z / xr and their mean parts; image scripts; not comparable with a published FID)')
     ap.add_argument('--swd', action='store_true', help='also score the dev set by the sliced Wasserstein distance of q_z against prior draws and of the dev images against generated ones in the full pixel space, over fixed random unit directions (dev swd z / x and their max rows; image scripts; not comparable with a published SWD)')
     ap.add_argument('--cls', action='store_true', help='also score 50000 generated images by the inception-score formula under a small classifier fitted on the labelled training rows (or loaded from $GGAN_CLS_CKPT), with the same score of the dev images, its accuracy and the Frechet distance of its features (dev classifier score x / score std x / score data / accuracy / frechet x; image scripts with labelled data; not comparable with a published inception score or FID)')
+    ap.add_argument('--kmeans', action='store_true', help='also bin 20000 generated images into k-means cells fitted on the device on the leading training rows and report NDB/K, the Jensen-Shannon divergence of the two histograms and the NDB/K of the dev images, and score a k-means of q_z of the labelled dev set by purity and NMI (dev ndb x / ndb js x / ndb data / kmeans accuracy z / kmeans nmi z; image scripts; the z rows need labels; comparable with published NDB figures only at equal K, row counts and space)')
     ap.add_argument('--ema', action='store_true', help="score the averaged generator-side weights the checkpoint holds (its ema/gen/ keys, written by a run with $GGAN_EMA_DECAY) instead of the last iterate: every name gets the suffix ' ema', every file '_ema'; the critic of 'dev gen cost ema' is the live one")
     ap.add_argument('--set', action='append', default=[], metavar='KEY=VALUE', help='override an UPPERCASE setting (int / float / str)')
     a = ap.parse_args(argv)
@@ -1304,6 +1457,8 @@ def main(argv=None):
             ap.error('--swd: %s' % _NO_CODE)
         if a.cls:
             ap.error('--cls: the state-space scripts have no single set of images to classify')
+        if a.kmeans:
+            ap.error('--kmeans: the state-space scripts have no single set of images to bin')
     if a.manifold:          # (checked before anything is built)
         name = os.path.splitext(os.path.basename(a.script))[0]
         if name not in MANIFOLD_SCRIPTS:
@@ -1331,18 +1486,19 @@ def main(argv=None):
         # the checkpoint's live ones), and the evaluators only name what they write
         tr.load_params(ema)
         tr.ema_loaded = True
-    res = evaluate_once(tr, S, out_dir=a.out_dir, manifold=a.manifold, probe=a.probe, frechet=a.frechet, swd=a.swd, cls=a.cls, **{row.name: getattr(a, row.name) for row in SET_SCORES})
+    res = evaluate_once(tr, S, out_dir=a.out_dir, manifold=a.manifold, probe=a.probe, frechet=a.frechet, swd=a.swd, cls=a.cls, kmeans=a.kmeans, **{row.name: getattr(a, row.name) for row in SET_SCORES})
     for k in sorted(res):
         print('%s\t%s' % (k, res[k]))
     return res
 
 
-def evaluate_once(tr, S, out_dir=None, frame='eval', manifold=False, probe=False, frechet=False, swd=False, cls=False, **scores):
+def evaluate_once(tr, S, out_dir=None, frame='eval', manifold=False, probe=False, frechet=False, swd=False, cls=False, kmeans=False, **scores):
     """every pass the script's data allow, once -> {name: value}; manifold: the latent-space pictures too (labelled dev data only);
     probe: the three values of Evaluator.probe_scores too, after the set-level scores (image scripts; skipped with one message where the
     dev set or the training split has no labels); frechet: the four values of Evaluator.frechet_scores too, after those (image scripts; no
     labels needed); swd: the four values of Evaluator.swd_scores too, after those (image scripts; no labels needed); cls: the five values of
     Evaluator.classifier_scores too, after those (image scripts; skipped with one message where the dev set or the training split has no labels);
+    kmeans: the values of Evaluator.kmeans_scores too, after those (image scripts; the two z rows need a labelled dev set);
     scores: the set-level scores of SET_SCORES to add, by name (mmd=True, ...: Evaluator.set_scores' keywords, one build of the sets for all
     of them; a score that needs labels is skipped on unlabelled dev data); a trainer whose weights are averaged ones loaded from a
     checkpoint (tr.ema_loaded, main --ema): names and files carry the suffixes.  The state-space scripts: the video files (with out_dir)
@@ -1359,6 +1515,8 @@ def evaluate_once(tr, S, out_dir=None, frame='eval', manifold=False, probe=False
             raise ValueError('swd: %s' % _NO_CODE)
         if cls:
             raise ValueError('cls: the state-space scripts have no single set of images to classify')
+        if kmeans:
+            raise ValueError('kmeans: the state-space scripts have no single set of images to bin')
         ev = SequenceEvaluator(tr, S)
         ev.weights = 'ema' if ema_names else 'live'
         dev, _ = run.eval_sets(S, tr.model, tr.device)
@@ -1398,6 +1556,8 @@ def evaluate_once(tr, S, out_dir=None, frame='eval', manifold=False, probe=False
             print('[evaluate] dev classifier score skipped: no labelled dev set and training split')
         else:
             res.update(ev.tag(ev.classifier_scores(fit, dev)))
+    if kmeans:
+        res.update(ev.tag(ev.kmeans_scores(run.kmeans_sets(S, tr.model, tr.device), dev)))
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
         ev.set_fixed_data(dev[0])

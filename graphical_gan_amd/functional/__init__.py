@@ -34,6 +34,9 @@ from .losses import BceSum, Distance, MeanSum, GradPenalty  # noqa: F401
 from .losses import (  # noqa: F401
     SoftmaxXent, softmax_xent, class_score, ClassScore, CLS_MAX_CLASSES, CLS_MAX_SPLITS, CLS_MAX_BATCH, CLS_SCORE_MAX_ROWS, CLS_BAD_LABEL,
     CLS_NONFINITE)
+from .kmeans import (  # noqa: F401
+    kmeans_seed, kmeans_pick, kmeans_assign, kmeans_update, kmeans_fit, KMeansFit, bin_test, cluster_scores, KMEANS_MAX_K, KMEANS_MAX_CLASSES,
+    KMEANS_ROW_BLOCK, KMEANS_MAX_ROWS, KMEANS_MAX_ITERS, KMEANS_NONFINITE, KMEANS_BAD_INDEX)
 from .optim_ops import ema_step_, swap_  # noqa: F401
 from .optim_ops import adam_step_, rmsprop_step_, NOISE_NORMAL, NOISE_UNIFORM, NOISE_ONEHOT, noise_state, noise_fill_, pack_  # noqa: F401
 from .tsne import (  # noqa: F401

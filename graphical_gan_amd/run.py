@@ -177,16 +177,20 @@ def probe_sets(S):
     return _leading_training_rows(S, S.get('PROBE_FIT_ROWS', PROBE_FIT_ROWS))
 
 
-def _leading_training_rows(S, rows):
+def _leading_training_rows(S, rows, labels=True):
     """the leading `rows` rows of the loader's labelled TRAINING split as full minibatches [(images, labels)], drawn under PROBE_DATA_SEED
-    inside the saved and restored numpy state; None without labels or data (probe_sets, classifier_sets)"""
+    inside the saved and restored numpy state; None without labels or data (probe_sets, classifier_sets).  labels=False (kmeans_sets):
+    celebA's unlabelled training split will do too"""
     ds, B = S['DATASET'], S['BATCH_SIZE']
     n = max(1, int(rows) // B)
     state = np.random.get_state()
     try:
-        if S.get('SYNTHETIC') == 'force' or ds not in ('mnist', 'cifar10', 'svhn'):
+        if S.get('SYNTHETIC') == 'force' or ds not in (('mnist', 'cifar10', 'svhn') if labels else ('mnist', 'cifar10', 'svhn', 'face')):
             return None
         np.random.seed(PROBE_DATA_SEED)
+        if ds == 'face':
+            train = lib.celebA.load(B, S.get('DATA_DIR', ''))[0]
+            return [(np.array(b[0] if isinstance(b, (tuple, list)) else b),) for b in itertools.islice(train(), n)] or None
         train = lib.mnist.load(B, B)[0] if ds == 'mnist' else getattr(lib, ds).load(B, S.get('DATA_DIR', ''))[0]
         fit = [tuple(np.array(a) for a in b[:2]) for b in itertools.islice(train(), n)]      # (copies: the loaders yield views of one array)
         return fit if labelled(fit) else None
@@ -218,6 +222,35 @@ def classifier_sets(S):
     minibatches) or are not there.  The dev side is eval_sets' labelled dev set."""
     from .evaluate import CLS_FIT_ROWS
     return _leading_training_rows(S, S.get('CLS_FIT_ROWS', CLS_FIT_ROWS))
+
+
+# NDB of the generated images and the k-means clustering scores of the codes (evaluate.Evaluator.kmeans_scores): k-means fitted on the
+# device, on the leading training rows (the bins) and on q_z of the dev set.  A pass of its own with a noise state of its own; no labels
+# needed for the bins.  Off unless asked for
+def kmeans_settings(script):
+    """{'KMEANS_EVERY': N} for the eight image scripts when $GGAN_KMEANS_EVERY = N is set, {} otherwise and for every other script (the
+    state-space scripts have no single set of images to bin)"""
+    name = os.path.splitext(os.path.basename(script))[0]
+    n = os.environ.get('GGAN_KMEANS_EVERY')
+    return {'KMEANS_EVERY': int(n)} if n and name in _IMAGE_SCRIPTS else {}
+
+
+def kmeans_due(S, it):
+    """does the k-means pass fire after iteration `it`: it % N == N - 1, the cadence of the other passes"""
+    n = int(S.get('KMEANS_EVERY') or 0)
+    return bool(n and it % n == n - 1)
+
+
+def kmeans_sets(S, model=None, device=None):
+    """the minibatches the bins are fitted on: the leading KM_FIT_ROWS rows of the loader's TRAINING split, drawn as probe_sets draws its
+    rows (the same constant seed: the probe's and the classifier's rows lead them), labels or not; without the dataset (synthetic
+    minibatches) and with a model, a synthetic set of the training ring's shapes under a seed of its own; else None"""
+    from .evaluate import KM_FIT_ROWS
+    rows = S.get('KM_FIT_ROWS', KM_FIT_ROWS)
+    fit = _leading_training_rows(S, rows, labels=False)
+    if fit is None and model is not None and S['DATASET'] not in SEQUENCE_DATASETS:
+        fit = [t for t in model.synthetic_ring(device, n=max(1, min(int(rows) // S['BATCH_SIZE'], 64)), seed=8765)]
+    return fit
 
 
 # the Frechet distance of codes and of projected images (evaluate.Evaluator.frechet_scores) is a pass of its own too: it draws its noise from
@@ -579,8 +612,14 @@ def train(S, cfg, model=None, out_dir=None):
     elif cls and not (labelled(the_sets()[0]) and the_cls_fit()):
         print('[run] dev classifier score skipped: no labelled dev set and training split (%s data)' % source)
         cls = False
-    ev = the_eval() if plan or manifold or on or probe or frechet or swd or cls else None
-    ev_dev, ev_test = the_sets() if plan or manifold or probe or frechet or swd or cls or (on and not sequences) else (None, None)
+    # NDB and the k-means clustering scores: the training rows the bins are fitted on are loaded once per run, where the pass is on
+    kmeans = bool(S.get('KMEANS_EVERY')) and lead
+    the_km_fit = functools.lru_cache(None)(lambda: kmeans_sets(S, tr.model, device))
+    if kmeans and sequences:
+        print('[run] dev ndb skipped: the state-space models have no single set of images to bin')
+        kmeans = False
+    ev = the_eval() if plan or manifold or on or probe or frechet or swd or cls or kmeans else None
+    ev_dev, ev_test = the_sets() if plan or manifold or probe or frechet or swd or cls or kmeans or (on and not sequences) else (None, None)
     flush = lambda: lib.plot.flush(out_dir, os.path.join(out_dir, 'logfile.txt') if out_dir else None)
     eval_ms = 0.0            # wall time of the evaluation passes (kept out of `time`)
     for it in range(S['ITERS']):
@@ -636,6 +675,11 @@ def train(S, cfg, model=None, out_dir=None):
             for w in passes:       # (the classifier is fitted by the first of these and scores both sets of weights)
                 with _on_weights(ev, w):
                     eval_ms += _timed(device, lambda: _plot(ev.tag(ev.classifier_scores(the_cls_fit(), ev_dev))))
+            flush()
+        if kmeans and kmeans_due(S, it):
+            for w in passes:       # (the bins are fitted by the first of these and kept)
+                with _on_weights(ev, w):
+                    eval_ms += _timed(device, lambda: _plot(ev.tag(ev.kmeans_scores(the_km_fit(), ev_dev))))
             flush()
         lib.plot.tick()
         if out_dir and S.get('SAVE_EVERY') and (it + 1) % S['SAVE_EVERY'] == 0:

@@ -638,6 +638,60 @@ size_t ggan_class_score_workspace(int N, int classes, int splits);
 int ggan_class_score(const float* logits, int N, int classes, int splits, float* scores, float* stats, int32_t* status, void* ws,
                      size_t ws_bytes, ggan_stream_t stream);
 
+/* k-means fitted on the device, and the two scores read off a fitted partition (functional.kmeans_* / bin_test / cluster_scores,
+ * evaluate.Evaluator.kmeans_scores).  Nothing of this exists in the reference.  Rows X [n, d] and centres C [k, d] are device fp32,
+ * row-major, 1 <= n <= 131072, any d >= 1 (a width that is no multiple of 4 or a base that is not 16-byte aligned takes the scalar
+ * loads of the sweep), 1 <= k <= GGAN_KMEANS_MAX_K.  Squared Euclidean distances in float32 Gram form |x|^2 + |c|^2 - 2 x.c clamped at 0.
+ * No floating-point atomics, no result depends on the launch shape: repeated calls give the same bits.  No host synchronisation inside.
+ *   ggan_kmeans_seed    k-means++ from k uniforms u [k] (device fp64, in [0, 1), drawn by the caller): centre 0 is row floor(u[0] n);
+ *                       centre t the first row, in row order, whose running fp64 sum of mind exceeds u[t] * total, mind[r] the smallest
+ *                       distance of row r to the centres chosen so far; a total of 0 (every row coincides with a centre): row
+ *                       floor(u[t] n).  centres [k, d] = the rows, idx int32 [k] their indices.  The picked index stays on the device.
+ *   ggan_kmeans_pick    that pick alone, for a given mind float32 [n] and one uniform u[0]: idx[0].
+ *   ggan_kmeans_assign  assign int32 [n] = the nearest centre, a tie in distance to the LOWER centre index; dist float32 [n] that distance;
+ *                       inertia (may be NULL) = the sum of dist in fp64, a fixed order; prev (may be NULL; may BE assign) an earlier
+ *                       assignment: moved[0] is WRITTEN, the rows whose centre changed (all n without prev; moved may be NULL without
+ *                       prev); counts (may be NULL) int32 [k]: counts[c] += the rows assigned to c -- ADDED, the caller zeroes them, so that
+ *                       slabs of one set accumulate.  status[0] is WRITTEN: GGAN_KMEANS_NONFINITE if the squared norm of a row or of a
+ *                       centre, or a distance, is NaN or +-inf (the assignment is then still an index below k, and nothing faults), else 0.
+ *   ggan_kmeans_update  centres[c] = the mean of the rows with assign == c, counts int32 [k] WRITTEN; an empty cluster keeps the centre it
+ *                       had (centres are in / out).  Blocks of GGAN_KMEANS_ROW_BLOCK rows are summed in fp32 in row order, the blocks in
+ *                       fp64 in block order.  An assignment outside [0, k) belongs to no cluster.
+ *   ggan_kmeans_fit     seed, then `iters` times (assign, update), then a final assign; 0 <= iters <= GGAN_KMEANS_MAX_ITERS, a fixed count:
+ *                       inertia double [iters + 1] and moved int32 [iters + 1] are those of every assign (moved[0] = n), moved[iters] == 0
+ *                       says it converged; counts are those of the final assignment; status as ggan_kmeans_assign, over all of them.
+ *   ggan_bin_test       NDB (Richardson & Weiss 2018) of two histograms int32 [k]: out[0] = the bins whose two-proportion z statistic
+ *                       |p1 - p2| / se, se = sqrt(P (1 - P) (1/N1 + 1/N2)), exceeds z_threshold (a bin with se == 0 does not differ),
+ *                       out[1] = out[0] / k, out[2] = the Jensen-Shannon divergence of the two histograms in nats, 0 log 0 = 0; fp64, one
+ *                       workgroup, sums in bin order.  An empty histogram gives NaN.
+ *   ggan_cluster_scores assign, labels int32 [n] -> table int32 [k, classes] (WRITTEN, integer atomics), out[0] = purity = the sum over
+ *                       clusters of the largest cell over n, out[1] = NMI = I(U; V) / ((H(U) + H(V)) / 2), 1 when both entropies are 0;
+ *                       1 <= classes <= GGAN_KMEANS_MAX_CLASSES.  status[0] is WRITTEN: GGAN_KMEANS_BAD_INDEX for a label outside
+ *                       [0, classes) or an assignment outside [0, k) (never an index; out is then NaN), else 0.
+ * ws: ggan_kmeans_workspace(n, d, k) bytes of 16-byte aligned device scratch, the same for seed, assign, update and fit (0 = arguments out
+ * of range); its largest part, the update's block partials, is ceil(n / GGAN_KMEANS_ROW_BLOCK) k d floats.  Arguments out of range, a null
+ * pointer or a short or misaligned workspace return a negative code before any device work.
+ * Added without a version change: no existing entry point or struct is touched. */
+#define GGAN_KMEANS_MAX_K 128
+#define GGAN_KMEANS_MAX_CLASSES 32
+#define GGAN_KMEANS_ROW_BLOCK 512
+#define GGAN_KMEANS_MAX_ITERS 1000
+#define GGAN_KMEANS_NONFINITE 1
+#define GGAN_KMEANS_BAD_INDEX 2
+size_t ggan_kmeans_workspace(int n, int d, int k);
+int ggan_kmeans_seed(const float* X, int n, int d, int k, const double* u, float* centres, int32_t* idx, void* ws, size_t ws_bytes,
+                     ggan_stream_t stream);
+int ggan_kmeans_pick(const float* mind, int n, const double* u, int32_t* idx, ggan_stream_t stream);
+int ggan_kmeans_assign(const float* X, const float* C, int n, int d, int k, const int32_t* prev, int32_t* assign, float* dist, double* inertia,
+                       int32_t* moved, int32_t* counts, int32_t* status, void* ws, size_t ws_bytes, ggan_stream_t stream);
+int ggan_kmeans_update(const float* X, const int32_t* assign, int n, int d, int k, float* centres, int32_t* counts, void* ws, size_t ws_bytes,
+                       ggan_stream_t stream);
+int ggan_kmeans_fit(const float* X, int n, int d, int k, int iters, const double* u, float* centres, int32_t* idx, int32_t* assign,
+                    int32_t* counts, double* inertia, int32_t* moved, int32_t* status, void* ws, size_t ws_bytes, ggan_stream_t stream);
+int ggan_bin_test(const int32_t* counts_ref, const int32_t* counts_test, int k, double z_threshold, double* out, ggan_stream_t stream);
+int ggan_cluster_scores(const int32_t* assign, const int32_t* labels, int n, int k, int classes, int32_t* table, double* out, int32_t* status,
+                        ggan_stream_t stream);
+
 /* Stochastic encoder head, TYPE_Q = 'learn_std' (gan_inference_cifar10.py:173-188): std = exp(log_std), z = mean + eps * std; the backward
  * takes the gradients arriving at z and at std (either may be NULL). */
 int ggan_reparam_fwd(const float* mean, const float* log_std, const float* eps, float* z, float* std_out, size_t n, ggan_stream_t stream);

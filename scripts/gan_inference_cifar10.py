@@ -17,6 +17,7 @@ SETTINGS.update(run.probe_settings(__file__))   # the least-squares linear probe
 SETTINGS.update(run.frechet_settings(__file__))   # the Frechet distance of codes and of projected images, off when unset: dev frechet z / xr and their mean parts every $GGAN_FRECHET_EVERY iterations
 SETTINGS.update(run.swd_settings(__file__))   # the sliced Wasserstein distance of codes and of images in the full pixel space, off when unset: dev swd z / x and their max rows every $GGAN_SWD_EVERY iterations
 SETTINGS.update(run.classifier_settings(__file__))   # the classifier score of generated images, off when unset: dev classifier score x / score std x / score data / accuracy / frechet x every $GGAN_CLS_EVERY iterations (labelled data only)
+SETTINGS.update(run.kmeans_settings(__file__))   # NDB of the generated images and k-means clustering scores of the codes, off when unset: dev ndb x / ndb js x / ndb data / kmeans accuracy z / kmeans nmi z every $GGAN_KMEANS_EVERY iterations (the z rows: labelled data only)
 SETTINGS.update(run.ema_settings(__file__))      # $GGAN_EMA_DECAY: average the generator-side weights; $GGAN_EMA_EVAL = live | ema | both: which the passes score
 if len(sys.argv) > 1:
     SETTINGS['ITERS'] = int(sys.argv[1])
