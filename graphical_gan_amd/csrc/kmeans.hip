@@ -488,6 +488,7 @@ int assign_launch(const float* X, const float* C, int n, int d, int k, const int
     GGAN_LAUNCH("kmeans_norms", 2.0 * (P.T - r0) * d, 4.0 * (P.T - r0) * d, kmeans_norms_k, dim3(cdiv(P.T - r0, 4)), dim3(256), 0, st,
                 static_cast<const RowSets&>(P), W.norms, r0);
     const int rc = dispatch_vec(P.vec, [&](auto VEC) {
+        if (trace_sets_on()) trace_sweep("kmeans_assign", 0, decltype(VEC)::value, P, dim3(nbq, 1));
         GGAN_LAUNCH("kmeans_assign", tile_flops(nbq, d), tile_bytes(nbq, d), (kmeans_assign_k<decltype(VEC)::value>), dim3(nbq, 1), dim3(256), 0,
                     st, P);
         return 0;

@@ -120,6 +120,7 @@ int ggan_knn_lists(const float* Q, const float* C, int m, int n, int d, int k, i
     P.skip = skip_diag ? 1 : 0;
     return dispatch_k_vec(k, P.vec, [&](auto K, auto VEC) {
         constexpr int kk = decltype(K)::value;
+        if (trace_sets_on()) trace_sweep("knn_lists", kk, decltype(VEC)::value, P, L.grid);
         GGAN_LAUNCH("knn_lists", L.flops, L.bytes, (knn_lists_k<kk, decltype(VEC)::value>), L.grid, dim3(256), 0, st, P);
         GGAN_LAUNCH("knn_lists_final", 0, 8.0 * P.S * kk * m, knn_lists_final_k<kk>, dim3(cdiv(m, 256)), dim3(256), 0, st, (const nkey*)P.pk, m,
                     P.S, idx, d2);

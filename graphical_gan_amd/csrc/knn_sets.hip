@@ -135,6 +135,7 @@ int ggan_knn_radii(const float* Z, int n, int d, int k, float* r2, void* ws, siz
     P.pf = (float*)L.part;
     return dispatch_k_vec(k, P.vec, [&](auto K, auto VEC) {
         constexpr int kk = decltype(K)::value;
+        if (trace_sets_on()) trace_sweep("knn_radii", kk, decltype(VEC)::value, P, L.grid);
         GGAN_LAUNCH("knn_radii", L.flops, L.bytes, (knn_radii_k<kk, decltype(VEC)::value>), L.grid, dim3(256), 0, st, P);
         GGAN_LAUNCH("knn_final", 0, 4.0 * P.S * kk * n, knn_final_k<kk>, dim3(cdiv(n, 256)), dim3(256), 0, st, (const float*)P.pf, n, P.S, r2);
         return 0;
@@ -162,6 +163,7 @@ int ggan_ball_counts(const float* A, const float* B, int m, int n, int d, const 
     P.pf = (float*)L.part;
     P.pi = (int*)((char*)L.part + (((size_t)P.S * m * 4 + 15) & ~(size_t)15));
     if (const int rc = dispatch_vec(P.vec, [&](auto VEC) {
+            if (trace_sets_on()) trace_sweep("ball_counts", 0, decltype(VEC)::value, P, L.grid);
             GGAN_LAUNCH("ball_counts", L.flops, L.bytes, ball_counts_k<decltype(VEC)::value>, L.grid, dim3(256), 0, st, P);
             return 0;
         }))

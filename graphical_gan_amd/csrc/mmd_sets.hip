@@ -164,6 +164,7 @@ int ggan_mix_rbf_sums(const float* X, const float* Y, int m, int n, int d, const
     // tiles computed: nb diagonal ones and nb (nb - 1) / 2 pairs
     const double tiles = 0.5 * (double)P.nb * (P.nb + 1);
     if (const int rc = dispatch_k_vec(ns, P.vec, [&](auto NS, auto VEC) {
+            if (trace_sets_on()) trace_sets("mmd_set_sums", decltype(NS)::value, decltype(VEC)::value, P, nullptr, P.nb, P.S, dim3(P.nb, P.S));
             GGAN_LAUNCH("mmd_set_sums", tile_flops(tiles, d), tile_bytes(tiles, d), (set_sums_k<decltype(NS)::value, decltype(VEC)::value>),
                         dim3(P.nb, P.S), dim3(256), 0, st, P);
             return 0;

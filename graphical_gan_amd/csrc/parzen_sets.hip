@@ -140,6 +140,7 @@ int ggan_parzen_lse(const float* Q, const float* S, int m, int n, int d, const f
         P.c2[g] = (float)(-1.4426950408889634 / (2.0 * sg * sg));
     }
     if (const int rc = dispatch_vec(P.vec, [&](auto VEC) {
+            if (trace_sets_on()) trace_sweep("parzen_lse", ns, decltype(VEC)::value, P, L.grid);
             GGAN_LAUNCH("parzen_lse", L.flops, L.bytes, parzen_lse_k<decltype(VEC)::value>, L.grid, dim3(256), 0, st, P);
             return 0;
         }))

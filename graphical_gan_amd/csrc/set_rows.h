@@ -2,6 +2,8 @@
 // row-major fp32 sets, its branch-free clamped loads, the tile constants, the squared-norm pre-pass, the 128 x 128 Gram tile, the walk over
 // a lane's accumulators, the query / candidate sweep with its sorted K-smallest lists, and the host preamble of the five entry points.
 #pragma once
+#include <cstdio>
+#include <cstdlib>
 #include <type_traits>
 #include "common.h"
 
@@ -317,6 +319,22 @@ inline int sweep_setup(SweepParams& P, SweepLaunch& L, const char* name, const f
     L.bytes = tile_bytes(tiles, d);
     L.part = (char*)ws + norms_bytes(P.T);
     return 0;
+}
+
+// GGAN_TRACE_SETS=1: one stderr line per launch of a Gram-sweep kernel with what its name cannot show -- the template instance (k: K or NS,
+// Parzen's run-time ns, 0 where the kernel has none; vec: the loader), the width, the row and block counts, the splits and the grid.
+// W == nullptr: the symmetric walk of mmd_sets.hip over the nb blocks of Z (rows m, T); else a query / candidate sweep (rows nq, nc, c0;
+// blocks grid.x, nbc).  Diagnostic only (tests/test_sets_dispatch_gpu.py reads the lines); looked up per launch on the host, like
+// GGAN_TRACE_GEMM.
+inline bool trace_sets_on() { return getenv("GGAN_TRACE_SETS") != nullptr; }
+inline void trace_sets(const char* name, int k, bool vec, const RowSets& P, const SweepParams* W, int nb, int S, dim3 grid) {
+    fprintf(stderr, "[ggan] sets %s k=%d vec=%d d=%d", name, k, (int)vec, P.d);
+    if (W) fprintf(stderr, " nq=%d nc=%d c0=%d nbq=%u nbc=%d", W->nq, W->nc, W->c0, grid.x, W->nbc);
+    else fprintf(stderr, " m=%d T=%d nb=%d", P.m, P.T, nb);
+    fprintf(stderr, " S=%d grid=(%u,%u)\n", S, grid.x, grid.y);
+}
+inline void trace_sweep(const char* name, int k, bool vec, const SweepParams& P, dim3 grid) {
+    trace_sets(name, k, vec, P, &P, 0, P.S, grid);
 }
 
 // f(std::bool_constant<VEC>) -> status for the run-time vec; f(std::integral_constant<int, K>, std::bool_constant<VEC>) with 1 <= k <= 8
