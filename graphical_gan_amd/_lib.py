@@ -94,6 +94,12 @@ SIGNATURES = {
     'ggan_probe_normal': (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
     'ggan_probe_solve': (_I, [_P, _P, _P, _I, _I, _I, _F, _P, _P, _P, _P]),
     'ggan_probe_predict': (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    'ggan_wprobe_moments_workspace': (_Z, [_I, _I, _I]),
+    'ggan_wprobe_moments': (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
+    'ggan_wprobe_normal': (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
+    'ggan_wprobe_factor': (_I, [_P, _I, _F, _P, _P]),
+    'ggan_wprobe_solve': (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    'ggan_wprobe_predict': (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     'ggan_frechet_moments_workspace': (_Z, [_I, _I]),
     'ggan_frechet_moments': (_I, [_P, _I, _I, _P, _P, _P, _P, _Z, _P]),
     'ggan_frechet_distance_workspace': (_Z, [_I]),

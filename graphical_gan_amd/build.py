@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libggan.so')
 STAMP = os.path.join(HERE, '.libggan.stamp')
-SOURCES = ['runtime.hip', 'pointwise.hip', 'losses.hip', 'optim.hip', 'latent.hip', 'penalty_tail.hip', 'bn.hip', 'linear_bn.hip', 'gemm.hip', 'conv_naive.hip', 'conv_corr.hip', 'conv_dg16.hip', 'conv_wgrad.hip', 'conv_wgrad_split.hip', 'conv_thin.hip', 'conv_api.hip', 'conv3d.hip', 'dynscan.hip', 'video_sheet.hip', 'tsne.hip', 'mmd_sets.hip', 'knn_sets.hip', 'knn_lists.hip', 'parzen_sets.hip', 'ssim_pairs.hip', 'probe_fit.hip', 'frechet.hip', 'swd.hip', 'class_score.hip', 'kmeans.hip']
+SOURCES = ['runtime.hip', 'pointwise.hip', 'losses.hip', 'optim.hip', 'latent.hip', 'penalty_tail.hip', 'bn.hip', 'linear_bn.hip', 'gemm.hip', 'conv_naive.hip', 'conv_corr.hip', 'conv_dg16.hip', 'conv_wgrad.hip', 'conv_wgrad_split.hip', 'conv_thin.hip', 'conv_api.hip', 'conv3d.hip', 'dynscan.hip', 'video_sheet.hip', 'tsne.hip', 'mmd_sets.hip', 'knn_sets.hip', 'knn_lists.hip', 'parzen_sets.hip', 'ssim_pairs.hip', 'probe_fit.hip', 'probe_wide.hip', 'frechet.hip', 'swd.hip', 'class_score.hip', 'kmeans.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=on', '-Wall', '-Wno-unused-function']
 EXTRA_FLAGS = {'conv_wgrad_split.hip': ['-mllvm', '-amdgpu-mfma-vgpr-form']}
 if os.environ.get('GGAN_BUILD_DIAG'):       # timing experiments only: compiles GGAN_SKIP_KERNELS in

@@ -33,6 +33,8 @@
                      scored on q_z of the labelled dev set, on its own fit rows, and (xr) the same probe on a fixed random projection of
                      the pixels to DIM_LATENT columns.  A pass of its own, not a row of SET_SCORES: it needs a second split and a fit
                      step, and draws its noise from a state of its own, so no other pass's values move.  Not a pass of the reference.
+                     With PROBE_WIDE also PROBE_WIDE_KEYS: the same probe on the pixels (x) and on the Extractor's top activations (h),
+                     up to 4096 columns (functional.lsq_probe_fit_wide), from the same forward pass.
   frechet_scores     `dev frechet z` / `dev frechet mean z` / `dev frechet xr` / `dev frechet mean xr`: the Frechet distance between Gaussians
                      fitted to two sets -- |dmu|^2 + tr S1 + tr S2 - 2 tr (S1 S2)^(1/2), the "FD" of FID, functional.frechet_distance -- of
                      q_z against as many prior draws (z) and of the dev images against as many generated ones, both through one fixed
@@ -108,6 +110,7 @@ PROBE_RIDGE = 1e-2        # its ridge, on standardised features (settings: PROBE
 PROBE_SLAB_ROWS = 10000   # images it keeps on the device at a time: only the codes of a slab stay
 PROBE_SEED = 104729       # offset of its own noise state, and of its projection matrix, from the evaluator's seed
 PROBE_KEYS = ('dev probe accuracy z', 'fit probe accuracy z', 'dev probe accuracy xr')
+PROBE_WIDE_KEYS = ('dev probe accuracy x', 'fit probe accuracy x', 'dev probe accuracy h', 'fit probe accuracy h')      # with PROBE_WIDE, after PROBE_KEYS
 FRECHET_MAX_ROWS = 10000  # rows per set of the frechet_scores pass (settings: FRECHET_MAX_ROWS)
 FRECHET_PROJ_DIM = 128    # columns of its fixed random projection of the pixels: functional.FRECHET_MAX_DIM, whatever DIM_LATENT is
 FRECHET_SEED = 130003     # offset of its own noise state, and of its projection matrix, from the evaluator's seed
@@ -627,9 +630,11 @@ class Evaluator(_Passes):
             self._probe_matrix = torch.as_tensor(P.astype(np.float32)).to(self.device)
         return self._probe_matrix
 
-    def _probe_codes(self, batches, rows):
+    def _probe_codes(self, batches, rows, wide=()):
         """z = q_z (as _score_sets computes sets['z']), xr = real_x through _probe_projection and y = the int32 labels of the leading full
-        minibatches, at most `rows` rows -> device tensors.  The images are staged PROBE_SLAB_ROWS rows at a time; only the codes stay."""
+        minibatches, at most `rows` rows -> device tensors.  The images are staged PROBE_SLAB_ROWS rows at a time; only the codes stay.
+        wide: which of 'x' (real_x flattened, in the scale the model reads) and 'h' (the Extractor's top activations) stay too, from the
+        SAME forward pass -- 4 rows (OUTPUT_DIM + flat) bytes on the device until the pass returns."""
         c = self.cfg
         B = c.B
         full = [b for b in batches if _split(b)[0].shape[0] == B]
@@ -640,6 +645,8 @@ class Evaluator(_Passes):
             raise ValueError('the probe takes at most %d rows, got %d' % (F.PROBE_MAX_ROWS, n * B))
         new = lambda w: torch.empty((n * B, w), dtype=torch.float32, device=self.device)
         out = dict(z=new(c.dim_latent), xr=new(c.dim_latent), y=torch.empty((n * B,), dtype=torch.int32, device=self.device))
+        out.update({k: new(c.output_dim if k == 'x' else c.flat) for k in wide})
+        top = {'return_top': True} if 'h' in wide else {}
         per, proj = max(1, PROBE_SLAB_ROWS // B), self._probe_projection()
         for s0 in range(0, n, per):
             X, Y = self._stage(full[s0:min(n, s0 + per)], want_labels=True)
@@ -649,12 +656,18 @@ class Evaluator(_Passes):
                 self.model.set_batch(self.feed, X[i])
                 self.model.sample_noise(self.feed)
                 real_x = self.model.real_x(self.feed)
-                q = self.model.Extractor(real_x, eps=self.feed['q_eps']) if c.agg else self.model.Extractor(real_x)
+                q = self.model.Extractor(real_x, eps=self.feed['q_eps'], **top) if c.agg else self.model.Extractor(real_x, **top)
+                if top:
+                    q, h = q
+                    out['h'][at].copy_(h)
                 out['z'][at].copy_(q[0] if isinstance(q, tuple) else q)
-                out['xr'][at].copy_(F.Gemm.apply(real_x.float().reshape(B, -1).contiguous(), proj, None, False, False, F.ACT_NONE, 0.0))
+                flat_x = real_x.float().reshape(B, -1).contiguous()
+                out['xr'][at].copy_(F.Gemm.apply(flat_x, proj, None, False, False, F.ACT_NONE, 0.0))
+                if 'x' in wide:
+                    out['x'][at].copy_(flat_x)
         return out
 
-    def probe_scores(self, fit_batches, dev_batches, return_fit=False):
+    def probe_scores(self, fit_batches, dev_batches, return_fit=False, wide=False):
         """{'dev probe accuracy z', 'fit probe accuracy z', 'dev probe accuracy xr'}: a least-squares linear probe (functional.lsq_probe_fit:
         the ridge-regularised least-squares classifier on standardised columns, ridge PROBE_RIDGE, in closed form -- neither logistic
         regression nor an SVM) fitted on q_z of the leading PROBE_FIT_ROWS rows of the labelled TRAINING minibatches fit_batches and scored on
@@ -664,11 +677,22 @@ class Evaluator(_Passes):
         accuracy z.  The pass draws from a noise state of its own, swapped into the feed while it runs: every other pass logs the same values
         whether it is on or not.  ONE host synchronisation; a raised status word (a label out of range, a non-finite moment, a failed
         factorisation: a diverged model) gives nan and one printed message, no exception.
-        return_fit: (values, {fit, fit_xr: the ProbeFit records, fit_z, fit_xr_rows, fit_y, dev_z, dev_xr, dev_y: the device rows})."""
+        return_fit: (values, {fit, fit_xr: the ProbeFit records, fit_z, fit_xr_rows, fit_y, dev_z, dev_xr, dev_y: the device rows}).
+        wide (or the setting PROBE_WIDE): PROBE_WIDE_KEYS after the three -- the same classifier (functional.lsq_probe_fit_wide, ridge
+        PROBE_WIDE_RIDGE, default PROBE_RIDGE) on the pixels x themselves, real_x flattened, and on h, the Extractor's top activations
+        (the [B, flat] rows Extractor.Output reads), dev and fit each.  Both come from the forward pass that yields z: no second Extractor
+        call, no further noise draw, and the three values above keep their bits.  The rows stay on the device for the pass: at the defaults
+        up to 10000 x (3072 + 4096) x 4 bytes = 287 MB per split, plus 134 MB for a 4096-column fit.  A width above
+        functional.WPROBE_MAX_DIM skips its pair with one message.  Still ONE host synchronisation.  return_fit gains fit_x, fit_h (the
+        records) and fit_x_rows, fit_h_rows, dev_x, dev_h."""
         S = self.S
         ridge = float(S.get('PROBE_RIDGE', PROBE_RIDGE))
         if not ridge > 0.0:
             raise ValueError('PROBE_RIDGE = %s: a positive number expected' % ridge)
+        wide = bool(wide or S.get('PROBE_WIDE'))
+        wide_ridge = float(S.get('PROBE_WIDE_RIDGE', ridge))
+        if wide and not wide_ridge > 0.0:
+            raise ValueError('PROBE_WIDE_RIDGE = %s: a positive number expected' % wide_ridge)
         labels = [_split(b)[1] for b in list(fit_batches) + list(dev_batches)]
         if not fit_batches or not dev_batches or any(y is None for y in labels):
             raise ValueError('the probe needs labelled minibatches on both sides')
@@ -679,24 +703,39 @@ class Evaluator(_Passes):
             if self._probe_rng is None:
                 self._probe_rng = F.noise_state(self.device, int(S.get('SEED', 0)) + EVAL_SEED + PROBE_SEED)
             shared, self.feed['rng_state'] = self.feed['rng_state'], self._probe_rng
+            sets = ()
+            if wide:
+                widths = dict(x=self.cfg.output_dim, h=self.cfg.flat)
+                sets = tuple(k for k in ('x', 'h') if widths[k] <= F.WPROBE_MAX_DIM)
+                for k in widths:
+                    if k not in sets:
+                        print('[evaluate] probe accuracy %s skipped: %d columns, the wide probe takes at most %d' % (k, widths[k], F.WPROBE_MAX_DIM))
             try:
-                fit = self._probe_codes(fit_batches, S.get('PROBE_FIT_ROWS', PROBE_FIT_ROWS))
-                dev = self._probe_codes(dev_batches, S.get('PROBE_MAX_ROWS', PROBE_MAX_ROWS))
+                fit = self._probe_codes(fit_batches, S.get('PROBE_FIT_ROWS', PROBE_FIT_ROWS), sets)
+                dev = self._probe_codes(dev_batches, S.get('PROBE_MAX_ROWS', PROBE_MAX_ROWS), sets)
             finally:
                 self.feed['rng_state'] = shared
             pz = F.lsq_probe_fit(fit['z'], fit['y'], classes, ridge)
             px = F.lsq_probe_fit(fit['xr'], fit['y'], classes, ridge)
             hits = [F.lsq_probe_predict(pz, dev['z'], dev['y']), F.lsq_probe_predict(pz, fit['z'], fit['y']),
                     F.lsq_probe_predict(px, dev['xr'], dev['y'])]
-            host = torch.cat(hits + [pz.status, px.status]).cpu().numpy()
-        rows = (dev['y'].shape[0], fit['y'].shape[0], dev['y'].shape[0])
-        status = (int(host[3]), int(host[3]), int(host[4]))
+            pw = {k: F.lsq_probe_fit_wide(fit[k], fit['y'], classes, wide_ridge) for k in sets}
+            for k in sets:
+                hits += [F.lsq_probe_predict_wide(pw[k], dev[k], dev['y']), F.lsq_probe_predict_wide(pw[k], fit[k], fit['y'])]
+            host = torch.cat(hits + [pz.status, px.status] + [pw[k].status for k in sets]).cpu().numpy()
+        nh = len(hits)
+        rows = (dev['y'].shape[0], fit['y'].shape[0], dev['y'].shape[0]) + (dev['y'].shape[0], fit['y'].shape[0]) * len(sets)
+        keys = PROBE_KEYS + tuple(k for k in PROBE_WIDE_KEYS if k[-1] in sets)
+        status = (int(host[nh]), int(host[nh]), int(host[nh + 1])) + tuple(int(host[nh + 2 + i // 2]) for i in range(2 * len(sets)))
         if any(status):
-            print('[evaluate] probe: status %d (z) / %d (xr) -- 1: a label out of range, 2: a non-finite moment or entry, 4: a pivot that is not '
-                  'positive -- its values are nan' % (status[0], status[2]))
-        res = {k: (float('nan') if st else int(h) / float(n)) for k, h, n, st in zip(PROBE_KEYS, host[:3], rows, status)}
+            print('[evaluate] probe: status %d (z) / %d (xr)%s -- 1: a label out of range, 2: a non-finite moment or entry, 4: a pivot that is not '
+                  'positive -- its values are nan' % (status[0], status[2], ''.join(' / %d (%s)' % (status[3 + 2 * i], k) for i, k in enumerate(sets))))
+        res = {k: (float('nan') if st else int(h) / float(n)) for k, h, n, st in zip(keys, host[:nh], rows, status)}
         if return_fit:
-            return res, dict(fit=pz, fit_xr=px, fit_z=fit['z'], fit_xr_rows=fit['xr'], fit_y=fit['y'], dev_z=dev['z'], dev_xr=dev['xr'], dev_y=dev['y'])
+            got = dict(fit=pz, fit_xr=px, fit_z=fit['z'], fit_xr_rows=fit['xr'], fit_y=fit['y'], dev_z=dev['z'], dev_xr=dev['xr'], dev_y=dev['y'])
+            for k in sets:
+                got.update({'fit_' + k: pw[k], 'fit_%s_rows' % k: fit[k], 'dev_' + k: dev[k]})
+            return res, got
         return res
 
     _frechet_rng = _frechet_matrix = None     # the Frechet pass's own noise state and projection matrix, made by its first call
@@ -1426,6 +1465,7 @@ def main(argv=None):
     for row in SET_SCORES:
         ap.add_argument('--' + row.name, action='store_true', help=row.help)
     ap.add_argument('--probe', action='store_true', help='also fit a least-squares linear probe on the codes of labelled training rows and score it on the labelled dev set (dev probe accuracy z / fit probe accuracy z / dev probe accuracy xr; image scripts with labelled data)')
+    ap.add_argument('--probe-wide', action='store_true', help='implies --probe; also fit the same probe on the pixels themselves and on the top activations of the Extractor (dev / fit probe accuracy x and h; up to 4096 columns)')
     ap.add_argument('--frechet', action='store_true', help='also score the dev set by the Frechet distance between Gaussians fitted to q_z and prior draws, and to randomly projected dev and generated images (dev frechet z / xr and their mean parts; image scripts; not comparable with a published FID)')
     ap.add_argument('--swd', action='store_true', help='also score the dev set by the sliced Wasserstein distance of q_z against prior draws and of the dev images against generated ones in the full pixel space, over fixed random unit directions (dev swd z / x and their max rows; image scripts; not comparable with a published SWD)')
     ap.add_argument('--cls', action='store_true', help='also score 50000 generated images by the inception-score formula under a small classifier fitted on the labelled training rows (or loaded from $GGAN_CLS_CKPT), with the same score of the dev images, its accuracy and the Frechet distance of its features (dev classifier score x / score std x / score data / accuracy / frechet x; image scripts with labelled data; not comparable with a published inception score or FID)')
@@ -1449,7 +1489,7 @@ def main(argv=None):
         for row in SET_SCORES:
             if getattr(a, row.name) and row.sequences is not True:
                 ap.error('--%s: %s' % (row.name, row.sequences))
-        if a.probe:
+        if a.probe or a.probe_wide:
             ap.error('--probe: %s' % _NO_CODE)
         if a.frechet:
             ap.error('--frechet: %s' % _NO_CODE)
@@ -1486,16 +1526,16 @@ def main(argv=None):
         # the checkpoint's live ones), and the evaluators only name what they write
         tr.load_params(ema)
         tr.ema_loaded = True
-    res = evaluate_once(tr, S, out_dir=a.out_dir, manifold=a.manifold, probe=a.probe, frechet=a.frechet, swd=a.swd, cls=a.cls, kmeans=a.kmeans, **{row.name: getattr(a, row.name) for row in SET_SCORES})
+    res = evaluate_once(tr, S, out_dir=a.out_dir, manifold=a.manifold, probe=a.probe or a.probe_wide, probe_wide=a.probe_wide, frechet=a.frechet, swd=a.swd, cls=a.cls, kmeans=a.kmeans, **{row.name: getattr(a, row.name) for row in SET_SCORES})
     for k in sorted(res):
         print('%s\t%s' % (k, res[k]))
     return res
 
 
-def evaluate_once(tr, S, out_dir=None, frame='eval', manifold=False, probe=False, frechet=False, swd=False, cls=False, kmeans=False, **scores):
+def evaluate_once(tr, S, out_dir=None, frame='eval', manifold=False, probe=False, probe_wide=False, frechet=False, swd=False, cls=False, kmeans=False, **scores):
     """every pass the script's data allow, once -> {name: value}; manifold: the latent-space pictures too (labelled dev data only);
     probe: the three values of Evaluator.probe_scores too, after the set-level scores (image scripts; skipped with one message where the
-    dev set or the training split has no labels); frechet: the four values of Evaluator.frechet_scores too, after those (image scripts; no
+    dev set or the training split has no labels); probe_wide: implies probe, and the four values of PROBE_WIDE_KEYS after its three; frechet: the four values of Evaluator.frechet_scores too, after those (image scripts; no
     labels needed); swd: the four values of Evaluator.swd_scores too, after those (image scripts; no labels needed); cls: the five values of
     Evaluator.classifier_scores too, after those (image scripts; skipped with one message where the dev set or the training split has no labels);
     kmeans: the values of Evaluator.kmeans_scores too, after those (image scripts; the two z rows need a labelled dev set);
@@ -1507,7 +1547,7 @@ def evaluate_once(tr, S, out_dir=None, frame='eval', manifold=False, probe=False
     from . import run
     ema_names = bool(getattr(tr, 'ema_loaded', False))
     if S['DATASET'] in run.SEQUENCE_DATASETS:       # the video passes: files only (train_data: the first dev minibatch)
-        if probe:
+        if probe or probe_wide:
             raise ValueError('probe: %s' % _NO_CODE)
         if frechet:
             raise ValueError('frechet: %s' % _NO_CODE)
@@ -1540,12 +1580,12 @@ def evaluate_once(tr, S, out_dir=None, frame='eval', manifold=False, probe=False
             scores[row.name] = False
     if any(scores.values()):
         res.update(ev.tag(ev.set_scores(dev, **scores)))
-    if probe:
+    if probe or probe_wide:
         fit = run.probe_sets(S) if run.labelled(dev) else None
         if not fit:
             print('[evaluate] dev probe accuracy skipped: no labelled dev set and training split')
         else:
-            res.update(ev.tag(ev.probe_scores(fit, dev)))
+            res.update(ev.tag(ev.probe_scores(fit, dev, wide=probe_wide)))
     if frechet:
         res.update(ev.tag(ev.frechet_scores(dev)))
     if swd:

@@ -27,7 +27,7 @@ from .linear import (  # noqa: F401
     gemm_colsum_, linear)
 from .norm import BatchNormTrain, BatchNormGroupedTrain, BatchNormBwd, LinearBatchNormRows, _all_gather_rows, SyncBatchNormTrain  # noqa: F401
 from .rows import (  # noqa: F401
-    JoinRows, Fanout, fanout, SplitRows, CastScaleI32, Axpby, MixMean, GmmLatent, GmmLatentST, MixRbfMmd2, MixRbfMmd2Unbiased, mix_rbf_sums, mmd2_from_sums, MMD_FUSED_MAX_ROWS, knn_radii, ball_counts, prdc, PRDC_MAX_K, knn_lists, knn_vote, knn_accuracy, KNN_MAX_K, KNN_MAX_CLASSES, parzen_lse, parzen_ll, PARZEN_MAX_SIGMAS, ssim_pairs, psnr_from_mse, lsq_probe_fit, lsq_probe_predict, ProbeFit, PROBE_MAX_DIM, PROBE_MAX_CLASSES, PROBE_MAX_ROWS, PROBE_ROW_BLOCK, PROBE_BAD_LABEL, PROBE_NONFINITE, PROBE_BAD_PIVOT, frechet_moments, frechet_distance, FRECHET_MAX_DIM, FRECHET_MAX_ROWS, FRECHET_NONFINITE, FRECHET_NOT_CONVERGED, sliced_wasserstein_projected, sliced_wasserstein, SWD_MAX_ROWS, SWD_MAX_DIRS, SWD_NONFINITE, Reparam, AGG_KL, AGG_IKL, AGG_JSD,
+    JoinRows, Fanout, fanout, SplitRows, CastScaleI32, Axpby, MixMean, GmmLatent, GmmLatentST, MixRbfMmd2, MixRbfMmd2Unbiased, mix_rbf_sums, mmd2_from_sums, MMD_FUSED_MAX_ROWS, knn_radii, ball_counts, prdc, PRDC_MAX_K, knn_lists, knn_vote, knn_accuracy, KNN_MAX_K, KNN_MAX_CLASSES, parzen_lse, parzen_ll, PARZEN_MAX_SIGMAS, ssim_pairs, psnr_from_mse, lsq_probe_fit, lsq_probe_predict, ProbeFit, PROBE_MAX_DIM, PROBE_MAX_CLASSES, PROBE_MAX_ROWS, PROBE_ROW_BLOCK, PROBE_BAD_LABEL, PROBE_NONFINITE, PROBE_BAD_PIVOT, lsq_probe_fit_wide, lsq_probe_predict_wide, WPROBE_MAX_DIM, WPROBE_TILE, WPROBE_PANEL, WPROBE_CHUNK, frechet_moments, frechet_distance, FRECHET_MAX_DIM, FRECHET_MAX_ROWS, FRECHET_NONFINITE, FRECHET_NOT_CONVERGED, sliced_wasserstein_projected, sliced_wasserstein, SWD_MAX_ROWS, SWD_MAX_DIRS, SWD_NONFINITE, Reparam, AGG_KL, AGG_IKL, AGG_JSD,
     AggDiv, RowLerp, gmm_posterior_assign_, cluster_accuracy_, sheet_grid, video_sheet_u8)
 from .conv3d import _dims3, Im2Col3d, Col2Im3d, _conv3d_patch, _igemm_ok, Conv3dImplicit, conv3d  # noqa: F401
 from .losses import BceSum, Distance, MeanSum, GradPenalty  # noqa: F401

@@ -652,6 +652,67 @@ def lsq_probe_predict(fit, z, y=None, return_pred=False):
     return (correct, pred) if return_pred else correct
 
 
+WPROBE_MAX_DIM, WPROBE_TILE, WPROBE_PANEL, WPROBE_CHUNK = 4096, 64, 64, 128      # include/ggan.h: GGAN_WPROBE_MAX_DIM / _TILE / _PANEL / _CHUNK
+
+
+def _wprobe_rows(name, z, y, d=None, least=1):
+    """_probe_rows with the wide chain's column range, 1 <= d <= WPROBE_MAX_DIM"""
+    if z.dim() != 2 or z.dtype != torch.float32 or z.shape[0] > PROBE_MAX_ROWS:
+        raise ValueError('%s: float32 rows [rows <= %d, d] expected, got %s %s' % (name, PROBE_MAX_ROWS, z.dtype, tuple(z.shape)))
+    if z.shape[0] < least:
+        raise ValueError('%s: at least %d rows expected, got %d' % (name, least, z.shape[0]))
+    if not 1 <= z.shape[1] <= WPROBE_MAX_DIM or (d is not None and z.shape[1] != d):
+        raise ValueError('%s: %s columns expected, got %d' % (name, '1 <= d <= %d' % WPROBE_MAX_DIM if d is None else d, z.shape[1]))
+    if y is not None:
+        y = _labels(name, 'y', y, z.shape[0], z.device)
+    _no_grad(name, [z])
+    return _c(z), y
+
+
+def lsq_probe_fit_wide(z, y, classes, ridge):
+    """lsq_probe_fit for 1 <= d <= WPROBE_MAX_DIM columns (ggan_wprobe_moments / _normal / _factor / _solve): the same classifier and the
+    same record, the normal equations and their Cholesky factor in float64 on the device (8 d (d + classes) bytes for the call: 134 MB at
+    d = 4096).  Device float32 / int32 inputs, nothing is read back, a failure is a bit of the record's status word.  Forward only."""
+    name = 'lsq_probe_fit_wide'
+    classes, ridge = int(classes), float(ridge)
+    if not 1 <= classes <= PROBE_MAX_CLASSES:
+        raise ValueError('%s: 1 <= classes <= %d expected, got %d' % (name, PROBE_MAX_CLASSES, classes))
+    if not (math.isfinite(ridge) and ridge > 0.0):
+        raise ValueError('%s: ridge must be finite and positive, got %s' % (name, ridge))
+    z, y = _wprobe_rows(name, z, y, least=2)
+    n, d = z.shape
+    dev = z.device
+    new = lambda shape, dt=torch.float32: torch.empty(shape, dtype=dt, device=dev)
+    fit = ProbeFit(new((d,)), new((d,)), new((d, classes)), new((classes,)), new((classes,), torch.int32), new((1,), torch.int32))
+    G, R = new((d, d), torch.float64), new((d, classes), torch.float64)
+    L = _L()
+    ws, nbytes = _workspace(L.ggan_wprobe_moments_workspace(n, d, classes), dev)
+    check(L.ggan_wprobe_moments(_p(z), _p(y), n, d, classes, _p(fit.mean), _p(fit.inv_std), _p(fit.counts), _p(fit.status), _p(ws), nbytes,
+                                _stream()), 'ggan_wprobe_moments')
+    check(L.ggan_wprobe_normal(_p(z), _p(y), n, d, classes, _p(fit.mean), _p(fit.inv_std), _p(G), _p(R), _stream()), 'ggan_wprobe_normal')
+    check(L.ggan_wprobe_factor(_p(G), d, ridge, _p(fit.status), _stream()), 'ggan_wprobe_factor')
+    check(L.ggan_wprobe_solve(_p(G), _p(R), _p(fit.counts), n, d, classes, _p(fit.W), _p(fit.bias), _p(fit.status), _stream()),
+          'ggan_wprobe_solve')
+    return fit
+
+
+def lsq_probe_predict_wide(fit, z, y=None, return_pred=False):
+    """lsq_probe_predict for a record of lsq_probe_fit_wide (ggan_wprobe_predict): the same arguments and results"""
+    name = 'lsq_probe_predict_wide'
+    d, classes = fit.W.shape
+    z, y = _wprobe_rows(name, z, y, d)
+    if any(t.device != z.device for t in fit):
+        raise ValueError('%s: the fit lives on %s, the rows on %s' % (name, fit.W.device, z.device))
+    m = z.shape[0]
+    pred = torch.empty((m,), dtype=torch.int32, device=z.device) if (return_pred or y is None) else None
+    correct = torch.empty((1,), dtype=torch.int32, device=z.device) if y is not None else None
+    check(_L().ggan_wprobe_predict(_p(z), _p(y), m, d, classes, _p(fit.mean), _p(fit.inv_std), _p(fit.W), _p(fit.bias), _p(pred), _p(correct),
+                                   _stream()), 'ggan_wprobe_predict')
+    if y is None:
+        return pred
+    return (correct, pred) if return_pred else correct
+
+
 FRECHET_MAX_DIM, FRECHET_MAX_ROWS = 128, 131072             # include/ggan.h: GGAN_FRECHET_MAX_DIM, the row range
 FRECHET_NONFINITE, FRECHET_NOT_CONVERGED = 1, 2             # ... and the bits of the status word
 

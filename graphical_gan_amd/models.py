@@ -287,10 +287,12 @@ class GraphicalGAN(object):
             ch = cout
         return out.reshape(-1, c.output_dim)
 
-    def Extractor(self, inputs, out_slot=None, eps=None, after_first=None):
+    def Extractor(self, inputs, out_slot=None, eps=None, after_first=None, return_top=False):
         """eps given (TYPE_Q = 'learn_std', gan_inference_cifar10.py:173-188): returns (mean + eps * std, mean, std), std = exp(Linear
         'Extractor.Std').  inputs may be a functional.PendingCast (the minibatch still int32 in the device ring: the first layer scales
-        it while staging); after_first: called once the first layer is issued (real_x exists from there on)."""
+        it while staging); after_first: called once the first layer is issued (real_x exists from there on).  return_top (the wide probe of
+        evaluate.Evaluator.probe_scores only; no training path and no captured graph passes it): (the result above, the [B, flat]
+        activations of the last conv layer that 'Extractor.Output' and 'Extractor.Std' read) -- the same launches, one more reference."""
         c = self.cfg
         out = inputs.reshape(-1, c.C, c.S, c.S)
         ch = c.C
@@ -310,8 +312,9 @@ class GraphicalGAN(object):
             log_std = lib.ops.linear.Linear('Extractor.Std', c.flat, c.dim_latent, out)
             mean = lib.ops.linear.Linear('Extractor.Output', c.flat, c.dim_latent, out)
             z, std = F.Reparam.apply(mean, log_std, eps)
-            return z, mean, std
-        return lib.ops.linear.Linear('Extractor.Output', c.flat, c.dim_latent, out, out=out_slot)
+            return ((z, mean, std), out) if return_top else (z, mean, std)
+        res = lib.ops.linear.Linear('Extractor.Output', c.flat, c.dim_latent, out, out=out_slot)
+        return (res, out) if return_top else res
 
     def Discriminator(self, x, z, grad_rows=None, twice=False, before_z=None, z_out=None):
         """grad_rows: only the first grad_rows images of x carry a gradient (generator steps: [fake; real]); twice: the result

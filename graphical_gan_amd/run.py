@@ -157,10 +157,14 @@ PROBE_DATA_SEED = 271828      # numpy's global RNG while the fit rows are drawn:
 
 def probe_settings(script):
     """{'PROBE_EVERY': N} for the eight image scripts when $GGAN_PROBE_EVERY = N is set, {} otherwise and for every other script (the
-    state-space scripts have no single code to probe)"""
+    state-space scripts have no single code to probe); with $GGAN_PROBE_WIDE = 1 as well, {'PROBE_WIDE': True} too: the pass then also
+    probes the pixels and the Extractor's top activations (evaluate.PROBE_WIDE_KEYS)"""
     name = os.path.splitext(os.path.basename(script))[0]
     n = os.environ.get('GGAN_PROBE_EVERY')
-    return {'PROBE_EVERY': int(n)} if n and name in _IMAGE_SCRIPTS else {}
+    out = {'PROBE_EVERY': int(n)} if n and name in _IMAGE_SCRIPTS else {}
+    if name in _IMAGE_SCRIPTS and os.environ.get('GGAN_PROBE_WIDE') == '1':
+        out['PROBE_WIDE'] = True
+    return out
 
 
 def probe_due(S, it):

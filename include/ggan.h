@@ -545,6 +545,43 @@ int ggan_probe_solve(const float* G, const float* R, const int32_t* counts, int 
 int ggan_probe_predict(const float* Z, const int32_t* y, int m, int d, int classes, const float* mean, const float* inv_std,
                        const float* W, const float* bias, int32_t* pred, int32_t* correct, ggan_stream_t stream);
 
+/* The wide twin of the probe chain: the same classifier, the same status bits, 1 <= d <= GGAN_WPROBE_MAX_DIM (pixels, the Extractor's top
+ * activations: functional.lsq_probe_fit_wide / lsq_probe_predict_wide, Evaluator.probe_scores with PROBE_WIDE).  classes, rows, n and ridge
+ * as above; G[d,d], R[d,classes] and the factor are device fp64 (8-byte aligned).  The summation orders:
+ *   ggan_wprobe_moments: as ggan_probe_moments for any d: a column's sum in fp64 in row order per block of GGAN_PROBE_ROW_BLOCK rows, the
+ *                        blocks in block order.  status[0] is WRITTEN.
+ *   ggan_wprobe_normal:  G and R in fp64.  One workgroup owns a pair (ti >= tj) of GGAN_WPROBE_TILE-column tiles and walks all row blocks:
+ *                        a block of GGAN_PROBE_ROW_BLOCK rows in fp32 in row order (v_mfma_f32_32x32x2_f32, the rows standardised as they
+ *                        are staged, columns past d as zeros), the blocks in fp64 in block order, / n.  No partial exists in memory; the
+ *                        upper triangle is the mirrored store of the lower: G is exactly symmetric.
+ *   ggan_wprobe_factor:  L L^T = G + ridge I in place on the lower triangle of G (the upper is left as it is), fp64, right-looking in
+ *                        panels of GGAN_WPROBE_PANEL columns: the diagonal block column by column in one workgroup's LDS, the panel
+ *                        below solved against it a row per thread, the trailing tiles updated by v_mfma_f64_16x16x4_f64.  No host
+ *                        synchronisation.  status[0] |= GGAN_PROBE_BAD_PIVOT for a pivot that is not positive (the factorisation goes on
+ *                        from a harmless one), GGAN_PROBE_NONFINITE for a non-finite entry.
+ *   ggan_wprobe_solve:   W = L^-T L^-1 R: one workgroup per right-hand side, a blocked sweep in steps of GGAN_WPROBE_PANEL rows, fp64,
+ *                        rounded once to fp32; bias[c] = counts[c] / n.  W is all NaN when status[0] carries GGAN_PROBE_NONFINITE or
+ *                        GGAN_PROBE_BAD_PIVOT (raised by any launch before, or here by a non-finite entry of R).
+ *   ggan_wprobe_predict: as ggan_probe_predict; a score is one fmaf chain in fp32 per chunk of GGAN_WPROBE_CHUNK columns (from the bias in
+ *                        the first chunk), the chunks added in fp64 in chunk order; for d <= GGAN_WPROBE_CHUNK it is ggan_probe_predict's.
+ * ws: ggan_wprobe_moments_workspace(n, d, classes) bytes of 16-byte aligned device scratch (0 = arguments out of range); the other entries
+ * need none.  No floating-point atomics: repeated calls give the same bits.  Arguments out of range, a null or misaligned pointer or a
+ * short workspace return a negative code before any device work.  Forward only.  Added without a version change. */
+#define GGAN_WPROBE_MAX_DIM 4096
+#define GGAN_WPROBE_TILE 64
+#define GGAN_WPROBE_PANEL 64
+#define GGAN_WPROBE_CHUNK 128
+size_t ggan_wprobe_moments_workspace(int n, int d, int classes);
+int ggan_wprobe_moments(const float* Z, const int32_t* y, int n, int d, int classes, float* mean, float* inv_std, int32_t* counts,
+                        int32_t* status, void* ws, size_t ws_bytes, ggan_stream_t stream);
+int ggan_wprobe_normal(const float* Z, const int32_t* y, int n, int d, int classes, const float* mean, const float* inv_std, double* G,
+                       double* R, ggan_stream_t stream);
+int ggan_wprobe_factor(double* G, int d, float ridge, int32_t* status, ggan_stream_t stream);
+int ggan_wprobe_solve(const double* L, const double* R, const int32_t* counts, int n, int d, int classes, float* W, float* bias,
+                      int32_t* status, ggan_stream_t stream);
+int ggan_wprobe_predict(const float* Z, const int32_t* y, int m, int d, int classes, const float* mean, const float* inv_std,
+                        const float* W, const float* bias, int32_t* pred, int32_t* correct, ggan_stream_t stream);
+
 /* Frechet distance between Gaussians fitted to two row sets, |mu1 - mu2|^2 + tr S1 + tr S2 - 2 tr (S1 S2)^(1/2) -- the "FD" of FID
  * (evaluate.Evaluator.frechet_scores, functional.frechet_moments / frechet_distance).  It stands in for the one number about samples the
  * reference publishes, tflib/inception_score.py (which needs a download), on the sets the reference draws as pictures in
